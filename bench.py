@@ -28,6 +28,11 @@ against the HBM bytes the offline PMC passes under profiles/ measured for that k
 host cores on a bounded sample.  At N = 1 with the default workload the same process then runs the
 other single-GPU BASELINE configs (cfg2 eager + replay, cfg3, cfg5 fp16 / fp32, the 512-graph shard
 of the headline) and reports them under `configs` (--no-configs skips them).
+
+--dump-outputs DIR writes what the last timed step of the headline workload computed -- its loss and the
+parameters, gradients and BatchNorm buffers it left in the model -- as DIR/<name>.npy (rank 0).  Every
+input (dataset, batch order, initial weights, dropout stream) is seeded, so the same arguments give the
+same inputs on every run and two builds can be compared array for array.
 """
 from __future__ import annotations
 
@@ -455,11 +460,41 @@ def projection_8gpu(headline_ms: float, shard_ms: float, gbatch: int = 4096) -> 
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir: str, model, loss) -> int:
+    """--dump-outputs: what the timed step handed back in its last step -- the loss it returned and the
+    state it left in the model (parameters, their gradients, BatchNorm buffers) -- as DIR/<name>.npy,
+    float64 where the tensor is float64 or integer, float32 otherwise.  Returns the number of arrays."""
+    import numpy as np
+    arrays = {"loss": loss.detach().reshape(1)}
+    for k, p in model.named_parameters():
+        arrays[f"param.{k}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{k}"] = p.grad.detach()
+    for k, v in model.named_buffers():
+        arrays[f"buffer.{k}"] = v.detach()
+    host = {}
+    for name, t in arrays.items():
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dump_dir, f"{name}.npy"), a)
+    return len(host)
+
+
 def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, batch: int = 0,
-                 label: str = None, extras: bool = True, e2e_dataset=None, dp_plumbing: bool = False) -> dict:
+                 label: str = None, extras: bool = True, e2e_dataset=None, dp_plumbing: bool = False,
+                 dump_dir: str = None) -> dict:
     """Warm up, time `args.steps` steps of workload `name` and return the JSON record (on every
     rank; only rank 0's is printed).  `label` names the record when it differs from the workload
-    key (the 512-graph shard of the headline)."""
+    key (the 512-graph shard of the headline).  `dump_dir`: rank 0 writes what the last timed step
+    computed there (dump_outputs) before anything else touches the model."""
     import connectome_gnn_amd as C
     from connectome_gnn_amd import _lib, dist as cdist, ops as cops
     from connectome_gnn_amd.resident import assemble_batch
@@ -607,6 +642,8 @@ def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, ba
         loss = step(args.warmup + i)
     fence()
     dt = time.perf_counter() - t0
+    if dump_dir and rank == 0:       # before the eager timing steps below move the parameters again
+        note(rank, f"dumped {dump_outputs(dump_dir, model, loss)} arrays of the last timed step to {dump_dir}")
     if graphed is not None:          # kernels inside a graph cannot be bracketed: time them eagerly
         _lib.TIMER = _lib.KernelTimer([dom])
         for i in range(4):
@@ -767,7 +804,13 @@ def main() -> None:
                          "per-rank step of a data-parallel run without the wire")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal only: every rank on cuda:0 (use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline workload computed (loss, parameters, "
+                         "gradients, BatchNorm buffers) to DIR/<name>.npy; inputs are seeded, so two builds "
+                         "compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.graph:
         args.launch = "graph"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -798,7 +841,7 @@ def main() -> None:
     dev = torch.device("cuda", local)
 
     out = run_workload(args, args.workload, rank, world, dev, launch=args.launch, batch=args.batch,
-                       e2e_dataset=e2e_dataset)
+                       e2e_dataset=e2e_dataset, dump_dir=args.dump_outputs)
     if world == 1 and headline_default and not args.no_configs:
         out["inference"] = []
         for label, key, data in (("cfg4-headline-gcn-4096x360-h64", args.workload, e2e_dataset),

@@ -804,7 +804,8 @@ def test_a_relu_tie_is_found_and_resolved():
     before = len(P.ARBITER["relu_ties"])
     P.assert_grads(grads, "sage", sd0, b, "tie-demo", g32=g32, g64=g64)
     # on the boxes this was written on rules (1)-(3) fail and exactly this tie resolves it; a host whose fp32
-    # matmul happens to round the tie the way the GPU does would pass without rule (4): both are fine
+    # matmul happens to round the tie the way the GPU does (rule (3) includes the single-threaded evaluation)
+    # would pass without rule (4): both are fine
     used = P.ARBITER["relu_ties"][before:]
     assert len(used) <= 1 and all("[('layer2', 931, 133)] decided" in u for u in used)
 

@@ -296,6 +296,25 @@ def test_bench_extra_configs_name_known_workloads():
     assert all(key in bench.WORKLOADS and launch in ("eager", "graph", "graph-dp", "auto", "trainer", "plain", "demo") for _, key, launch, _ in bench.EXTRA_CONFIGS)
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.py --dump-outputs: the loss plus every parameter, gradient and buffer the step left in the model,
+    one DIR/<name>.npy each, float32 (float64 for the integer step counter), values unchanged."""
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(5, 8), torch.nn.BatchNorm1d(8)).train()
+    loss = m(torch.randn(16, 5)).square().mean()
+    loss.backward()
+    n = bench.dump_outputs(str(tmp_path / "out"), m, loss)
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "out"))
+    assert n == len(names) == 12 and "loss" in names and "grad.0.weight" in names
+    assert "buffer.1.running_var" in names and "buffer.1.num_batches_tracked" in names
+    for f in names:
+        a = np.load(tmp_path / "out" / f"{f}.npy")
+        assert a.dtype == (np.float64 if f.endswith("num_batches_tracked") else np.float32), f
+    np.testing.assert_array_equal(np.load(tmp_path / "out" / "grad.0.weight.npy"), m[0].weight.grad.numpy())
+    assert float(np.load(tmp_path / "out" / "loss.npy")[0]) == float(loss.detach())
+
+
 def test_bench_rank_bookkeeping_for_eight_gpus():
     """The 8-GPU run nobody can rehearse on hardware: bench.py's rank bookkeeping driven for
     --gpus 8 with no GPU work -- shard sizes, launch=auto -> HIP-graph replay at 512 graphs per rank, the config
