@@ -21,13 +21,20 @@ before anything touches the GPU); under the driver's torchrun it just joins the 
 --launch auto replays a HIP graph of the step when the per-rank shard is small enough to be
 host-bound (< 2048 graphs), else launches eagerly.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel of the step, timed live
-with HIP events on its own stream (`frac` against SURVEY 8d's algorithmic bytes, `real_traffic_frac`
-against the HBM bytes the offline PMC passes under profiles/ measured for that kernel);
-`cpu_baseline` is the oracle (a port of the reference's pure-PyTorch CPU path) timed on this box's
-host cores on a bounded sample.  At N = 1 with the default workload the same process then runs the
-other single-GPU BASELINE configs (cfg2 eager + replay, cfg3, cfg5 fp16 / fp32, the 512-graph shard
-of the headline) and reports them under `configs` (--no-configs skips them).
+Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: it sets up,
+warms up, times the steps, writes --dump-outputs if asked and prints the line.  `roofline` is for
+the dominant kernel of the step, timed with HIP events around its launches inside the timed steps
+when they launch eagerly (`frac` against SURVEY 8d's algorithmic bytes, `real_traffic_frac` against
+the HBM bytes the offline PMC passes under profiles/ measured for that kernel); a replayed graph
+cannot be bracketed, so there it is null unless --full times a few eager steps of its own.
+
+--full adds everything else the benchmark measures, each in runs of its own after the headline:
+the kernel timing of a replayed step, the headline dataset relabelled by degree, the fresh-batch
+`end_to_end` legs, `cpu_baseline` (the oracle, a port of the reference's pure-PyTorch CPU path,
+timed on this box's host cores on a bounded sample) and, at N = 1 with the default workload,
+`inference` and the other single-GPU BASELINE configs (cfg2 eager + replay, cfg3, cfg5 fp16 / fp32,
+the 512-graph shard of the headline) under `configs`, with the 8-GPU `projection` built from them.
+--no-end-to-end, --no-cpu-baseline and --no-configs leave parts of that out.
 
 --dump-outputs DIR writes what the last timed step of the headline workload computed -- its loss and the
 parameters, gradients and BatchNorm buffers it left in the model -- as DIR/<name>.npy (rank 0).  Every
@@ -494,7 +501,9 @@ def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, ba
     """Warm up, time `args.steps` steps of workload `name` and return the JSON record (on every
     rank; only rank 0's is printed).  `label` names the record when it differs from the workload
     key (the 512-graph shard of the headline).  `dump_dir`: rank 0 writes what the last timed step
-    computed there (dump_outputs) before anything else touches the model."""
+    computed there (dump_outputs) before anything else touches the model.  Measurements that take
+    runs of their own (kernel timing of a replayed step, and with `extras` the degree-relabelled and
+    end-to-end legs) happen with --full only."""
     import connectome_gnn_amd as C
     from connectome_gnn_amd import _lib, dist as cdist, ops as cops
     from connectome_gnn_amd.resident import assemble_batch
@@ -644,7 +653,7 @@ def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, ba
     dt = time.perf_counter() - t0
     if dump_dir and rank == 0:       # before the eager timing steps below move the parameters again
         note(rank, f"dumped {dump_outputs(dump_dir, model, loss)} arrays of the last timed step to {dump_dir}")
-    if graphed is not None:          # kernels inside a graph cannot be bracketed: time them eagerly
+    if graphed is not None and args.full:   # kernels inside a graph cannot be bracketed: time them eagerly
         _lib.TIMER = _lib.KernelTimer([dom])
         for i in range(4):
             eager_step(i)
@@ -660,7 +669,7 @@ def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, ba
 
     graphs_per_s = global_batch * args.steps / dt
     bpg = algorithmic_bytes_per_graph(model_kind, n, e, hidden, elem)
-    kms = timer.ms(dom)
+    kms = timer.ms(dom) if timer is not None else []
     nn_, ee = bsz * n, bsz * e
     dom_bytes = dom_bytes_fn(nn_, ee)
     avg_ms = sum(kms) / max(len(kms), 1)
@@ -698,9 +707,11 @@ def run_workload(args, name: str, rank: int, world: int, dev, *, launch: str, ba
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "real_traffic_frac": real_frac,
                      "traffic_source": traffic_source,
-                     "algorithmic_bytes_per_launch": dom_bytes},
+                     "algorithmic_bytes_per_launch": dom_bytes} if timer is not None else None,
         "final_loss": final_loss,
     }
+    if not args.full:
+        return out
     if extras and rank == 0 and world == 1 and not args.no_end_to_end and graphed is None \
             and fused_kind == "tile" and args.node_order == "dataset":
         # the same step on the same graphs with every subject's nodes renumbered by degree
@@ -776,14 +787,17 @@ def main() -> None:
     ap.add_argument("--impl", default=os.environ.get("CGNN_IMPL", "auto"))
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
     ap.add_argument("--nbuf", type=int, default=2, help="distinct resident batches cycled through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure: kernel timing of a replayed "
+                         "step, degree relabelling, end-to-end legs, inference, the other configs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--sync-bn", action="store_true",
                     help="full-batch BN statistics across ranks (default OFF: per-rank BN, what stock DDP does)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: global batch fixed, split over ranks; weak: fixed batch per rank")
     ap.add_argument("--launch", default="auto", choices=["auto", "eager", "graph"],
                     help="graph: replay a HIP graph of the whole step (kernel timing then comes from a "
-                         "short eager pass after the timed region); auto: graph below 2048 graphs/rank")
+                         "short eager pass after the timed region, with --full); auto: graph below 2048 graphs/rank")
     ap.add_argument("--graph", action="store_true", help="same as --launch graph")
     ap.add_argument("--collectives", default="split", choices=["split", "captured"],
                     help="graph launch at N > 1: all-reduce between two graphs, or captured inside one")
@@ -792,12 +806,13 @@ def main() -> None:
     ap.add_argument("--optimizer", default="cgnn", choices=["cgnn", "torch"],
                     help="cgnn: connectome_gnn_amd.optim.Adam (one launch); torch: torch.optim.Adam(fused=True)")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the fresh-batch (assemble + structure build + step) measurement")
+                    help="with --full: skip the fresh-batch (assemble + structure build + step) measurement")
     ap.add_argument("--no-configs", action="store_true",
-                    help="headline only: skip the other single-GPU BASELINE configs (cfg2/3/5, 512-graph shard)")
+                    help="with --full: skip inference and the other single-GPU BASELINE configs (cfg2/3/5, "
+                         "512-graph shard)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--subjects", type=int, default=32768,
-                    help="subjects of the headline config's dataset for the end-to-end (loader-inclusive) "
+                    help="with --full: subjects of the headline config's dataset for the end-to-end (loader-inclusive) "
                          "measurement: BASELINE config 4 says 32768 (8 steps of 4096 per epoch on one GPU)")
     ap.add_argument("--dp-plumbing", action="store_true",
                     help="single rank with dist.GradSync in place (flat gradient buffer, exchange a no-op): the "
@@ -818,11 +833,11 @@ def main() -> None:
 
     from connectome_gnn_amd import dist as cdist
 
-    # BASELINE config 4's dataset (32,768 x 360-ROI subjects, 3.5 GB): generated on the host cores by forked
-    # workers NOW, before this process touches the GPU (a fork afterwards would share the device handles)
+    # --full: BASELINE config 4's dataset (32,768 x 360-ROI subjects, 3.5 GB): generated on the host cores by
+    # forked workers NOW, before this process touches the GPU (a fork afterwards would share the device handles)
     e2e_dataset = None
     headline_default = args.workload.startswith("cfg4") and not args.batch and args.impl == "auto"
-    if args.gpus == 1 and headline_default and not args.no_end_to_end and args.subjects > 4096:
+    if args.full and args.gpus == 1 and headline_default and not args.no_end_to_end and args.subjects > 4096:
         from connectome_gnn_amd.synthetic import generate_packed
         wl0 = WORKLOADS[args.workload]
         t_gen = time.perf_counter()
@@ -842,7 +857,7 @@ def main() -> None:
 
     out = run_workload(args, args.workload, rank, world, dev, launch=args.launch, batch=args.batch,
                        e2e_dataset=e2e_dataset, dump_dir=args.dump_outputs)
-    if world == 1 and headline_default and not args.no_configs:
+    if args.full and world == 1 and headline_default and not args.no_configs:
         out["inference"] = []
         for label, key, data in (("cfg4-headline-gcn-4096x360-h64", args.workload, e2e_dataset),
                                  ("cfg2-gcn-512x84-h64", "cfg2-gcn-512x84-h64", None)):
@@ -881,7 +896,7 @@ def main() -> None:
             out["projection"] = projection_8gpu(out["ms_per_step"], shard[0]["ms_per_step"])
             out["projection"]["shard_record"] = shard[0]["workload"]
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             wl = WORKLOADS[args.workload]
             out["cpu_baseline"] = cpu_baseline(wl["model"], wl["n"], wl["k"], wl["hidden"])
         print(json.dumps(out), flush=True)

@@ -4,7 +4,7 @@ devices are visible the same test also runs over backend "nccl" (= RCCL, ReduceO
 rank per device.  With SyncBatchNorm the graph-sharded run must reproduce the single-process
 full-batch run: logits of each shard, the averaged gradients and the BatchNorm running
 statistics.  Also: bench.py's self-launching strong-scaling + HIP-graph mode, rehearsed on two
-ranks."""
+ranks, and what its plain and --full runs report."""
 import os
 import socket
 import sys
@@ -135,6 +135,34 @@ def test_bench_self_launch_two_ranks(mode):
     assert out["config"]["graphs_per_gpu"] == (32 if scaling == "strong" else 64)
     assert out["config"]["launch"].startswith("hip-graph" if launch == "graph" else "eager")
     assert out["value"] > 0 and out["final_loss"] == out["final_loss"]      # finite, not NaN
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_the_headline_only_and_full_adds_the_rest():
+    """A plain `bench.py` run times its steps and prints the line; the measurements that take runs of their
+    own (eager kernel timing of a replayed step, end-to-end legs) come with --full only."""
+    import json
+    import subprocess
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--workload", "cfg2-gcn-512x84-h64", "--batch", "64"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = {}
+    for tag, extra in (("graph", ["--launch", "graph"]), ("eager", ["--launch", "eager"]),
+                       ("full", ["--launch", "graph", "--full", "--no-cpu-baseline"])):
+        res = subprocess.run(base + extra, capture_output=True, text=True, timeout=180, env=env, cwd=ROOT)
+        assert res.returncode == 0, (tag, res.stderr[-3000:])
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, (tag, res.stdout[-2000:])
+        out[tag] = json.loads(lines[0])
+    for tag in ("graph", "eager"):
+        o = out[tag]
+        assert o["steps"] == 3 and o["warmup"] == 1 and o["value"] > 0 and o["ms_per_step"] > 0
+        assert not {"end_to_end", "relabelled_by_degree", "cpu_baseline", "configs", "inference"} & set(o), tag
+    assert out["graph"]["config"]["launch"].startswith("hip-graph") and out["graph"]["roofline"] is None
+    assert out["eager"]["config"]["launch"] == "eager" and out["eager"]["roofline"]["launches_timed"] > 0
+    full = out["full"]
+    assert full["config"]["launch"].startswith("hip-graph") and full["roofline"]["launches_timed"] > 0
+    assert full["end_to_end"]["graphs_per_s"] > 0 and "cpu_baseline" not in full
 
 
 @pytest.mark.parametrize("kind", ["gcn64", "sage64", "gcn128"])

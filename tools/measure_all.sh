@@ -25,8 +25,8 @@ for spec in "$H - headline" "cfg3-sage-512x360-h128 - cfg3" "cfg2-gcn-512x84-h64
   echo "pmc $wl ok"
 done
 unset CGNN_BENCH_COLLECTING_PMC
-# 2. the driver's command: headline + every single-GPU config in one JSON line
-python3 $R/bench.py > $O/headline_bench.json 2> $O/headline_bench.err && tail -c 600 $O/headline_bench.json && echo &&
+# 2. the full benchmark: headline + every single-GPU config in one JSON line
+python3 $R/bench.py --full > $O/headline_bench.json 2> $O/headline_bench.err && tail -c 600 $O/headline_bench.json && echo &&
 # 3. kernel traces
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -o headline -- python3 $R/bench.py --steps 10 --warmup 3 $ONE > $O/prof_headline.log 2>&1 &&
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_shard512 -o ks -- python3 $R/bench.py --batch 512 --launch eager --steps 10 --warmup 3 $ONE > $O/prof_shard512.log 2>&1 &&
