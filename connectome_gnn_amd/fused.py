@@ -20,7 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .structure import BatchStructure
+from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
 
 HID = 64
 MAX_ROWS = 384
@@ -39,6 +39,8 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return f"a graph has more than {MAX_ROWS} nodes"
     if batch.node_features.requires_grad:
         return "node_features require grad"
+    if edge_grad_requested(structure):
+        return EDGE_GRAD_REASON
     for bn in model.batch_norms:
         if not (bn.affine and bn.track_running_stats) or bn.momentum is None:
             return "BatchNorm without affine/running stats/momentum"

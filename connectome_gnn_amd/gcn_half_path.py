@@ -33,7 +33,7 @@ import torch
 
 from . import _lib, ops
 from .sage_path import bn_modules_ok, pooled_bn_backward_coefs
-from .structure import BatchStructure
+from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
 
 MAX_NODES = 1024          # dense pitch limit of cgnn_dense_adj_f16
 
@@ -48,6 +48,8 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return f"a graph has more than {MAX_NODES} nodes"
     if batch.node_features.requires_grad:
         return "node_features require grad"
+    if edge_grad_requested(structure):
+        return EDGE_GRAD_REASON
     if model.convs[0].linear.weight.shape[1] > P0_COLS:
         return f"more than {P0_COLS} input features"
     if not bn_modules_ok(model) or any(isinstance(bn, torch.nn.SyncBatchNorm) for bn in model.batch_norms):

@@ -30,7 +30,7 @@ from . import _lib, ops
 from .sage_path import (PAD_K, PAD_MIN_ROWS, TILE_ROWS, _f32, _linear_fwd_stats, bn_backward_coefs,
                         pooled_bn_backward_coefs,
                         bn_forward_coef, bn_modules_ok, sync_group_of)
-from .structure import BatchStructure
+from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
 
 
 def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
@@ -44,6 +44,8 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return "graphs do not fit an LDS tile and the structure has no CSR form"
     if batch.node_features.requires_grad:
         return "node_features require grad"
+    if edge_grad_requested(structure):
+        return EDGE_GRAD_REASON
     if not bn_modules_ok(model):
         return "BatchNorm is not a plain affine BatchNorm1d / SyncBatchNorm with running stats"
     return None

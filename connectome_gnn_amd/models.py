@@ -72,16 +72,18 @@ class GCNLayer(nn.Module):
         bf, bb = s.band_ops("gcn", norm) if hasattr(s, "band_ops") else (None, None)
         fwd = (s.rowptr_dst, s.col_dst, norm.coef_dst, norm.selfc, None, bf)
         bwd = (s.rowptr_src, s.col_src, norm.coef_src, bb)
+        # edge_weight.requires_grad: every aggregate also returns its dL/dw (ops.edge_weight_grad)
+        eg = dict(edge_weight=edge_weight, edge_grad=("gcn", s, norm)) if ops.edge_grad_wanted(edge_weight) else {}
         w = self.linear.weight
         if w.shape[1] < w.shape[0]:
             # A_hat (X W^T) == (A_hat X) W^T: aggregate at the narrower width first
-            return ops.linear(ops.aggregate(x, None, fwd, bwd), None, w, self.bias)
+            return ops.linear(ops.aggregate(x, None, fwd, bwd, **eg), None, w, self.bias)
         t = ops.linear(x, None, w, None)
         if s.tiled_ok(t.shape[1]):
             # wide features: LDS-staged tiles, dis * (A_w + I)(dis * T) with the self-loop in the ELL
             meta = s.fused_meta(_TILE_ROWS, _grid(), 1.0)
-            return ops.aggregate_tiled(t, self.bias, s, meta, pre=norm.dis, post=norm.dis)
-        return ops.aggregate(t, self.bias, fwd, bwd)
+            return ops.aggregate_tiled(t, self.bias, s, meta, pre=norm.dis, post=norm.dis, **eg)
+        return ops.aggregate(t, self.bias, fwd, bwd, **eg)
 
 
 class SAGELayer(nn.Module):
@@ -100,14 +102,15 @@ class SAGELayer(nn.Module):
         if norm is None:
             norm = structure.sage_norm()
         s = structure
+        eg = dict(edge_weight=edge_weight, edge_grad=("sage", s, norm)) if ops.edge_grad_wanted(edge_weight) else {}
         if s.tiled_ok(x.shape[1]):
             # wide features: LDS-staged tiles, (A_w X) / (wsum + 1e-8), no self-loop
             meta = s.fused_meta(_TILE_ROWS, _grid(), 0.0)
-            agg = ops.aggregate_tiled(x, None, s, meta, post=norm.den, post_div=True)
+            agg = ops.aggregate_tiled(x, None, s, meta, post=norm.den, post_div=True, **eg)
         else:
             bf, bb = s.band_ops("sage", norm) if hasattr(s, "band_ops") else (None, None)
             agg = ops.aggregate(x, None, (s.rowptr_dst, s.col_dst, norm.w_dst, None, norm.den, bf),
-                                (s.rowptr_src, s.col_src, norm.coef_src_bwd, bb))
+                                (s.rowptr_src, s.col_src, norm.coef_src_bwd, bb), **eg)
         # the [x || agg] concat is never materialised: two K-panels of one GEMM, ReLU epilogue
         return ops.linear(x, agg, self.linear.weight, self.linear.bias, relu=True)
 

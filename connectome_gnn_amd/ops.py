@@ -154,6 +154,81 @@ def colsum_raw(a: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sddmm_raw(rowptr, col, eid, dy, x, xself=None, rowdiv=None, out=None, gself=None, num_slots=None) -> torch.Tensor:
+    """out[eid[k] or k] = (<dy[r], x[col[k]]> - <dy[r], xself[r]>) / rowdiv[r] over the CSR (rowptr, col)
+    (the subtraction and division only with rowdiv); gself[r] = <dy[r], xself[r]> (cgnn_sddmm_f32)."""
+    lib = _lib.load()
+    n, f = dy.shape
+    if out is None:
+        out = torch.empty(int(col.numel()) if num_slots is None else num_slots, dtype=torch.float32,
+                          device=dy.device)
+    with _lib.device_guard(dy.device), _lib.timed("cgnn_sddmm_f32", f"F={f}"):
+        _lib.check(lib.cgnn_sddmm_f32(
+            _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(dy), dy.stride(0), _lib.ptr(x), x.stride(0),
+            _lib.ptr(xself), 0 if xself is None else xself.stride(0), _lib.ptr(rowdiv), _lib.ptr(out),
+            _lib.ptr(gself), n, f, _lib.stream_ptr()), "cgnn_sddmm_f32")
+    return out
+
+
+def gcn_norm_bwd_raw(structure, edge_weight, dis, g, gself) -> torch.Tensor:
+    """dw [Ee] (COO order) of one GCN aggregate from g (COO order) and gself (cgnn_gcn_norm_bwd)."""
+    lib = _lib.load()
+    s = structure
+    dw = torch.empty(s.num_edges, dtype=torch.float32, device=g.device)
+    ws = _scratch(lib.cgnn_gcn_norm_bwd_workspace_bytes(s.num_nodes), g.device)
+    with _lib.device_guard(g.device):
+        _lib.check(lib.cgnn_gcn_norm_bwd(
+            _lib.ptr(s.rowptr_dst), _lib.ptr(s.col_dst), _lib.ptr(s.eid_dst), _lib.ptr(s.rowptr_src),
+            _lib.ptr(s.col_src), _lib.ptr(s.eid_src), _lib.ptr(edge_weight), _lib.ptr(dis), _lib.ptr(g),
+            _lib.ptr(gself), s.num_nodes, s.num_edges, _lib.ptr(dw), _lib.ptr(ws), _lib.nbytes(ws),
+            _lib.stream_ptr()), "cgnn_gcn_norm_bwd")
+    return dw
+
+
+def edge_grad_wanted(edge_weight) -> bool:
+    """The loss gradient w.r.t. the batch's edge weights is asked for: the aggregates then take
+    ``edge_weight`` as an autograd input (models.GCNLayer / SAGELayer)."""
+    return edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled()
+
+
+def edge_weight_grad(kind: str, structure, norm, dy, xp, y=None) -> torch.Tensor:
+    """dL/dw [Ee] (COO order) of one aggregate Y = A_hat X' (+ b) with dY = dy at its output:
+    GCN (models.py:94-114) through the normalisation's backward, GraphSAGE (:146-149) whole in the SDDMM
+    (y = the aggregate's output, the weighted mean)."""
+    s = structure
+    ew = s._edge_weight
+    if s.num_edges == 0:
+        return torch.zeros(0, dtype=torch.float32, device=dy.device)
+    if kind == "gcn":
+        g = torch.empty(s.num_edges, dtype=torch.float32, device=dy.device)
+        gself = torch.empty(s.num_nodes, dtype=torch.float32, device=dy.device)
+        sddmm_raw(s.rowptr_dst, s.col_dst, s.eid_dst, dy, xp, xself=xp, out=g, gself=gself)
+        return gcn_norm_bwd_raw(s, ew, norm.dis, g, gself)
+    return sddmm_raw(s.rowptr_dst, s.col_dst, s.eid_dst, dy, xp, xself=y, rowdiv=norm.den)
+
+
+def _edge_grad_check(edge_weight, edge_grad):
+    from .structure import BatchStructure
+    if edge_weight is None:
+        return
+    if edge_grad is None or edge_grad[0] not in ("gcn", "sage"):
+        raise ValueError("edge_weight needs edge_grad=(kind 'gcn' | 'sage', structure, norm)")
+    s = edge_grad[1]
+    if not isinstance(s, BatchStructure):
+        raise RuntimeError("edge-weight gradients need the batch's own CSR structure (BatchStructure), got "
+                           f"{type(s).__name__}")
+    if edge_weight.numel() != s.num_edges:
+        raise ValueError(f"edge_weight has {edge_weight.numel()} entries, the structure {s.num_edges} edges")
+
+
+def _edge_grad_out(ctx, dy, xp, y):
+    """dw shaped as the edge_weight input, or None when autograd does not ask for it."""
+    if ctx.edge_grad is None or not ctx.needs_input_grad[ctx.ew_index]:
+        return None
+    kind, s, norm = ctx.edge_grad
+    return edge_weight_grad(kind, s, norm, dy, xp, y).view(ctx.ew_shape)
+
+
 def linear_fwd_raw(x1, x2, w, bias, relu: bool) -> torch.Tensor:
     lib = _lib.load()
     m, k1 = x1.shape
@@ -211,7 +286,7 @@ class _Aggregate(torch.autograd.Function):
     """Y = A_coef X (+ selfc*X) (/rowdiv) (+bias); backward runs the transposed CSR."""
 
     @staticmethod
-    def forward(ctx, x, bias, fwd, bwd):
+    def forward(ctx, x, bias, fwd, bwd, edge_weight=None, edge_grad=None):
         rowptr, col, coef, selfc, rowdiv = fwd[:5]
         x = _prep(x, "x")
         bias_c = _prep(bias, "bias")
@@ -219,19 +294,27 @@ class _Aggregate(torch.autograd.Function):
         ctx.bwd = bwd
         ctx.selfc = selfc
         ctx.has_bias = bias is not None
+        ctx.edge_grad = None
+        if edge_weight is not None and ctx.needs_input_grad[4]:
+            # X' (and GraphSAGE's weighted mean, the output) kept for the SDDMM of the edge gradient
+            ctx.edge_grad, ctx.ew_index, ctx.ew_shape = edge_grad, 4, edge_weight.shape
+            ctx.save_for_backward(x, y if edge_grad[0] == "sage" else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         dy = _prep(dy, "grad")
         t_rowptr, t_col, t_coef = ctx.bwd[:3]
-        dx = db = None
+        dx = db = dw = None
         if ctx.needs_input_grad[0]:
             dx = aggregate_raw(t_rowptr, t_col, t_coef, ctx.selfc, None, None, dy,
                                band=ctx.bwd[3] if len(ctx.bwd) > 3 else None)
         if ctx.has_bias and ctx.needs_input_grad[1]:
             db = colsum_raw(dy)
-        return dx, db, None, None
+        if ctx.edge_grad is not None:
+            xp, y = ctx.saved_tensors
+            dw = _edge_grad_out(ctx, dy, xp, y)
+        return dx, db, None, None, dw, None
 
 
 AGG_TRANSPOSED, AGG_PRE_DIV, AGG_POST_DIV = 1, 2, 4   # include/cgnn.h
@@ -496,37 +579,55 @@ class _AggregateTiled(torch.autograd.Function):
     pre and post swapped."""
 
     @staticmethod
-    def forward(ctx, x, bias, structure, meta, pre, post, pre_div, post_div):
+    def forward(ctx, x, bias, structure, meta, pre, post, pre_div, post_div, edge_weight=None, edge_grad=None):
         x = _prep(x, "x")
         bias_c = _prep(bias, "bias")
         flags = (AGG_PRE_DIV if pre_div else 0) | (AGG_POST_DIV if post_div else 0)
         y = aggregate_tiled_raw(structure, meta, flags, x, pre, post, bias_c)
         ctx.cfg = (structure, meta, pre, post, pre_div, post_div)
         ctx.has_bias = bias is not None
+        ctx.edge_grad = None
+        if edge_weight is not None and ctx.needs_input_grad[8]:
+            ctx.edge_grad, ctx.ew_index, ctx.ew_shape = edge_grad, 8, edge_weight.shape
+            ctx.save_for_backward(x, y if edge_grad[0] == "sage" else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         structure, meta, pre, post, pre_div, post_div = ctx.cfg
         dy = _prep(dy, "grad")
-        dx = db = None
+        dx = db = dw = None
         if ctx.needs_input_grad[0]:
             flags = AGG_TRANSPOSED | (AGG_PRE_DIV if post_div else 0) | (AGG_POST_DIV if pre_div else 0)
             dx = aggregate_tiled_raw(structure, meta, flags, dy, post, pre, None)
         if ctx.has_bias and ctx.needs_input_grad[1]:
             db = colsum_raw(dy)
-        return dx, db, None, None, None, None, None, None
+        if ctx.edge_grad is not None:
+            xp, y = ctx.saved_tensors
+            dw = _edge_grad_out(ctx, dy, xp, y)
+        return dx, db, None, None, None, None, None, None, dw, None
 
 
-def aggregate_tiled(x, bias, structure, meta, pre=None, post=None, pre_div=False, post_div=False):
-    return _AggregateTiled.apply(x, bias, structure, meta, pre, post, pre_div, post_div)
+def aggregate_tiled(x, bias, structure, meta, pre=None, post=None, pre_div=False, post_div=False,
+                    edge_weight=None, edge_grad=None):
+    """edge_weight / edge_grad: as aggregate()."""
+    if edge_weight is None:
+        return _AggregateTiled.apply(x, bias, structure, meta, pre, post, pre_div, post_div)
+    _edge_grad_check(edge_weight, edge_grad)
+    return _AggregateTiled.apply(x, bias, structure, meta, pre, post, pre_div, post_div, edge_weight, edge_grad)
 
 
-def aggregate(x, bias, fwd, bwd) -> torch.Tensor:
+def aggregate(x, bias, fwd, bwd, edge_weight=None, edge_grad=None) -> torch.Tensor:
     """fwd = (rowptr, col, coef, selfc|None, rowdiv|None [, band]) on the dst-sorted CSR;
     bwd = (rowptr, col, coef [, band]) on the src-sorted CSR (coef already divided by rowdiv);
-    band = (structure, BandOp) or None (aggregate_raw)."""
-    return _Aggregate.apply(x, bias, fwd, bwd)
+    band = (structure, BandOp) or None (aggregate_raw).
+    edge_weight (optional): the batch's COO edge weights [Ee] the coefficients were computed from, taken as an
+    autograd input: backward then returns dL/dw of this aggregate, edge_grad = ("gcn", structure, GcnNorm) or
+    ("sage", structure, SageNorm) saying how (edge_weight_grad).  The forward launches are the same."""
+    if edge_weight is None:
+        return _Aggregate.apply(x, bias, fwd, bwd)
+    _edge_grad_check(edge_weight, edge_grad)
+    return _Aggregate.apply(x, bias, fwd, bwd, edge_weight, edge_grad)
 
 
 class _Linear(torch.autograd.Function):

@@ -24,7 +24,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib, ops
-from .structure import BatchStructure
+from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
 
 TILE_ROWS = 384
 
@@ -42,6 +42,8 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return "graphs do not fit an LDS tile and hidden_dim is not 64, 128 or 256"
     if batch.node_features.requires_grad:
         return "node_features require grad"
+    if edge_grad_requested(structure):
+        return EDGE_GRAD_REASON
     if not bn_modules_ok(model):
         return "BatchNorm is not a plain affine BatchNorm1d / SyncBatchNorm with running stats"
     return None

@@ -43,6 +43,17 @@ class SageNorm:
 
 TILED_MAX_ROWS = 384      # CGNN_FUSED_MAX_ROWS: rows of one LDS tile
 
+EDGE_GRAD_REASON = "edge_weight requires grad (edge gradients are computed on the layered path)"
+
+
+def edge_grad_requested(structure) -> bool:
+    """The batch's edge weights require grad and autograd is recording: the one-node encoders step aside
+    for the layered path, whose aggregates return dL/dw (ops.edge_weight_grad).  Read from the weights the
+    structure was built from (the batch's own tensor, or its contiguous copy in the autograd graph), so a
+    batch whose COO fields are assembled lazily is not made to assemble them."""
+    ew = getattr(structure, "__dict__", {}).get("_edge_weight")
+    return ew is not None and ew.requires_grad and torch.is_grad_enabled()
+
 
 def twin_view(structure, x: torch.Tensor):
     """(structure', x', twin): the batch's degree-ordered twin and the node features in its order when

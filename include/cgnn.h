@@ -123,6 +123,41 @@ int cgnn_aggregate_acc_f32(const int32_t* rowptr, const int32_t* col, const floa
                            int64_t num_rows, int32_t F, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Edge-weight gradients (csrc/edge_grad.hip): the reference's autograd of edge_weight through
+ * models.py:94-114 (GCN) and :146-149 (SAGE).  Every aggregate is Y = A_hat X' (+ b); with dY the
+ * gradient at its output, per edge e = (s -> d): g_e = <dY[d,:], X'[s,:]>.  No atomics: two
+ * identical calls give bit-identical outputs.
+ * ------------------------------------------------------------------------------------- */
+
+/* SDDMM over the dst-sorted CSR (rowptr, col): for slot k of row r,
+ *     g[eid ? eid[k] : k] = ( <dY[r,:], X[col[k],:]> - t_r ) / rowdiv[r]
+ * with t_r = <dY[r,:], Xself[r,:]> and the division only when rowdiv is not NULL (else t_r = 0 and
+ * no division): rowdiv = den of cgnn_sage_norm and Xself = the aggregate's output give GraphSAGE's
+ * whole dw_e (models.py:146-149) in COO order through eid = eid_dst.  gself [num_rows] (nullable)
+ * receives t_r: the GCN self-loop's <dY[i], X'[i]> (models.py:98-100).  Xself is required when
+ * rowdiv or gself is given.  Any F >= 1; F = 64 / 128 / 256 with 16-byte aligned rows take the
+ * vector path.  Row strides lddy / ldx / ldxs in elements (>= F).  col and g may be NULL only when the
+ * CSR has no slots (rowptr all zero). */
+int cgnn_sddmm_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                   const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                   const float* Xself, int64_t ldxs, const float* rowdiv, float* g, float* gself,
+                   int64_t num_rows, int32_t F, void* stream);
+
+/* Bytes of scratch cgnn_gcn_norm_bwd needs for num_nodes (the per-node ddis). */
+int64_t cgnn_gcn_norm_bwd_workspace_bytes(int64_t num_nodes);
+
+/* Backward of cgnn_gcn_norm (models.py:94-108) for one aggregate: from g [Ee] (COO order, cgnn_sddmm_f32
+ * with eid = eid_dst), gself [Nn], the COO edge weights w and dis of the forward,
+ *     ddis_i = sum_{e: src=i} g_e w_e dis[dst_e] + sum_{e: dst=i} g_e w_e dis[src_e] + 2 dis_i gself_i
+ *     dw_e   = g_e dis[src_e] dis[dst_e] - 1/2 dis[src_e]^3 ddis[src_e]          (COO order)
+ * ddis goes to `workspace` (cgnn_gcn_norm_bwd_workspace_bytes(Nn) bytes; shorter -> CGNN_EINVAL). */
+int cgnn_gcn_norm_bwd(const int32_t* rowptr_dst, const int32_t* col_dst, const int32_t* eid_dst,
+                      const int32_t* rowptr_src, const int32_t* col_src, const int32_t* eid_src,
+                      const float* edge_weight, const float* dis, const float* g, const float* gself,
+                      int64_t num_nodes, int64_t num_edges, float* dw, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Feature projection on the matrix cores (v_mfma_f32_32x32x2_f32: exact fp32),
  * models.py:111 (GCN, no bias) and :151-152 (SAGE: Linear([X || agg]) + bias, ReLU).
  *   fwd        : Y[M,N]  = act( X1[M,K1] W[:, 0:K1]^T + X2[M,K2] W[:, K1:K1+K2]^T + bias )
