@@ -19,8 +19,8 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib
-from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
+from . import _lib, bn_stage, ops
+from .structure import BatchStructure
 
 HID = 64
 MAX_ROWS = 384
@@ -37,10 +37,9 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return "edges cross graph boundaries"
     if structure.max_nodes_per_graph > MAX_ROWS:
         return f"a graph has more than {MAX_ROWS} nodes"
-    if batch.node_features.requires_grad:
-        return "node_features require grad"
-    if edge_grad_requested(structure):
-        return EDGE_GRAD_REASON
+    why = bn_stage.ineligible(batch, structure)
+    if why is not None:
+        return why
     for bn in model.batch_norms:
         if not (bn.affine and bn.track_running_stats) or bn.momentum is None:
             return "BatchNorm without affine/running stats/momentum"
@@ -440,29 +439,8 @@ class FusedGCNEncode(torch.autograd.Function):
                     jb.dW[i], jb.db[i] = dw_o.data_ptr(), db_o.data_ptr()
                 _lib.check(lib.cgnn_dw_db_reduce_multi(ctypes.byref(jb), st()), "cgnn_dw_db_reduce_multi")
         ctx.c = None
-        # (a gradient written into its armed .grad view is not handed to autograd again)
-        return (None, None, *[None if (dst[i] is not None and grads[i] is dst[i]) else grads[i]
-                              for i in range(4 * L)])
+        return (None, None, *ops.undelivered(grads, dst))
 
 
 def encode(model, batch, structure: BatchStructure) -> torch.Tensor:
-    params = []
-    for conv, bn in zip(model.convs, model.batch_norms):
-        params += [conv.linear.weight, conv.bias, bn.weight, bn.bias]
-    sync_group = None
-    for bn in model.batch_norms:
-        if isinstance(bn, torch.nn.SyncBatchNorm) and model.training and dist.is_initialized() \
-                and dist.get_world_size(bn.process_group) > 1:
-            sync_group = bn.process_group if bn.process_group is not None else dist.group.WORLD
-    # (on the batch's degree-ordered twin when one was prepared: less blocked-ELL padding; only the node
-    # features enter in the batch's own order)
-    from .structure import twin_view, unpermute_record
-    structure, x0, twin = twin_view(structure, batch.node_features)
-    from .ops import grad_destination
-    meta = {"structure": structure, "batch_norms": list(model.batch_norms),
-            "grad_dst": [grad_destination(q) for q in params] if (model.training and torch.is_grad_enabled()) else None,
-            "training": model.training, "dropout": float(model.dropout), "sync_group": sync_group,
-            "rng_state": getattr(model, "rng_device_state", None), "record": model._dropout_record()}
-    out = FusedGCNEncode.apply(x0, meta, *params)
-    unpermute_record(twin, meta.get("record"))
-    return out
+    return bn_stage.encode(FusedGCNEncode, model, batch, structure)

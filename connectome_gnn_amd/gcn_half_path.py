@@ -15,8 +15,8 @@ per edge, so the operator is applied DENSE, per graph, on the fp16 matrix cores:
                     Y0 = P0 W0^T + b0
   layer l > 0       T = X W^T                       cgnn_linear_fwd_f16 (weight-stationary, fp32 accumulate)
                     Y = Mf T + b                    cgnn_dense_aggregate_f16 (v_mfma_f32_32x32x16_f16)
-  every layer       X' = dropout(relu(BatchNorm(Y)))            cgnn_bn_act_*_f16 (two passes)
-  readout           fused into the last BatchNorm pass          cgnn_bn_act_pool_fwd_f16
+  every layer       X' = dropout(relu(BatchNorm(Y)))            cgnn_bn_act_*_f16 (two passes, bn_stage.py)
+  readout           fused into the last BatchNorm pass
   backward          dY = BatchNorm'(...) (two passes, db = column sums), dT = Mb dY,
                     dW = dT^T X (cgnn_linear_bwd_weight_f16: LDS transposing reads, fp32 partials
                     per run of rows), dX = dT W (cgnn_linear_bwd_input_f16);
@@ -27,13 +27,13 @@ converted fp32 -> half inside the kernels): nothing on this path goes to a GEMM 
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Optional
 
 import torch
 
 from . import _lib, ops
-from .sage_path import bn_modules_ok, pooled_bn_backward_coefs
-from .structure import EDGE_GRAD_REASON, BatchStructure, edge_grad_requested
+from .bn_stage import BnStage, bn_modules_ok, encode as _encode, ineligible
+from .structure import BatchStructure
 
 MAX_NODES = 1024          # dense pitch limit of cgnn_dense_adj_f16
 
@@ -46,10 +46,9 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return "edges cross graph boundaries"
     if structure.max_nodes_per_graph > MAX_NODES:
         return f"a graph has more than {MAX_NODES} nodes"
-    if batch.node_features.requires_grad:
-        return "node_features require grad"
-    if edge_grad_requested(structure):
-        return EDGE_GRAD_REASON
+    why = ineligible(batch, structure)
+    if why is not None:
+        return why
     if model.convs[0].linear.weight.shape[1] > P0_COLS:
         return f"more than {P0_COLS} input features"
     if not bn_modules_ok(model) or any(isinstance(bn, torch.nn.SyncBatchNorm) for bn in model.batch_norms):
@@ -92,11 +91,7 @@ P0_COLS = 64             # layer 0's input features ride in one 64-column half p
 
 
 class _Saved:
-    __slots__ = ("s", "mb", "xs", "ys", "coefs", "masks", "ws", "p0", "p", "training", "fsum")
-
-
-def _f32(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
+    __slots__ = ("s", "mb", "xs", "ws", "p0", "bn")
 
 
 class GcnHalfEncode(torch.autograd.Function):
@@ -106,144 +101,78 @@ class GcnHalfEncode(torch.autograd.Function):
     def forward(ctx, x0, cfg, *params):
         lib = _lib.load()
         s: BatchStructure = cfg["structure"]
-        bns_mod = cfg["batch_norms"]
-        training: bool = cfg["training"]
-        p: float = cfg["dropout"] if training else 0.0
         L = len(params) // 4
         dev = x0.device
-        sp = _lib.stream_ptr(dev)
-        n_nodes, B = s.num_nodes, s.num_graphs
         mf, mb = dense_operators(s)
         sv = _Saved()
-        sv.s, sv.mb, sv.p, sv.training = s, mb, p, training
-        sv.xs, sv.ys, sv.coefs, sv.masks, sv.ws = [], [], [], [], []
+        sv.s, sv.mb = s, mb
+        sv.xs, sv.ws = [], []
         x = None
-        rng = cfg.get("rng_state")          # device words a captured step refreshes per replay
         with _lib.device_guard(dev):
-            rows = int(lib.cgnn_bn_act_slab_rows(n_nodes))
-            if rng is not None and p > 0:
-                _lib.check(lib.cgnn_rng_advance(_lib.ptr(rng), L + 1, sp), "cgnn_rng_advance")
+            sv.bn = bn = BnStage(cfg, L, dev, relu_after_bn=True, half=True)
             for li in range(L):
                 w, b, gamma, beta = (t.contiguous() for t in params[4 * li:4 * li + 4])
                 hid = w.shape[0]
+                slab = None
                 if li == 0:
                     # A_hat (X0 W0^T) == (A_hat X0) W0^T: aggregate the few input columns (one
                     # 64-column half panel through the dense operator), then project
                     sv.p0 = _agg(s, mf, ops.pad_cast_f16(x0, P0_COLS))    # [Nn, 64] half, cols >= F0 zero
                     y = None
-                    if training:                                           # statistics in the epilogue
+                    if bn.training:                                        # statistics in the epilogue
                         y, slab = ops.linear_fwd_stats_f16_raw(sv.p0, w, b, int(lib.cgnn_fused_grid()))
-                        srows = int(lib.cgnn_fused_grid())
                     if y is None:
                         y = ops.linear_fwd_f16_raw(sv.p0, w, b)           # K = 64 panel, W0 [H, F0]
-                        slab, srows = None, rows
                 else:
-                    slab, srows = None, rows
-                if li > 0:
                     t = ops.linear_fwd_f16_raw(x, w)                       # half in / out, fp32 accumulate
-                    if training:                                           # statistics in the epilogue
-                        srows = int(lib.cgnn_fused_grid())
-                        slab = torch.empty(srows, 2 * hid, dtype=torch.float64, device=dev)
+                    if bn.training:                                        # statistics in the epilogue
+                        slab = torch.empty(int(lib.cgnn_fused_grid()), 2 * hid, dtype=torch.float64, device=dev)
                     y = _agg(s, mf, t, b, slab)
-                if training and slab is None:
-                    slab = torch.empty(rows, 2 * hid, dtype=torch.float64, device=dev)
-                    _lib.check(lib.cgnn_bn_act_fwd_stats_f16(_lib.ptr(y), n_nodes, hid, _lib.ptr(slab), _lib.nbytes(slab), sp),
-                               "cgnn_bn_act_fwd_stats_f16")
-                bn = bns_mod[li]
-                coef = _f32(dev, 4 * hid)
-                _lib.check(lib.cgnn_bn_act_finalize(
-                    _lib.ptr(slab), srows, hid, float(max(n_nodes, 1)), None, int(training), _lib.ptr(gamma),
-                    _lib.ptr(beta), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.momentum),
-                    float(bn.eps), _lib.ptr(bn.num_batches_tracked) if training else None, _lib.ptr(coef), sp),
-                    "cgnn_bn_act_finalize")
-                mask = torch.empty(n_nodes * (hid // 4), dtype=torch.uint8, device=dev) if p > 0 else None
-                seed = _lib.next_seed(dev) if p > 0 else 0
-                rw = None if (rng is None or p <= 0) else rng.data_ptr() + 4 * li
-                sv.xs.append(x); sv.ys.append(y); sv.coefs.append(coef); sv.masks.append(mask); sv.ws.append(w)
-                if li == L - 1:
-                    pooled = _f32(dev, B, hid)
-                    # per-graph factor sums: the backward statistics of this layer need no pass over Y
-                    sv.fsum = _f32(dev, 2, B, hid) if any(ctx.needs_input_grad) else None
-                    _lib.check(lib.cgnn_bn_act_pool_fwd_f16(_lib.ptr(y), _lib.ptr(coef), 1, p, seed, rw,
-                                                            _lib.ptr(mask), _lib.ptr(s.gptr), B,
-                                                            _lib.ptr(pooled), hid, _lib.ptr(sv.fsum), sp),
-                               "cgnn_bn_act_pool_fwd_f16")
-                    break
-                xn = torch.empty_like(y)
-                _lib.check(lib.cgnn_bn_act_fwd_apply_f16(_lib.ptr(y), _lib.ptr(coef), 1, p, seed, rw,
-                                                         _lib.ptr(mask), _lib.ptr(xn), n_nodes, hid, sp),
-                           "cgnn_bn_act_fwd_apply_f16")
-                x = xn
-        if cfg.get("record") is not None:
-            cfg["record"]["layers"] = list(sv.masks)
-        ctx.sv, ctx.L = sv, L
+                bn.forward(y, gamma, beta, slab)
+                sv.xs.append(x); sv.ws.append(w)
+                if li < L - 1:
+                    x = bn.apply(li)
+            # readout fused into the last BatchNorm pass; its per-graph factor sums: the backward
+            # statistics of this layer need no pass over Y
+            pooled = bn.pool(any(ctx.needs_input_grad))
+        ctx.sv = sv
         return pooled
 
     @staticmethod
     def backward(ctx, dP):
-        lib = _lib.load()
         sv: _Saved = ctx.sv
-        s, L = sv.s, ctx.L
+        s, bn = sv.s, sv.bn
         dev = dP.device
-        sp = _lib.stream_ptr(dev)
-        n_nodes = s.num_nodes
         dP = dP.contiguous()
-        grads: List[Optional[torch.Tensor]] = [None] * (4 * L)
         with _lib.device_guard(dev):
-            rows = int(lib.cgnn_bn_act_slab_rows(n_nodes))
+            bn.begin_backward(dP)
             dx = None                           # last layer: gradient rebuilt from dP inside the kernels
-            deferred = _lib.DeferredReduce()
-            for li in range(L - 1, -1, -1):
-                x, y, coef, mask, w = sv.xs[li], sv.ys[li], sv.coefs[li], sv.masks[li], sv.ws[li]
-                hid = w.shape[0]
-                pool = (_lib.ptr(dP), _lib.ptr(s.node_graph), _lib.ptr(s.gptr)) if li == L - 1 else (None, None, None)
-                if li == L - 1 and sv.fsum is not None:
-                    dgamma, dbeta, bwc = pooled_bn_backward_coefs(lib, dP, sv.fsum, s, hid, n_nodes, sv.training, sp, dev)
-                else:
-                    slab, srows = torch.empty(rows, 2 * hid, dtype=torch.float64, device=dev), rows
-                    _lib.check(lib.cgnn_bn_act_bwd_stats_f16(_lib.ptr(dx), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(coef),
-                                                             1, sv.p, n_nodes, hid, _lib.ptr(slab), _lib.nbytes(slab), *pool, sp),
-                               "cgnn_bn_act_bwd_stats_f16")
-                    dgamma, dbeta, bwc = _f32(dev, hid), _f32(dev, hid), _f32(dev, 2 * hid)
-                    _lib.check(lib.cgnn_bn_act_bwd_finalize(_lib.ptr(slab), srows, hid, float(max(n_nodes, 1)), None,
-                                                            int(not sv.training), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                                            _lib.ptr(bwc), sp), "cgnn_bn_act_bwd_finalize")
-                db = _f32(dev, hid)
+            for li in range(bn.L - 1, -1, -1):
+                x, w = sv.xs[li], sv.ws[li]
+                bwc = bn.bwd_coefs(li, dx)
                 if li > 0 and isinstance(sv.mb, ops.DensePack):
                     # dT = A_hat^T dY with dY formed while the aggregate stages its slices: no apply
                     # pass, dY is never written (db from the per-graph column sums it leaves)
                     dt, cs_slab = ops.dense_aggregate_c16_bnbwd_raw(
-                        s, sv.mb, dx, dP if li == L - 1 else None, y, mask, coef, bwc, True, sv.p)
-                    deferred.add(cs_slab, s.num_graphs, hid, db)
+                        s, sv.mb, dx, dP if li == bn.L - 1 else None, bn.ys[li], bn.masks[li], bn.coefs[li], bwc,
+                        True, bn.p)
+                    bn.add_db(li, cs_slab, s.num_graphs)
                     dy = None
                 else:
-                    cs_rows = int(lib.cgnn_bn_act_apply_blocks(n_nodes, hid))
-                    cs_slab = torch.empty(cs_rows, hid, dtype=torch.float64, device=dev)
-                    dy = torch.empty_like(y)
-                    _lib.check(lib.cgnn_bn_act_bwd_apply_f16(_lib.ptr(dx), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(coef),
-                                                             _lib.ptr(bwc), 1, sv.p, 0, _lib.ptr(cs_slab), _lib.nbytes(cs_slab), _lib.ptr(dy),
-                                                             n_nodes, hid, *pool, sp), "cgnn_bn_act_bwd_apply_f16")
-                    deferred.add(cs_slab, cs_rows, hid, db)       # all layers' db: one launch at the end
+                    dy = bn.bwd_apply(li, dx, bwc)
                     dt = None
                 if li == 0:
                     # Y0 = (A_hat X0) W0^T + b0: dW0 = dY0^T P0, no aggregation in the backward
-                    dw = ops.linear_bwd_weight_f16_raw(dy, sv.p0, w.shape[1])
-                    grads[0:4] = [dw, db, dgamma, dbeta]
+                    bn.grads[0] = ops.linear_bwd_weight_f16_raw(dy, sv.p0, w.shape[1])
                     break
                 if dt is None:
                     dt = _agg(s, sv.mb, dy)         # dT = A_hat^T dY
-                grads[4 * li:4 * li + 4] = [ops.linear_bwd_weight_f16_raw(dt, x), db, dgamma, dbeta]
+                bn.grads[4 * li] = ops.linear_bwd_weight_f16_raw(dt, x)
                 dx = ops.linear_bwd_input_f16_raw(dt, w)                   # dX = dT W
-            deferred.flush(sp)
+            grads = bn.finish()
         ctx.sv = None
         return (None, None, *grads)
 
 
 def encode(model, batch, structure: BatchStructure) -> torch.Tensor:
-    params = []
-    for conv, bn in zip(model.convs, model.batch_norms):
-        params += [conv.linear.weight, conv.bias, bn.weight, bn.bias]
-    cfg = {"structure": structure, "batch_norms": list(model.batch_norms), "training": model.training,
-           "dropout": float(model.dropout), "record": model._dropout_record(),
-           "rng_state": getattr(model, "rng_device_state", None)}
-    return GcnHalfEncode.apply(batch.node_features, cfg, *params)
+    return _encode(GcnHalfEncode, model, batch, structure, half=True)

@@ -203,13 +203,13 @@ class Trainer:
     def _subject_cache_serves(self, ds, batch_size: int) -> bool:
         """The per-subject structure cache (structure_cache.py) carries what the per-tile GCN encoder and the
         GraphSAGE encoder index with, and nothing else (no CSR)."""
-        from . import fused, sage_path
+        from . import bn_stage, fused
         from .models import GCNConnectome, GraphSAGEConnectome
         from .structure_cache import MAX_ROWS
         m = self.model
         n = int(ds.x.shape[1])
         if not (0 < n <= MAX_ROWS) or getattr(m, "impl", None) == "layered" or getattr(m, "storage", "fp32") != "fp32" \
-                or any(isinstance(mod, nn.SyncBatchNorm) for mod in m.modules()) or not sage_path.bn_modules_ok(m):
+                or any(isinstance(mod, nn.SyncBatchNorm) for mod in m.modules()) or not bn_stage.bn_modules_ok(m):
             return False
         hid, fin = m.convs[0].linear.weight.shape
         if type(m) is GCNConnectome:                       # the per-tile kernels (fused.eligible)
