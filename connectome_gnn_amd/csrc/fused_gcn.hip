@@ -639,6 +639,20 @@ struct PoolIn {
   const uint8_t* mask_cur;       // keep bits of THIS layer's activation (or NULL)
 };
 
+// phase-A tunables of k_gcn_bwd (A/B builds may override them)
+#ifndef CGNN_BWD_UNR
+#define CGNN_BWD_UNR 4           // rows requested per thread before the first is consumed
+#endif
+#ifndef CGNN_BWD_UNR_POOL
+#define CGNN_BWD_UNR_POOL 4
+#endif
+// POOLIN: readout-gradient rows staged in LDS per tile (a tile with more graphs reads them per
+// row; 0 = never staged, an A/B switch)
+#ifndef CGNN_BWD_RO_G
+#define CGNN_BWD_RO_G 8
+#endif
+constexpr int RO_G = CGNN_BWD_RO_G;
+
 
 // XP0: the previous layer's output is layer 0's in factored form: its rows are rebuilt from the
 // narrow aggregate l0.P0 (32 bytes per row) instead of being read from Xprev (256 bytes per row).
@@ -664,6 +678,32 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
   __shared__ __attribute__((aligned(16))) float bnl[FIRST ? 4 : 4 * HID];
   if (!FIRST) {
     for (int i = threadIdx.x; i < 4 * HID; i += (NW * 64)) bnl[i] = bn_prev[i];
+  }
+  // POOLIN: dP[g] / (n_g + 1e-8) for the <= RO_G graphs of a tile (rog), its first graph and
+  // whether it was staged (rog_g).  The last wave (never more blocks than the others) stages the
+  // NEXT tile's rows at the end of phase B, so phase A reads them from LDS instead of following
+  // node_graph -> gptr / dP with a dependent HBM trip per row.
+  __shared__ __attribute__((aligned(16))) float rog[POOLIN && RO_G > 0 ? RO_G * HID : 4];
+  __shared__ int rog_g[2];
+  auto stage_readout = [&](int tt) {
+    const int nb = t.tile_ptr[tt], nn = t.tile_ptr[tt + 1] - nb;
+    const int g0 = nn > 0 ? pin.node_graph[nb] : 0;
+    const int ng = nn > 0 ? pin.node_graph[nb + nn - 1] - g0 + 1 : 0;
+    if (ng <= RO_G) {
+      for (int i = lane; i < ng * 16; i += 64) {
+        const int g = g0 + (i >> 4), c = i & 15;
+        const float inv = 1.0f / ((float)(pin.gptr[g + 1] - pin.gptr[g]) + 1e-8f);
+        st4(rog + (i >> 4) * HID + 4 * c, scale4(ld4(pin.dP + (int64_t)g * HID + 4 * c), inv));
+      }
+    }
+    if (lane == 0) {
+      rog_g[0] = g0;
+      rog_g[1] = ng <= RO_G;
+    }
+  };
+  if (POOLIN) {
+    if (cgnn_uniform(wave) == NW - 1 && (int)blockIdx.x < t.num_tiles) stage_readout(blockIdx.x);
+    __syncthreads();
   }
   // XP0: rows of Y0 rebuilt on the fp32 matrix pipe (l0src.h): D_t[row][col 4j + t]
   L0W w0;
@@ -700,6 +740,7 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
     }
     MetaRegs pre;
     if (wave < nblk) pre = meta_issue<FIRST>(ent + (off0 >> 1), width, q, j);
+    const int nxt = tid + gridDim.x;
 
     // --------------------------- phase A: dis * dY, dY = BatchNorm'(dZ), into the tile
     {
@@ -708,8 +749,8 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
       const float4 ca = ld4(bn + 4 * j), cmean = ld4(bn + 2 * HID + 4 * j), cis = ld4(bn + 3 * HID + 4 * j);
       const float4 c1 = ld4(bwc + 4 * j), c2 = ld4(bwc + HID + 4 * j);
       const float4 cb = POOLIN ? ld4(bn + HID + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-#define CGNN_BWD_UNR 6
-#define CGNN_BWD_UNR_POOL 6
+      const int rg0 = POOLIN ? rog_g[0] : 0;
+      const bool rstaged = POOLIN && rog_g[1] != 0;
       // rows requested per thread before the first is consumed: every batch is one exposed HBM
       // round trip of this phase (the dW accumulators leave no room to prefetch across tiles)
       constexpr int UNR = POOLIN ? CGNN_BWD_UNR_POOL : CGNN_BWD_UNR;
@@ -736,7 +777,13 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
             dv[u] = t.dis[base + row];
           }
         }
-        if (POOLIN) {
+        if (POOLIN && rstaged) {
+#pragma unroll
+          for (int u = 0; u < UNR; ++u) {
+            const int row = r0 + (NW * 4) * u;
+            if (row < n) zb[u] = ld4(rog + (gid[u] - rg0) * HID + 4 * j);
+          }
+        } else if (POOLIN) {
 #pragma unroll
           for (int u = 0; u < UNR; ++u) {
             const int row = r0 + (NW * 4) * u;
@@ -795,17 +842,21 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
         // commit (so the commit does not wait on it) and BEFORE the aggregation (which hides
         // its HBM latency).  Only the raw pre-BatchNorm values and the keep bits stay live; X
         // (B operand of dW) and relu'/dropout'/xhat (epilogue) are re-derived where needed.
+        // The keep bytes of rows 4q..4q+3 are one contiguous 64-byte run: lane j requests bytes
+        // 4j..4j+3 of it (one load, rows past n read as 0, no drop reads as 0xF) and the bytes
+        // are redistributed after the aggregation.
+        uint32_t kword = 0u;
         if (!FIRST) {
+          if (16 * b + 4 * q + (j >> 2) < n) {
+            kword = 0x0F0F0F0Fu;
+            if (use_drop)
+              kword = *reinterpret_cast<const uint32_t*>(mask_prev + (int64_t)(base + 16 * b + 4 * q) * 16 + 4 * j);
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = 16 * b + 4 * q + r;
             yp[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < n) {
-                if (!XP0) yp[r] = BW_LD(Xprev + (int64_t)(base + row) * HID + 4 * j);
-                uint32_t kb = 0xFu;
-                if (use_drop) kb = mask_prev[(int64_t)(base + row) * 16 + j];
-                keeps |= kb << (8 * r);
-            }
+            if (row < n && !XP0) yp[r] = BW_LD(Xprev + (int64_t)(base + row) * HID + 4 * j);
           }
         }
         if (!FIRST && XP0 && 16 * b + j < n) {
@@ -815,6 +866,14 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
         }
         float4 ag[4];
         agg_block<FIRST ? 4 : BWD_G, FIRST>(tile, pre, ent + (off0 >> 1), width, q, j, ag);
+        if (!FIRST) {
+          // row 4q+r, chunk j = byte 16r + j of the run: byte j&3 of lane (q, 4r + j/4)'s word
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const uint32_t v = (uint32_t)__shfl((int)kword, 16 * q + 4 * r + (j >> 2), 64);
+            keeps |= ((v >> (8 * (j & 3))) & 0xFFu) << (8 * r);
+          }
+        }
         CGNN_STAMP(3)
         if (XP0) {
           // rows outside the tile rebuild to b0, harmless: their keep byte is 0 -> x = f = 0
@@ -906,6 +965,7 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
       }
       CGNN_STAMP(4)
     }
+    if (POOLIN && cgnn_uniform(wave) == NW - 1 && nxt < t.num_tiles) stage_readout(nxt);
     CGNN_STAMP(5)
     __syncthreads();
     CGNN_STAMP(6)
@@ -1621,7 +1681,7 @@ int cgnn_gcn_fused_bwd(const cgnn_tiles* t, const float* dZ, const float* Y, con
     return CGNN_EINVAL;
   if (!tail_ok(tail, 1)) return CGNN_EINVAL;
   const cgnn_bn_tail tl = tail ? *tail : cgnn_bn_tail{};
-  if (p_drop > 0.f && !mask_prev) return CGNN_EINVAL;
+  if (p_drop > 0.f && (!mask_prev || (reinterpret_cast<uintptr_t>(mask_prev) & 3u))) return CGNN_EINVAL;
   if (dP ? (!node_graph || !gptr || (p_drop > 0.f && !mask_cur)) : !dZ) return CGNN_EINVAL;
   CGNN_NEED_BYTES(s_slab_prev, s_slab_prev_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
   CGNN_NEED_BYTES(dW_slab, dW_slab_bytes, (int64_t)fused_grid() * HID * HID * (int64_t)sizeof(float));

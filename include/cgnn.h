@@ -579,7 +579,9 @@ int cgnn_bn_bwd_finalize(const double* sums, double count, const double* count_d
 /* Last layer only: pass dP != NULL (then dZ is ignored and may be NULL) together with
  * node_graph int32 [Nn], gptr int32 [B+1] and mask_cur (this layer's keep bits): the incoming
  * gradient is rebuilt per row as dP[g]/(n_g+1e-8) * relu' * dropout'.  Otherwise dP = NULL.
- * Yprev == NULL: the previous layer is layer 0 in factored form, rows rebuilt from *l0. */
+ * Yprev == NULL: the previous layer is layer 0 in factored form, rows rebuilt from *l0.
+ * mask_prev (when p_drop > 0) is read as 32-bit words and must be 4-byte aligned (CGNN_EINVAL
+ * otherwise); node_graph must be non-decreasing (the batch vector of whole graphs). */
 int cgnn_gcn_fused_bwd(const cgnn_tiles* t, const float* dZ, const float* Y, const float* bn,
                        const float* bwc, const float* Yprev, const cgnn_l0src* l0,
                        const float* bn_prev, float p_drop, const uint8_t* mask_prev, const float* W,
