@@ -36,6 +36,8 @@
 // the slabs' traffic at the headline size.
 #pragma once
 #include "common.h"
+#include "bn_coef.h"
+#include "drop_ew.h"
 
 namespace {
 
@@ -106,42 +108,17 @@ __device__ __forceinline__ void bnacc_reset(BnAcc* acc) {
   __hip_atomic_store(&acc->nonfinite, 0u, __ATOMIC_RELAXED, CGNN_AGENT);
 }
 
-__device__ __forceinline__ uint32_t bn_tail_mix32(uint32_t x) {      // (= mix32 of the dropout hash)
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// The finalisation itself, thread c < 64 of the last workgroup (the arithmetic of k_bn_fwd_stats /
-// k_bn_bwd_stats, fused_gcn.hip).  mean_off: the constant the statistics were taken without (centred layer 0).
+// The finalisation itself, thread c < 64 of the last workgroup (bn_coef.h; the step's dropout words as
+// drop_ew.h advances them).  mean_off: the constant the statistics were taken without (centred layer 0).
 __device__ __forceinline__ void bn_tail_finalize(const cgnn_bn_tail& t, BnAcc* acc, int c, float mean_off) {
   const double S1 = bnacc_take(acc, c), S2 = bnacc_take(acc, 64 + c);
   if (t.mode == 0) {
-    const double m = S1 / t.count;
-    double v = S2 / t.count - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mean = (float)m, var = (float)v;
-    const double unbiased = t.count > 1.0 ? v * t.count / (t.count - 1.0) : v;
-    const float mean_y = (float)(m + (double)mean_off);
-    t.running_mean[c] = (1.0f - t.momentum) * t.running_mean[c] + t.momentum * (mean_off != 0.f ? mean_y : mean);
-    t.running_var[c] = (1.0f - t.momentum) * t.running_var[c] + t.momentum * (float)unbiased;
-    const float invstd = 1.0f / sqrtf(var + t.eps);
-    const float a = t.gamma[c] * invstd;
-    t.bn_out[c] = a;
-    t.bn_out[64 + c] = t.beta[c] - mean * a;
-    t.bn_out[128 + c] = mean;
-    t.bn_out[192 + c] = invstd;
+    bn_fwd_coef(true, S1, S2, t.count, t.gamma, t.beta, t.running_mean, t.running_var, t.momentum, t.eps,
+                mean_off, t.bn_out, 64, c);
     if (c == 0 && t.num_batches_tracked) *t.num_batches_tracked += 1;
-    if (t.rng_state && c < t.rng_n)
-      t.rng_state[c] = bn_tail_mix32(t.rng_state[c] + 0x9E3779B9u * (uint32_t)(c + 1));
+    if (t.rng_state && c < t.rng_n) t.rng_state[c] = rng_refresh(t.rng_state[c], c);
   } else {
-    t.dbeta[c] = (float)S1;
-    t.dgamma[c] = (float)S2;
-    t.bwc[c] = t.zero_coef ? 0.f : (float)(S1 / t.count);
-    t.bwc[64 + c] = t.zero_coef ? 0.f : (float)(S2 / t.count);
+    bn_bwd_coef(S1, S2, t.count, t.zero_coef, t.dgamma, t.dbeta, t.bwc, 64, c);
   }
 }
 

@@ -45,6 +45,16 @@ __device__ __forceinline__ double cgnn_wave_sum(double v) {
   return v;
 }
 
+// Block-wide fixed-order sum of v over 256 threads (4 waves); sh: 4 doubles of LDS.
+__device__ __forceinline__ double block_sum256(double v, double* sh) {
+  v = cgnn_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double t = sh[0] + sh[1] + sh[2] + sh[3];
+  __syncthreads();
+  return t;
+}
+
 // Streamed data -- arrays a kernel reads or writes exactly once -- goes through non-temporal
 // accesses: they do not allocate in the cache hierarchy the way default loads/stores do, and a
 // streaming pass over 0.4 GB ran 24 % faster with them (k_pool_fwd 98 -> 74 us).  NOT for data

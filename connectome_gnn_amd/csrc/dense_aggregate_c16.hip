@@ -530,7 +530,7 @@ int cgnn_dense_aggregate_c16_bnbwd(const void* dfrag, const int32_t* dstep, cons
   bb.coef = coef;
   bb.bwc = bwc;
   bb.relu = relu;
-  bb.scale = p_drop > 0.f ? (float)(1.0 / (1.0 - (double)p_drop)) : 1.0f;
+  bb.scale = drop_scale(p_drop);
   bb.cs_slab = cs_slab;
   k_dense_agg_c<true><<<grid, C_THR, c_lds(P, F), cgnn_stream(stream)>>>(
       static_cast<const __half*>(dfrag), dstep, doff, sent, sstep, soff, P, gptr, num_graphs,

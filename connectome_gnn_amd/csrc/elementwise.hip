@@ -9,6 +9,7 @@
 //   X' = drop( act( a*Y + b ) ),  a = gamma*invstd, b = beta - mean*a,  act = ReLU or identity
 //   dY = a * ( dZ - c1 - xhat*c2 ),  dZ = dX' * drop' * act'
 #include "common.h"
+#include "bn_coef.h"
 #include "drop_ew.h"
 
 namespace {
@@ -121,20 +122,35 @@ __global__ void __launch_bounds__(THR) k_colstats(
   }
 }
 
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-  v = cgnn_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+// Blocks of FIN_C consecutive channels x FIN_G row groups: thread (rg, cc) holds the partials a1, a2
+// of channel cc over row group rg; the FIN_G partials are combined in fixed order, two levels deep (a
+// serial chain of FIN_G dependent LDS reads costs ~3 us).  Results in S1, S2 for threads rg == 0.
+constexpr int FIN_C = 8, FIN_G = 128;      // 1024 threads: 64-byte row pieces, 128 row groups
+__device__ __forceinline__ void fold_groups(double a1, double a2, double (*sh)[FIN_C][2], double& S1,
+                                            double& S2) {
+  const int cc = threadIdx.x % FIN_C, rg = threadIdx.x / FIN_C;
+  sh[rg][cc][0] = a1;
+  sh[rg][cc][1] = a2;
   __syncthreads();
-  const double t = sh[0] + sh[1] + sh[2] + sh[3];
+  __shared__ double sh2[FIN_G / 8][FIN_C][2];
+  if (rg < FIN_G / 8) {
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { t1 += sh[8 * rg + k][cc][0]; t2 += sh[8 * rg + k][cc][1]; }
+    sh2[rg][cc][0] = t1;
+    sh2[rg][cc][1] = t2;
+  }
   __syncthreads();
-  return t;
+  S1 = S2 = 0.0;
+  if (rg == 0) {
+#pragma unroll
+    for (int k = 0; k < FIN_G / 8; ++k) { S1 += sh2[k][cc][0]; S2 += sh2[k][cc][1]; }
+  }
 }
 
-// Column sums of a slab [rows][2N] fp64 for FIN_C consecutive channels per block: thread (rg, cc)
-// adds rows rg, rg + FIN_G, ... of columns c and N + c (each load instruction reads FIN_C
-// consecutive doubles of a row: coalesced; one block per channel read 4 KB-strided columns), then
-// the FIN_G partials are combined in fixed order.  Results in s1[cc], s2[cc] for threads rg == 0.
-constexpr int FIN_C = 8, FIN_G = 128;      // 1024 threads: 64-byte row pieces, 128 row groups
+// Column sums of a slab [rows][2N] fp64: thread (rg, cc) adds rows rg, rg + FIN_G, ... of columns
+// c and N + c (each load instruction reads FIN_C consecutive doubles of a row: coalesced; one block
+// per channel read 4 KB-strided columns), then fold_groups.
 __device__ __forceinline__ void slab_colsum2(const double* __restrict__ slab, int rows, int N, int c0,
                                              double (*sh)[FIN_C][2], double& S1, double& S2) {
   const int cc = threadIdx.x % FIN_C, rg = threadIdx.x / FIN_C, c = c0 + cc;
@@ -156,24 +172,7 @@ __device__ __forceinline__ void slab_colsum2(const double* __restrict__ slab, in
       a2 += slab[(int64_t)r * 2 * N + N + c];
     }
   }
-  sh[rg][cc][0] = a1;
-  sh[rg][cc][1] = a2;
-  __syncthreads();
-  // fixed-order two-level fold (a serial chain of FIN_G dependent LDS reads costs ~3 us)
-  __shared__ double sh2[FIN_G / 8][FIN_C][2];
-  if (rg < FIN_G / 8) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { t1 += sh[8 * rg + k][cc][0]; t2 += sh[8 * rg + k][cc][1]; }
-    sh2[rg][cc][0] = t1;
-    sh2[rg][cc][1] = t2;
-  }
-  __syncthreads();
-  S1 = S2 = 0.0;
-  if (rg == 0) {
-#pragma unroll
-    for (int k = 0; k < FIN_G / 8; ++k) { S1 += sh2[k][cc][0]; S2 += sh2[k][cc][1]; }
-  }
+  fold_groups(a1, a2, sh, S1, S2);
 }
 
 __global__ void __launch_bounds__(FIN_C * FIN_G) k_bn_fwd_finalize_n(
@@ -185,33 +184,11 @@ __global__ void __launch_bounds__(FIN_C * FIN_G) k_bn_fwd_finalize_n(
   __shared__ double sh[FIN_G][FIN_C][2];
   const double count = count_dev ? count_dev[0] : count_host;
   const int c = blockIdx.x * FIN_C + threadIdx.x % FIN_C;
-  const bool owner = threadIdx.x < FIN_C && c < N;
-  float mean = 0.f, var = 1.f;
-  if (training) {
-    double S1, S2;
-    slab_colsum2(slab, rows, N, blockIdx.x * FIN_C, sh, S1, S2);
-    if (owner) {
-      const double m = S1 / count;
-      double v = S2 / count - m * m;
-      if (v < 0.0) v = 0.0;
-      mean = (float)m;
-      var = (float)v;
-      const double unbiased = count > 1.0 ? v * count / (count - 1.0) : v;
-      rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean;
-      rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;
-      if (c == 0 && tracked) *tracked += 1;
-    }
-  } else if (owner) {
-    mean = rmean[c];
-    var = rvar[c];
-  }
-  if (owner) {
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float a = gamma[c] * invstd;
-    coef[c] = a;
-    coef[N + c] = beta[c] - mean * a;
-    coef[2 * N + c] = mean;
-    coef[3 * N + c] = invstd;
+  double S1 = 0.0, S2 = 0.0;
+  if (training) slab_colsum2(slab, rows, N, blockIdx.x * FIN_C, sh, S1, S2);
+  if (threadIdx.x < FIN_C && c < N) {
+    if (training && c == 0 && tracked) *tracked += 1;
+    bn_fwd_coef(training, S1, S2, count, gamma, beta, rmean, rvar, momentum, eps, 0.f, coef, N, c);
   }
 }
 
@@ -226,12 +203,7 @@ __global__ void __launch_bounds__(FIN_C * FIN_G) k_bn_bwd_finalize_n(const doubl
   const int c = blockIdx.x * FIN_C + threadIdx.x % FIN_C;
   double S1, S2;
   slab_colsum2(slab, rows, N, blockIdx.x * FIN_C, sh, S1, S2);
-  if (threadIdx.x < FIN_C && c < N) {
-    dbeta[c] = (float)S1;
-    dgamma[c] = (float)S2;
-    bwc[c] = zero_coef ? 0.f : (float)(S1 / count);
-    bwc[N + c] = zero_coef ? 0.f : (float)(S2 / count);
-  }
+  if (threadIdx.x < FIN_C && c < N) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, N, c);
 }
 
 // BatchNorm-backward sums of a pooled last layer from the forward pass's factor sums (see
@@ -242,7 +214,6 @@ __global__ void __launch_bounds__(FIN_C * FIN_G) k_bn_pool_bwd_finalize(
     int N, double count, int zero_coef, float* __restrict__ dgamma, float* __restrict__ dbeta,
     float* __restrict__ bwc) {
   __shared__ double sh[FIN_G][FIN_C][2];
-  __shared__ double sh2[FIN_G / 8][FIN_C][2];
   const int cc = threadIdx.x % FIN_C, rg = threadIdx.x / FIN_C, c = blockIdx.x * FIN_C + cc;
   double a1 = 0.0, a2 = 0.0;
   if (c < N)
@@ -252,26 +223,9 @@ __global__ void __launch_bounds__(FIN_C * FIN_G) k_bn_pool_bwd_finalize(
       a1 += (double)(d * Fsum[(int64_t)g * N + c]);
       a2 += (double)(d * Fsum[(int64_t)(B + g) * N + c]);
     }
-  sh[rg][cc][0] = a1;
-  sh[rg][cc][1] = a2;
-  __syncthreads();
-  if (rg < FIN_G / 8) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { t1 += sh[8 * rg + k][cc][0]; t2 += sh[8 * rg + k][cc][1]; }
-    sh2[rg][cc][0] = t1;
-    sh2[rg][cc][1] = t2;
-  }
-  __syncthreads();
-  if (rg == 0 && c < N) {
-    double S1 = 0.0, S2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < FIN_G / 8; ++k) { S1 += sh2[k][cc][0]; S2 += sh2[k][cc][1]; }
-    dbeta[c] = (float)S1;
-    dgamma[c] = (float)S2;
-    bwc[c] = zero_coef ? 0.f : (float)(S1 / count);
-    bwc[N + c] = zero_coef ? 0.f : (float)(S2 / count);
-  }
+  double S1, S2;
+  fold_groups(a1, a2, sh, S1, S2);
+  if (rg == 0 && c < N) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, N, c);
 }
 
 // forward apply (BWD=false): X' = drop(act(a*Y+b)), keep bytes out
@@ -282,7 +236,7 @@ __global__ void __launch_bounds__(256) k_bn_act_apply(
     const float* __restrict__ bwc, int relu, DropCfg drop, int use_drop,
     uint8_t* __restrict__ mask_out, const uint8_t* __restrict__ mask_in, T* __restrict__ out,
     int64_t M, int N, int relu_in, double* __restrict__ colsum_slab, PoolGrad pg) {
-  if (drop.dev_key) drop.key1 ^= drop.dev_key[0];
+  drop = drop_resolve(drop);
   const int nch = N >> 2;
   const int64_t total = M * nch;
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);   // column sums of dY: this thread's chunk is fixed
@@ -353,7 +307,7 @@ __global__ void __launch_bounds__(PTHR) k_bn_act_pool_fwd(
     const T* __restrict__ Y, const float* __restrict__ coef, int relu, DropCfg drop, int use_drop,
     uint8_t* __restrict__ mask_out, const int32_t* __restrict__ gptr, int B, float* __restrict__ P,
     int N, int CS, float* __restrict__ Fsum) {
-  if (drop.dev_key) drop.key1 ^= drop.dev_key[0];
+  drop = drop_resolve(drop);
   extern __shared__ float pred[];                    // [rpp][N / CS] (x 3 with factor sums)
   const int nch = N >> 2, nchb = nch / CS, NB = N / CS;
   const int cl = threadIdx.x % nchb, rr = threadIdx.x / nchb, rpp = PTHR / nchb;

@@ -33,7 +33,9 @@
 #include "common.h"
 #include "agg_block.h"
 #include "split_bf16.h"
+#include "bn_coef.h"
 #include "bn_tail.h"
+#include "drop_ew.h"
 #include "l0src.h"
 
 // streamed operands / results of the tile kernels (each read or written once per launch)
@@ -71,40 +73,6 @@ constexpr int NWAVE = 8;
 constexpr int NTHR = NWAVE * 64;            // 512
 constexpr int SLD = 68;                     // staging row stride (floats)
 constexpr int STG_FLOATS = 16 * SLD;        // per wave
-
-struct DropCfg {
-  uint32_t thr16;     // keep iff 16-bit hash >= thr16  (thr16 = round(p * 65536))
-  float scale;        // 1 / (1 - p)
-  uint32_t key0, key1;
-  const uint32_t* dev_key;   // optional device word XOR-ed into key1 (graph replay: a captured
-                             // kernel advances it, so replays draw fresh masks)
-};
-
-__device__ __forceinline__ DropCfg drop_resolve(DropCfg d) {
-  if (d.dev_key) d.key1 ^= d.dev_key[0];
-  return d;
-}
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
-
-// 4 keep-bits for the float4 at (global row, chunk); bit i <-> column 4*chunk + i.  One keyed
-// counter hash gives the first 32 random bits, a second round of the same mixer the other 32
-// (chained, not a second counter: half the multiplies of two independent hashes).
-__device__ __forceinline__ uint32_t drop_bits(const DropCfg& d, uint32_t row, uint32_t chunk) {
-  const uint32_t e = row * 16u + chunk;
-  const uint32_t h0 = mix32((e ^ d.key0) + d.key1);
-  const uint32_t h1 = mix32(h0 + 0x9E3779B9u);
-  uint32_t b = 0;
-  b |= ((h0 & 0xFFFFu) >= d.thr16) ? 1u : 0u;
-  b |= ((h0 >> 16) >= d.thr16) ? 2u : 0u;
-  b |= ((h1 & 0xFFFFu) >= d.thr16) ? 4u : 0u;
-  b |= ((h1 >> 16) >= d.thr16) ? 8u : 0u;
-  return b;
-}
-
 
 // x = drop(relu(a*y + b)); returns x, and the combined (z>0 & keep) factor per component in f.
 __device__ __forceinline__ float4 act4(const float4& y, const float4& a, const float4& b,
@@ -274,7 +242,7 @@ __global__ void __launch_bounds__(NTHR) k_gcn_fwd(
           if (row < n) {
             uint32_t keep = 0xFu;
             if (use_drop) {
-              keep = drop_bits(drop, (uint32_t)(base + row), (uint32_t)j);
+              keep = drop_bits(drop, (uint32_t)(base + row) * 16u + (uint32_t)j);
               if (mask_out) mask_out[(int64_t)(base + row) * 16 + j] = (uint8_t)keep;
             }
             float4 f;
@@ -552,7 +520,7 @@ __global__ void __launch_bounds__(PF_NTHR) k_gcn_fwd_pf(
           const int c = 2 * ms + h2;
           uint32_t keep = 0xFu;
           if (use_drop) {
-            keep = drop_bits(drop, (uint32_t)(base + row), (uint32_t)(4 * c + q));
+            keep = drop_bits(drop, (uint32_t)(base + row) * 16u + (uint32_t)(4 * c + q));
             if (mask_out && live) mask_out[(int64_t)(base + row) * 16 + 4 * c + q] = (uint8_t)keep;
           }
           float4 f;
@@ -1080,7 +1048,7 @@ __global__ void __launch_bounds__(PTHR) k_pool_fwd(const float* __restrict__ Y,
         if (row < rend) {
           uint32_t keep = 0xFu;
           if (use_drop) {
-            keep = drop_bits(drop, (uint32_t)row, (uint32_t)j);
+            keep = drop_bits(drop, (uint32_t)row * 16u + (uint32_t)j);
             if (mask_out) mask_out[(int64_t)row * 16 + j] = (uint8_t)keep;
           }
           float4 f;
@@ -1137,7 +1105,6 @@ __global__ void __launch_bounds__(128) k_pool_bwd_sums(const float* __restrict__
 // The same sums folded over ALL graphs by one block per channel, finalised on the spot (per-rank
 // BatchNorm: no exchange between the sums and the coefficients) -- k_pool_bwd_sums +
 // k_bn_bwd_stats in one launch.
-__device__ __forceinline__ double block_sum256(double v, double* sh);
 __global__ void __launch_bounds__(256) k_pool_bwd_finalize(const float* __restrict__ dP,
                                                            const float* __restrict__ F1,
                                                            const float* __restrict__ F2,
@@ -1156,12 +1123,7 @@ __global__ void __launch_bounds__(256) k_pool_bwd_finalize(const float* __restri
     a2 += d * (double)F2[(int64_t)g * HID + c];
   }
   const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)S1;
-    dgamma[c] = (float)S2;
-    bwc[c] = zero_coef ? 0.f : (float)(S1 / count);
-    bwc[HID + c] = zero_coef ? 0.f : (float)(S2 / count);
-  }
+  if (threadIdx.x == 0) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, HID, c);
 }
 
 constexpr int PBTHR = 1024;  // readout backward: 64 row-lanes x 16 chunks (16 waves per CU)
@@ -1279,28 +1241,10 @@ __global__ void k_bn_finalize(const double* __restrict__ sums, double count,
   if (c >= HID) return;
   if (count_dev) count = count_dev[0];
   // mean_offset (nullable): the statistics are those of y - mean_offset[c] (the factored layer 0 is
-  // handed on without its constant term); the module's running mean is that of y
-  const double off = mean_offset ? (double)mean_offset[c] : 0.0;
-  float mean, var;
-  if (training) {
-    const double m = sums[c] / count;
-    double v = sums[HID + c] / count - m * m;            // biased batch variance
-    if (v < 0.0) v = 0.0;
-    mean = (float)m;
-    var = (float)v;
-    const double unbiased = count > 1.0 ? v * count / (count - 1.0) : v;
-    rmean[c] = (1.0f - momentum) * rmean[c] + momentum * (float)(m + off);
-    rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;
-  } else {
-    mean = (float)((double)rmean[c] - off);
-    var = rvar[c];
-  }
-  const float invstd = 1.0f / sqrtf(var + eps);
-  const float a = gamma[c] * invstd;
-  bn_out[c] = a;
-  bn_out[HID + c] = beta[c] - mean * a;
-  bn_out[2 * HID + c] = mean;
-  bn_out[3 * HID + c] = invstd;
+  // handed on without its constant term); the module's running mean is that of y.  sums: NULL in eval
+  const double S1 = training ? sums[c] : 0.0, S2 = training ? sums[HID + c] : 0.0;
+  bn_fwd_coef(training, S1, S2, count, gamma, beta, rmean, rvar, momentum, eps,
+              mean_offset ? mean_offset[c] : 0.f, bn_out, HID, c);
 }
 
 __global__ void k_bn_bwd_finalize(const double* __restrict__ sums, double count,
@@ -1310,22 +1254,10 @@ __global__ void k_bn_bwd_finalize(const double* __restrict__ sums, double count,
   const int c = threadIdx.x;
   if (c >= HID) return;
   if (count_dev) count = count_dev[0];
-  dbeta[c] = (float)sums[c];
-  dgamma[c] = (float)sums[HID + c];
-  bwc[c] = zero_coef ? 0.f : (float)(sums[c] / count);
-  bwc[HID + c] = zero_coef ? 0.f : (float)(sums[HID + c] / count);
+  bn_bwd_coef(sums[c], sums[HID + c], count, zero_coef, dgamma, dbeta, bwc, HID, c);
 }
 
 // ---- merged "reduce the per-workgroup partials + finalise" kernels (single-GPU fast path) ----
-// Block-wide fixed-order sum of v over 256 threads (4 waves).
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-  v = cgnn_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double t = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return t;
-}
 
 // one block per channel c: S1 = sum_r slab[r][c], S2 = sum_r slab[r][64+c], then finalise
 __global__ void __launch_bounds__(256) k_bn_fwd_stats(
@@ -1335,10 +1267,10 @@ __global__ void __launch_bounds__(256) k_bn_fwd_stats(
     uint32_t* __restrict__ rng_state, int rng_n, const float* __restrict__ mean_offset) {
   __shared__ double sh[4];
   const int c = blockIdx.x;
-  // graph replay: refresh the device dropout words here (cgnn_rng_advance's arithmetic) -- this
-  // launch runs after every consumer of the previous step's words and before the first of this one
+  // graph replay: refresh the device dropout words here -- this launch runs after every consumer of
+  // the previous step's words and before the first of this one
   if (rng_state && c == 0 && (int)threadIdx.x < rng_n)
-    rng_state[threadIdx.x] = mix32(rng_state[threadIdx.x] + 0x9E3779B9u * (uint32_t)(threadIdx.x + 1));
+    rng_state[threadIdx.x] = rng_refresh(rng_state[threadIdx.x], threadIdx.x);
   double a1 = 0.0, a2 = 0.0;
   for (int r = threadIdx.x; r < rows; r += 256) {
     a1 += slab[(int64_t)r * 128 + c];
@@ -1346,21 +1278,8 @@ __global__ void __launch_bounds__(256) k_bn_fwd_stats(
   }
   const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
   if (threadIdx.x == 0) {
-    const double m = S1 / count;
-    double v = S2 / count - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mean = (float)m, var = (float)v;
-    const double unbiased = count > 1.0 ? v * count / (count - 1.0) : v;
-    // (mean_offset: the statistics are those of y - offset, the running mean is that of y)
-    const float mean_y = mean_offset ? (float)(m + (double)mean_offset[c]) : mean;
-    rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean_y;
-    rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float a = gamma[c] * invstd;
-    bn_out[c] = a;
-    bn_out[HID + c] = beta[c] - mean * a;
-    bn_out[2 * HID + c] = mean;
-    bn_out[3 * HID + c] = invstd;
+    bn_fwd_coef(true, S1, S2, count, gamma, beta, rmean, rvar, momentum, eps,
+                mean_offset ? mean_offset[c] : 0.f, bn_out, HID, c);
     if (c == 0 && tracked) *tracked += 1;
   }
 }
@@ -1378,12 +1297,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_stats(const double* __restrict__
     a2 += slab[(int64_t)r * 128 + HID + c];
   }
   const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)S1;
-    dgamma[c] = (float)S2;
-    bwc[c] = zero_coef ? 0.f : (float)(S1 / count);
-    bwc[HID + c] = zero_coef ? 0.f : (float)(S2 / count);
-  }
+  if (threadIdx.x == 0) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, HID, c);
 }
 
 // dW (f32 slab [rows][64*out_cols]) and db (f64 slab [rows][64]) in one launch.  A block folds
@@ -1455,14 +1369,6 @@ __device__ __forceinline__ void dw_db_reduce_block(const float* __restrict__ dw_
   }
 }
 
-__global__ void __launch_bounds__(RD_C * RD_G) k_dw_db_reduce(const float* __restrict__ dw_slab,
-                                                      const double* __restrict__ db_slab, int rows,
-                                                      int out_cols, int take_cols,
-                                                      float* __restrict__ dW, int ldw,
-                                                      float* __restrict__ db) {
-  dw_db_reduce_block(dw_slab, db_slab, rows, out_cols, take_cols, dW, ldw, db, blockIdx.x);
-}
-
 // several layers' slabs in ONE launch (the reductions do not feed the backward chain, so they can
 // all wait for its end: one launch instead of one per layer)
 __global__ void __launch_bounds__(RD_C * RD_G) k_dw_db_reduce_multi(cgnn_dw_jobs jobs) {
@@ -1495,24 +1401,9 @@ int fused_grid() {
   return g_grid_cache[dev];
 }
 
-DropCfg make_drop(float p, uint64_t seed, int* use_drop) {
-  DropCfg d;
-  *use_drop = (p > 0.f) ? 1 : 0;
-  double thr = (double)p * 65536.0 + 0.5;
-  if (thr > 65535.0) thr = 65535.0;
-  d.thr16 = (uint32_t)thr;
-  // the reference's scale, 1/(1-p) (aten::native_dropout), not 1/(realised keep rate): with
-  // replayed keep bits the arithmetic then matches the oracle to rounding
-  d.scale = p > 0.f ? (float)(1.0 / (1.0 - (double)p)) : 1.0f;
-  d.key0 = (uint32_t)(seed & 0xFFFFFFFFu) * 0x9E3779B9u + 0x85EBCA6Bu;
-  d.key1 = (uint32_t)(seed >> 32) ^ 0xC2B2AE35u;
-  d.dev_key = nullptr;
-  return d;
-}
-
 __global__ void k_rng_advance(uint32_t* state, int n) {
   const int i = threadIdx.x;
-  if (i < n) state[i] = mix32(state[i] + 0x9E3779B9u * (uint32_t)(i + 1));
+  if (i < n) state[i] = rng_refresh(state[i], i);
 }
 
 bool l0src_ok(const cgnn_l0src* l0) {
@@ -1727,19 +1618,6 @@ int cgnn_gcn_fused_bwd_first(const cgnn_tiles* t, const float* dZ, const float* 
   return CGNN_OK;
 }
 
-int cgnn_bn_stats_finalize(const double* slab, int32_t rows, double count, const float* gamma,
-                           const float* beta, float* running_mean, float* running_var,
-                           float momentum, float eps, int64_t* num_batches_tracked, float* bn_out,
-                           void* stream) {
-  if (!slab || rows <= 0 || count <= 0.0 || !gamma || !beta || !running_mean || !running_var || !bn_out)
-    return CGNN_EINVAL;
-  k_bn_fwd_stats<<<HID, 256, 0, cgnn_stream(stream)>>>(
-      slab, rows, count, gamma, beta, running_mean, running_var, momentum, eps,
-      reinterpret_cast<long long*>(num_batches_tracked), bn_out, nullptr, 0, nullptr);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
 int cgnn_bn_stats_finalize_rng(const double* slab, int32_t rows, double count, const float* gamma,
                                const float* beta, float* running_mean, float* running_var,
                                float momentum, float eps, int64_t* num_batches_tracked, float* bn_out,
@@ -1770,17 +1648,6 @@ int cgnn_bn_bwd_stats_finalize(const double* slab, int32_t rows, double count, i
                                float* dgamma, float* dbeta, float* bwc, void* stream) {
   if (!slab || rows <= 0 || count <= 0.0 || !dgamma || !dbeta || !bwc) return CGNN_EINVAL;
   k_bn_bwd_stats<<<HID, 256, 0, cgnn_stream(stream)>>>(slab, rows, count, zero_coef, dgamma, dbeta, bwc);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_dw_db_reduce(const float* dw_slab, const double* db_slab, int32_t rows, int32_t out_cols,
-                      int32_t take_cols, float* dW, int32_t ld_dw, float* db, void* stream) {
-  if (!dw_slab || !db_slab || !dW || !db || rows <= 0 || out_cols <= 0 || take_cols <= 0 ||
-      take_cols > out_cols || ld_dw < take_cols)
-    return CGNN_EINVAL;
-  k_dw_db_reduce<<<(HID * out_cols + HID) / RD_C, RD_C * RD_G, 0, cgnn_stream(stream)>>>(dw_slab, db_slab, rows, out_cols,
-                                                                 take_cols, dW, ld_dw, db);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
@@ -1829,14 +1696,6 @@ int cgnn_slab_reduce_f64_multi(const cgnn_reduce_jobs* jobs, void* stream) {
     wmax = jobs->width[j] > wmax ? jobs->width[j] : wmax;
   }
   k_slab_reduce_multi<<<dim3((wmax + 3) / 4, jobs->n), 256, 0, cgnn_stream(stream)>>>(*jobs);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_slab_reduce_f64(const double* slab, int32_t rows, int32_t width, float* out, void* stream) {
-  if (!slab || !out || rows <= 0 || width <= 0) return CGNN_EINVAL;
-  k_slab_reduce<double><<<(width + 3) / 4, 256, 0, cgnn_stream(stream)>>>(
-      slab, rows, width, nullptr, out, width, width, width);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

@@ -8,6 +8,7 @@
 // (row, output unit); the backward leaves per-workgroup partial parameter gradients in a slab
 // [grid][H2*H + H2 + C*H2 + C] that cgnn_slab_reduce_f32 combines in fixed order.
 #include "common.h"
+#include "drop_ew.h"
 
 namespace {
 
@@ -16,30 +17,25 @@ constexpr int HEAD_MAX_H = 256;          // input width (wider heads stay on the
                                          // 256: W1 [128 x 256] is 128 KB of the 160 KB LDS
 constexpr int HEAD_MAX_C = 16;           // classes
 
-__device__ __forceinline__ uint32_t hmix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
+// the head's dropout stream: keys of its own, one 16-bit draw per element (mix32(mix32(e ^ key0) + key1))
+DropCfg head_drop(float p, uint64_t seed, const uint32_t* seed_dev, int* use_drop) {
+  DropCfg d = make_drop(p, seed, use_drop, 0x7F4A7C15u, 0x94D049BBu);
+  d.dev_key = seed_dev;
+  return d;
 }
-
-struct HeadDrop {
-  uint32_t thr16;      // keep iff 16-bit hash >= thr16
-  float scale;         // 1 / (1 - p)
-  uint32_t key0, key1;
-  const uint32_t* dev_key;
-};
 
 // ---------------------------------------------------------------------------------- forward
 // block: rows [r0, r0 + RB), RB = HTHR / H2 (H2 <= 128 -> RB >= 2)
 __global__ void __launch_bounds__(HTHR) k_head_fwd(
     const float* __restrict__ P, int B, int H, int H2, int C, const float* __restrict__ W1,
     const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
-    HeadDrop drop, int use_drop, float* __restrict__ H1, float* __restrict__ fac,
+    DropCfg drop, int use_drop, float* __restrict__ H1, float* __restrict__ fac,
     float* __restrict__ logits) {
   extern __shared__ float sm[];
   float* w1 = sm;                          // [H2][H + 1]
   float* pl = w1 + H2 * (H + 1);           // [RB][H]
   float* hl = pl + (HTHR / H2) * H;        // [RB][H2]
-  if (drop.dev_key) drop.key1 ^= drop.dev_key[0];
+  drop = drop_resolve(drop);
   const int RB = HTHR / H2;
   // (16-byte loads, eight in flight: the scalar one-at-a-time form was a chain of 128 round trips
   // for a 128 x 256 weight -- 22 us of a 64-graph batch's step)
@@ -80,7 +76,7 @@ __global__ void __launch_bounds__(HTHR) k_head_fwd(
       float f = z > 0.f ? 1.f : 0.f;
       if (use_drop) {
         const uint32_t e = (uint32_t)r * (uint32_t)H2 + (uint32_t)j;
-        const uint32_t hsh = hmix32(hmix32(e ^ drop.key0) + drop.key1);
+        const uint32_t hsh = mix32(mix32(e ^ drop.key0) + drop.key1);
         f = ((hsh & 0xFFFFu) >= drop.thr16) ? f * drop.scale : 0.f;
       }
       const float hv = z * f;
@@ -406,7 +402,7 @@ template <int H, int H2, int C, int HBR>
 __global__ void __launch_bounds__(256) k_head_loss_t(
     const float* __restrict__ P, int B, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ W2, const float* __restrict__ b2, const int64_t* __restrict__ labels,
-    HeadDrop drop, int use_drop, float* __restrict__ H1, float* __restrict__ fac,
+    DropCfg drop, int use_drop, float* __restrict__ H1, float* __restrict__ fac,
     float* __restrict__ logits, float* __restrict__ dP, float* __restrict__ slab) {
   constexpr int KT = H / 16, JT = H2 / 16;
   constexpr int TPR = 256 / HBR;
@@ -420,7 +416,7 @@ __global__ void __launch_bounds__(256) k_head_loss_t(
   __shared__ int cnt[256];
   __shared__ double lred[HBR];
   const int t = threadIdx.x;
-  if (drop.dev_key) drop.key1 ^= drop.dev_key[0];
+  drop = drop_resolve(drop);
   if ((reinterpret_cast<uintptr_t>(W1) & 15) == 0) {     // 16-byte loads, eight in flight
     constexpr int N4 = H2 * H / 4;
     for (int i0 = t; i0 < N4; i0 += 8 * 256) {
@@ -492,7 +488,7 @@ __global__ void __launch_bounds__(256) k_head_loss_t(
       float f = z > 0.f ? 1.f : 0.f;
       if (use_drop) {
         const uint32_t e = (uint32_t)r * (uint32_t)H2 + (uint32_t)j;
-        const uint32_t hsh = hmix32(hmix32(e ^ drop.key0) + drop.key1);
+        const uint32_t hsh = mix32(mix32(e ^ drop.key0) + drop.key1);
         f = ((hsh & 0xFFFFu) >= drop.thr16) ? f * drop.scale : 0.f;
       }
       const float hv = r < B ? z * f : 0.f;
@@ -676,18 +672,12 @@ int cgnn_head_fwd_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t 
   if (!head_ok(H, H2, C)) return CGNN_EUNSUPPORTED;
   if (B == 0) return CGNN_OK;
   if (!P || !W1 || !b1 || !W2 || !b2 || !H1 || !fac || !logits) return CGNN_EINVAL;
-  HeadDrop d;
-  double thr = (double)p_drop * 65536.0 + 0.5;
-  if (thr > 65535.0) thr = 65535.0;
-  d.thr16 = (uint32_t)thr;
-  d.scale = p_drop > 0.f ? (float)(1.0 / (1.0 - (double)p_drop)) : 1.0f;   // reference: 1/(1-p)
-  d.key0 = (uint32_t)(seed & 0xFFFFFFFFu) * 0x9E3779B9u + 0x7F4A7C15u;
-  d.key1 = (uint32_t)(seed >> 32) ^ 0x94D049BBu;
-  d.dev_key = seed_dev;
+  int use_drop;
+  const DropCfg d = head_drop(p_drop, seed, seed_dev, &use_drop);
   const size_t lds = head_fwd_lds(H, H2);
   if (lds > 64 * 1024 && !head_allow_lds()) return CGNN_ELAUNCH;
   k_head_fwd<<<head_grid(B, H2), HTHR, lds, cgnn_stream(stream)>>>(
-      P, B, H, H2, C, W1, b1, W2, b2, d, p_drop > 0.f ? 1 : 0, H1, fac, logits);
+      P, B, H, H2, C, W1, b1, W2, b2, d, use_drop, H1, fac, logits);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
@@ -737,15 +727,8 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
   if (B <= 0 || p_drop < 0.f || p_drop >= 1.f) return CGNN_EINVAL;
   if (!head_ok(H, H2, C) || !head_tiled(H, H2, C)) return CGNN_EUNSUPPORTED;
   if (!P || !W1 || !b1 || !W2 || !b2 || !labels || !H1 || !fac || !logits || !dP || !slab) return CGNN_EINVAL;
-  HeadDrop d;
-  double thr = (double)p_drop * 65536.0 + 0.5;
-  if (thr > 65535.0) thr = 65535.0;
-  d.thr16 = (uint32_t)thr;
-  d.scale = p_drop > 0.f ? (float)(1.0 / (1.0 - (double)p_drop)) : 1.0f;
-  d.key0 = (uint32_t)(seed & 0xFFFFFFFFu) * 0x9E3779B9u + 0x7F4A7C15u;
-  d.key1 = (uint32_t)(seed >> 32) ^ 0x94D049BBu;
-  d.dev_key = seed_dev;
-  const int use = p_drop > 0.f ? 1 : 0;
+  int use;
+  const DropCfg d = head_drop(p_drop, seed, seed_dev, &use);
   const int rows = head_loss_rows(B, H);
   const int tg = head_loss_grid(B, H);
   CGNN_NEED_BYTES(slab, slab_bytes,

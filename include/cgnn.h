@@ -451,7 +451,7 @@ int cgnn_dense_aggregate_c16(const void* dfrag, const int32_t* dstep, const uint
  * fp32 (row gradient dP[graph] / (n_g + 1e-8)); exactly one of the two -- the layer's pre-BatchNorm
  * output Yl, keep bytes, coefficient block `coef` and the backward coefficients `bwc`.  dY feeds
  * nothing else but the bias gradient: its column sums are left per graph in cs_slab [B][F] fp64
- * (combine with cgnn_slab_reduce_f64(cs_slab, B, F, db)). */
+ * (combine with cgnn_slab_reduce_f64_multi: B rows of width F -> db). */
 int cgnn_dense_aggregate_c16_bnbwd(const void* dfrag, const int32_t* dstep, const uint32_t* doff,
                                    const uint32_t* sent, const int32_t* sstep, const uint32_t* soff,
                                    int32_t P, const int32_t* gptr, int32_t num_graphs, const void* dX,
@@ -669,16 +669,12 @@ typedef struct cgnn_adam_jobs {
 int cgnn_adam_step(const cgnn_adam_jobs* jobs, float* step, uint32_t* arrivals, int32_t advance,
                    double lr, double beta1, double beta2, double eps, double weight_decay, void* stream);
 
-/* Single-launch forms of (cgnn_bn_reduce + cgnn_bn_finalize [+ num_batches_tracked += 1]),
- * (cgnn_bn_reduce + cgnn_bn_bwd_finalize) and (cgnn_slab_reduce_f32 + cgnn_slab_reduce_f64):
- * used when no cross-rank exchange sits between the reduction and the finalisation.
- * zero_coef != 0 writes c1 = c2 = 0 (eval-mode BatchNorm backward is a fixed affine map). */
-int cgnn_bn_stats_finalize(const double* slab, int32_t rows, double count, const float* gamma,
-                           const float* beta, float* running_mean, float* running_var,
-                           float momentum, float eps, int64_t* num_batches_tracked, float* bn_out,
-                           void* stream);
-/* the same, also refreshing the rng_n (<= 64) device dropout words of a graph-captured step
- * (cgnn_rng_advance's arithmetic) in the same launch; rng_state NULL / rng_n 0: no refresh.
+/* Single-launch forms of (cgnn_bn_reduce + cgnn_bn_finalize [+ num_batches_tracked += 1]) and
+ * (cgnn_bn_reduce + cgnn_bn_bwd_finalize): used when no cross-rank exchange sits between the
+ * reduction and the finalisation.
+ * zero_coef != 0 writes c1 = c2 = 0 (eval-mode BatchNorm backward is a fixed affine map).
+ * cgnn_bn_stats_finalize_rng also refreshes the rng_n (<= 64) device dropout words of a graph-captured
+ * step (cgnn_rng_advance's arithmetic) in the same launch; rng_state NULL / rng_n 0: no refresh.
  * mean_offset (float[64], nullable; also cgnn_bn_finalize): the slab holds the statistics of
  * y - mean_offset[c] (the centred factored layer 0 is handed on without its constant term, which
  * BatchNorm's output does not depend on): bn_out describes that shifted variable, the module's
@@ -689,10 +685,9 @@ int cgnn_bn_stats_finalize_rng(const double* slab, int32_t rows, double count, c
                                uint32_t* rng_state, int32_t rng_n, const float* mean_offset, void* stream);
 int cgnn_bn_bwd_stats_finalize(const double* slab, int32_t rows, double count, int32_t zero_coef,
                                float* dgamma, float* dbeta, float* bwc, void* stream);
-int cgnn_dw_db_reduce(const float* dw_slab, const double* db_slab, int32_t rows, int32_t out_cols,
-                      int32_t take_cols, float* dW, int32_t ld_dw, float* db, void* stream);
-/* The same for up to CGNN_DW_MAX_JOBS layers in one launch (dW[i] dense [64][take_cols[i]]): the
- * reductions do not feed the backward chain, so all of a model's layers wait for its end. */
+/* The weight and bias gradients of up to CGNN_DW_MAX_JOBS layers from their per-workgroup slabs in one
+ * launch: dw_slab f32 [rows][64*out_cols] -> dW[i] dense [64][take_cols[i]], db_slab f64 [rows][64] ->
+ * db[i] [64].  The reductions do not feed the backward chain, so all of a model's layers wait for its end. */
 #define CGNN_DW_MAX_JOBS 8
 typedef struct cgnn_dw_jobs {
   int32_t n;
@@ -706,18 +701,17 @@ int cgnn_dw_db_reduce_multi(const cgnn_dw_jobs* jobs, void* stream);
 
 /* Fixed-order combination of per-workgroup partials (fp64 accumulate):
  * f32 slab [rows][width] -> out[r*ld_out + c] for width = out_rows*out_cols (take the first
- * `take_cols` of every `out_cols` columns); f64 slab [rows][width] -> f32 out [width]. */
+ * `take_cols` of every `out_cols` columns). */
 int cgnn_slab_reduce_f32(const float* slab, int32_t rows, int32_t out_rows, int32_t out_cols,
                          int32_t take_cols, float* out, int32_t ld_out, void* stream);
-int cgnn_slab_reduce_f64(const double* slab, int32_t rows, int32_t width, float* out,
-                         void* stream);
 /* f32 slab [rows][width] -> out[0..split) and out_tail[0..width-split): the same fold with its result in two
  * places -- the classifier's parameter gradients straight into a caller-owned gradient buffer (data-parallel
  * training: the flat all-reduce buffer) and the loss column of cgnn_head_loss_f32's slab next to it. */
 int cgnn_slab_reduce_f32_split(const float* slab, int32_t rows, int32_t width, int32_t split, float* out,
                                float* out_tail, void* stream);
-/* up to CGNN_REDUCE_MAX_JOBS of the f64 form in ONE launch (the bias gradients of every layer of a
- * backward pass: their per-block column sums are final long before the pass ends) */
+/* f64 slabs [rows[j]][width[j]] -> f32 out[j] [width[j]], up to CGNN_REDUCE_MAX_JOBS in ONE launch (the
+ * bias gradients of every layer of a backward pass: their per-block column sums are final long before
+ * the pass ends) */
 #define CGNN_REDUCE_MAX_JOBS 8
 typedef struct cgnn_reduce_jobs {
   int32_t n;
@@ -777,7 +771,7 @@ int cgnn_bn_act_bwd_finalize(const double* slab, int32_t rows, int32_t N, double
 /* relu_in != 0: Y is itself the output of a ReLU (SAGELayer, models.py:152): dY is additionally
  * masked by Y > 0, i.e. it is the gradient of the layer's pre-activation.  colsum_slab (nullable):
  * fp64 [cgnn_bn_act_apply_blocks(M, N)][N] per-block column sums of dY (the bias gradient),
- * combined with cgnn_slab_reduce_f64. */
+ * combined with cgnn_slab_reduce_f64_multi. */
 int64_t cgnn_bn_act_apply_blocks(int64_t M, int32_t N);
 int cgnn_bn_act_bwd_apply(const float* dX, const float* Y, const uint8_t* mask, const float* coef,
                           const float* bwc, int32_t relu, float p_drop, int32_t relu_in,
