@@ -52,10 +52,11 @@ def bn_modules_ok(model) -> bool:
     return True
 
 
-def ineligible(batch, structure, model=None) -> Optional[str]:
+def ineligible(batch, structure, model=None, input_grad_ok: bool = False) -> Optional[str]:
     """The reason shared by every one-node encoder's eligible() for not covering (model, batch), or None;
-    with `model`, its BatchNorm modules are checked too (bn_modules_ok)."""
-    if batch.node_features.requires_grad:
+    with `model`, its BatchNorm modules are checked too (bn_modules_ok).  input_grad_ok: the encoder returns
+    the gradient of the node features itself (fused.py) -- edge-weight gradients still come first."""
+    if batch.node_features.requires_grad and not input_grad_ok:
         return "node_features require grad"
     if edge_grad_requested(structure):
         return EDGE_GRAD_REASON

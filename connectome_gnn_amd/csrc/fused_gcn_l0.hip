@@ -14,7 +14,10 @@
 //              wherever they are needed (l0src.h), 32 instead of 256 bytes per node.
 //              25 KB of LDS per workgroup -> 6 workgroups per CU hide the gather latency.
 //   k_l0_bwd : dY0 = BatchNorm'(dZ0); dW0 += dY0^T P0; db0 += dY0  (no LDS tile, no metadata;
-//              Y0 read from HBM or rebuilt from the P0 row it loads anyway).
+//              Y0 read from HBM or rebuilt from the P0 row it loads anyway).  Its WANT_G variant also
+//              writes G0 = dY0 W0 [Nn, 8] (32 bytes per node) for the node-feature gradient:
+//   k_l0_dx  : dX0 = A_hat^T G0, the mirror image of k_l0_fwd's phases 1-2 over the source-side
+//              blocked-ELL (dis * G0 -> LDS [rows][8], one thread per source row); no statistics.
 #include "common.h"
 #include "l0src.h"
 #include "bn_tail.h"
@@ -295,8 +298,16 @@ __global__ void __launch_bounds__(L0THR, WRITE_Y ? 5 : CGNN_L0_MINW) k_l0_fwd(cg
   }
 }
 
+// v of another lane of this lane's DPP row (16 consecutive lanes): quad_perm [1,0,3,2] = lane ^ 1 (0xB1),
+// quad_perm [2,3,0,1] = lane ^ 2 (0x4E), row_ror:n = lane - n mod 16 (0x120 + n)
+#define L0_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false))
+
 // dW0[o][k] = sum_rows dY0[row][o] * P0[row][k];  db0[o] = sum_rows dY0[row][o]
-template <bool REBUILD>
+// WANT_G (REBUILD only): also G0[row][k] = sum_o dY0[row][o] * W0[o][k] (k < the true feature count, zero
+// up to 8) -- what the node-feature gradient dX0 = A_hat^T G0 aggregates (k_l0_dx).  W0 comes from the
+// `wl` image staged for the rebuild: in the centred form its first F0 - 1 rows (the function does not
+// depend on the centring constants, so the W0 c column takes no part).
+template <bool REBUILD, bool WANT_G = false>
 __global__ void __launch_bounds__(L0BTHR) k_l0_bwd(const float* __restrict__ dZ,
                                                   const float* __restrict__ Y, cgnn_l0src l0,
                                                   const float* __restrict__ bn,
@@ -304,7 +315,9 @@ __global__ void __launch_bounds__(L0BTHR) k_l0_bwd(const float* __restrict__ dZ,
                                                   const float* __restrict__ P0, int64_t nn,
                                                   float* __restrict__ dW_slab,
                                                   double* __restrict__ db_slab,
-                                                  const float* __restrict__ center) {
+                                                  const float* __restrict__ center,
+                                                  float* __restrict__ G0) {
+  static_assert(REBUILD || !WANT_G, "G0 takes W0 from the rebuild's LDS image");
   __shared__ float redw[16 * HID * FP];          // 32 KB
   __shared__ double redb[16 * HID];
   __shared__ __attribute__((aligned(16))) float wl[REBUILD ? L0_LDS_FLOATS : 4];
@@ -361,6 +374,38 @@ __global__ void __launch_bounds__(L0BTHR) k_l0_bwd(const float* __restrict__ dZ,
 #pragma unroll
           for (int k = 0; k < FP; ++k) dw[c][k] = fmaf(dy[c], pv[k], dw[c][k]);
         }
+        if (WANT_G) {
+          // this thread's 4 columns of the 64 -> F0 narrowing, then the sum over the 16 j-lanes of the
+          // row (one DPP row: `row` is uniform in it)
+          const int FG = center ? l0.F0 - 1 : l0.F0;
+          float g[FP];
+#pragma unroll
+          for (int k = 0; k < FP; ++k) {
+            g[k] = 0.f;
+            if (k < FG) {                            // wave-uniform
+              const float4 wk = ld4(wl + k * 64 + 4 * j);
+              g[k] = fmaf(dy[3], wk.w, fmaf(dy[2], wk.z, fmaf(dy[1], wk.y, dy[0] * wk.x)));
+            }
+          }
+          // reduce-scatter over the row's 16 lanes: halve the columns a lane carries across lane ^ 1, then
+          // lane ^ 2 (8 -> 4 -> 2, one select pair and one DPP add per kept column), then add the four lanes
+          // that carry the same pair (rotations by 8 and 4): lane (b0, b1) ends with columns 4 b0 + 2 b1, + 1
+          const bool b0 = j & 1, b1 = j & 2;
+          float h[4], tt[2];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float send = b0 ? g[k] : g[4 + k];
+            h[k] = (b0 ? g[4 + k] : g[k]) + L0_DPP(send, 0xB1);
+          }
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const float send = b1 ? h[k] : h[2 + k];
+            tt[k] = (b1 ? h[2 + k] : h[k]) + L0_DPP(send, 0x4E);
+          }
+          tt[0] += L0_DPP(tt[0], 0x128); tt[1] += L0_DPP(tt[1], 0x128);
+          tt[0] += L0_DPP(tt[0], 0x124); tt[1] += L0_DPP(tt[1], 0x124);
+          if (j < 4) *reinterpret_cast<float2*>(G0 + row * FP + 4 * (j & 1) + (j & 2)) = make_float2(tt[0], tt[1]);
+        }
       }
     }
   }
@@ -389,6 +434,71 @@ __global__ void __launch_bounds__(L0BTHR) k_l0_bwd(const float* __restrict__ dZ,
 #pragma unroll
     for (int r2 = 0; r2 < 16; ++r2) tot += redb[r2 * HID + threadIdx.x];
     db_slab[(int64_t)blockIdx.x * HID + threadIdx.x] = tot;
+  }
+}
+
+// dX0 = A_hat^T G0 with G0 = dY0 W0 [Nn, 8] (k_l0_bwd<true, true>): k_l0_fwd's phases 1-2 over the source-side
+// blocked-ELL (same entry format, the self-loop is an entry of it): per tile dis * G0 -> LDS [rows][8], one
+// thread per source row walks its entries, times dis[row], written unpadded ([Nn, F0]).  Rows without edges
+// get their self-loop term, empty tiles nothing.
+__global__ void __launch_bounds__(L0THR, CGNN_L0_MINW) k_l0_dx(cgnn_tiles t, const float* __restrict__ G0, int F0,
+                                                               float* __restrict__ dX0) {
+  __shared__ __attribute__((aligned(16))) float gs[MAXR * FP];       // 12 KB
+  const uint2* ent = static_cast<const uint2*>(t.ent_src);
+  for (int tid = blockIdx.x; tid < t.num_tiles; tid += gridDim.x) {
+    const int base = t.tile_ptr[tid];
+    const int n = t.tile_ptr[tid + 1] - base;
+    const int gb0 = t.tile_blk[tid];
+    // 1. dis * G0 -> LDS (half a row per thread and pass)
+    {
+      constexpr int NI = MAXR * FP / 4 / L0THR;        // 2 float4 per thread
+      float4 gv[NI];
+      float dvv[NI];
+#pragma unroll
+      for (int u = 0; u < NI; ++u) {
+        const int idx = threadIdx.x + L0THR * u, r = idx >> 1;
+        gv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        dvv[u] = 0.f;
+        if (r < n) {
+          gv[u] = ld4(G0 + (int64_t)(base + r) * FP + 4 * (idx & 1));
+          dvv[u] = t.dis[base + r];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < NI; ++u)
+        st4(gs + 4 * (threadIdx.x + L0THR * u),
+            make_float4(gv[u].x * dvv[u], gv[u].y * dvv[u], gv[u].z * dvv[u], gv[u].w * dvv[u]));
+    }
+    __syncthreads();
+    // 2. narrow transposed aggregate, one thread per source row (entries of 16 rows are contiguous)
+    for (int r = threadIdx.x; r < n; r += L0THR) {
+      const int b = r >> 4, i = r & 15;
+      const int off0 = t.blk_off_src[gb0 + b];
+      const int width = (t.blk_off_src[gb0 + b + 1] - off0) >> 4;
+      float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+      const uint2* e = ent + off0 + i;
+      constexpr int EB = CGNN_L0_EB;                   // entries in flight, as in k_l0_fwd<false>
+      for (int s0 = 0; s0 < width; s0 += EB) {
+        uint2 eb[EB];
+#pragma unroll
+        for (int u = 0; u < EB; ++u) eb[u] = s0 + u < width ? L0NTE(e + 16 * (s0 + u)) : make_uint2(0u, 0u);
+#pragma unroll
+        for (int u = 0; u < EB; ++u) {
+          const float w = __uint_as_float(eb[u].y);          // padding: weight 0, row 0
+          const float* src = gs + (eb[u].x >> 8) * FP;       // entry offset = 256 * local row
+          const float4 v0 = ld4(src), v1 = ld4(src + 4);
+          a0.x = fmaf(w, v0.x, a0.x); a0.y = fmaf(w, v0.y, a0.y); a0.z = fmaf(w, v0.z, a0.z); a0.w = fmaf(w, v0.w, a0.w);
+          a1.x = fmaf(w, v1.x, a1.x); a1.y = fmaf(w, v1.y, a1.y); a1.z = fmaf(w, v1.z, a1.z); a1.w = fmaf(w, v1.w, a1.w);
+        }
+      }
+      const float dv = t.dis[base + r];
+      const float av[FP] = {a0.x * dv, a0.y * dv, a0.z * dv, a0.w * dv, a1.x * dv, a1.y * dv, a1.z * dv, a1.w * dv};
+      float* out = dX0 + (int64_t)(base + r) * F0;
+#pragma unroll
+      for (int k = 0; k < FP; ++k)
+        if (k < F0) out[k] = av[k];
+    }
+    __syncthreads();                                   // (gs is restaged for the next tile)
   }
 }
 
@@ -491,9 +601,10 @@ int cgnn_gcn_l0_fwd(const cgnn_tiles* t, const float* X0, int32_t F0, const floa
   return CGNN_OK;
 }
 
-int cgnn_gcn_l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const float* bn,
-                    const float* bwc, const float* P0, int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes,
-                    double* db_slab, int64_t db_slab_bytes, const float* center, void* stream) {
+// cgnn_gcn_l0_bwd, and with G0 != NULL cgnn_gcn_l0_bwd_dx
+static int l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const float* bn,
+                  const float* bwc, const float* P0, int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes,
+                  double* db_slab, int64_t db_slab_bytes, const float* center, float* G0, void* stream) {
   if (num_nodes < 0 || !dZ || !bn || !bwc || !P0 || !dW_slab || !db_slab) return CGNN_EINVAL;
   if (!Y && !(l0 && l0->W0 && l0->b0 && l0->F0 >= 1 && l0->F0 <= FP)) return CGNN_EINVAL;
   if (center && (Y || l0->F0 < 2)) return CGNN_EINVAL;
@@ -501,10 +612,40 @@ int cgnn_gcn_l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const
   CGNN_NEED_BYTES(db_slab, db_slab_bytes, (int64_t)l0_grid(num_nodes) * HID * (int64_t)sizeof(double));
   if (Y)
     k_l0_bwd<false><<<l0_grid(num_nodes), L0BTHR, 0, cgnn_stream(stream)>>>(dZ, Y, cgnn_l0src{}, bn, bwc, P0,
-                                                                   num_nodes, dW_slab, db_slab, nullptr);
+                                                                   num_nodes, dW_slab, db_slab, nullptr, nullptr);
+  else if (G0)
+    k_l0_bwd<true, true><<<l0_grid(num_nodes), L0BTHR, 0, cgnn_stream(stream)>>>(dZ, nullptr, *l0, bn, bwc, P0,
+                                                                        num_nodes, dW_slab, db_slab, center, G0);
   else
     k_l0_bwd<true><<<l0_grid(num_nodes), L0BTHR, 0, cgnn_stream(stream)>>>(dZ, nullptr, *l0, bn, bwc, P0,
-                                                                  num_nodes, dW_slab, db_slab, center);
+                                                                  num_nodes, dW_slab, db_slab, center, nullptr);
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
+}
+
+int cgnn_gcn_l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const float* bn,
+                    const float* bwc, const float* P0, int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes,
+                    double* db_slab, int64_t db_slab_bytes, const float* center, void* stream) {
+  return l0_bwd(dZ, Y, l0, bn, bwc, P0, num_nodes, dW_slab, dW_slab_bytes, db_slab, db_slab_bytes, center, nullptr,
+                stream);
+}
+
+int cgnn_gcn_l0_bwd_dx(const float* dZ, const cgnn_l0src* l0, const float* bn, const float* bwc, const float* P0,
+                       int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes, double* db_slab,
+                       int64_t db_slab_bytes, const float* center, float* G0, int64_t G0_bytes, void* stream) {
+  if (!G0 || num_nodes < 0) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(G0, G0_bytes, num_nodes * FP * (int64_t)sizeof(float));
+  return l0_bwd(dZ, nullptr, l0, bn, bwc, P0, num_nodes, dW_slab, dW_slab_bytes, db_slab, db_slab_bytes, center, G0,
+                stream);
+}
+
+int cgnn_gcn_l0_dx(const cgnn_tiles* t, const float* G0, int32_t F0, float* dX0, int64_t dX0_bytes, void* stream) {
+  if (!t || F0 <= 0 || F0 > FP || t->max_tile_rows > CGNN_FUSED_MAX_ROWS) return t && F0 > FP ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (t->num_nodes < 0 || !G0 || !dX0) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(dX0, dX0_bytes, t->num_nodes * F0 * (int64_t)sizeof(float));
+  if (t->num_tiles == 0) return CGNN_OK;
+  if (!t->tile_ptr || !t->tile_blk || !t->blk_off_src || !t->ent_src || !t->dis) return CGNN_EINVAL;
+  k_l0_dx<<<l0_grid(t->num_nodes), L0THR, 0, cgnn_stream(stream)>>>(*t, G0, F0, dX0);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

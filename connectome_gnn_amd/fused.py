@@ -37,9 +37,13 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         return "edges cross graph boundaries"
     if structure.max_nodes_per_graph > MAX_ROWS:
         return f"a graph has more than {MAX_ROWS} nodes"
-    why = bn_stage.ineligible(batch, structure)
+    why = bn_stage.ineligible(batch, structure, input_grad_ok=True)
     if why is not None:
         return why
+    if batch.node_features.requires_grad and not _narrow0(len(model.convs), model.convs[0].linear.weight.shape[1]):
+        # dX0 = A_hat^T (dY0 W0) exists for the factored layer 0 only (cgnn_gcn_l0_bwd_dx, cgnn_gcn_l0_dx)
+        return ("node_features require grad: the fused path returns the input gradient from its narrow layer 0 "
+                "only (in_channels <= 8 and num_layers >= 2)")
     for bn in model.batch_norms:
         if not (bn.affine and bn.track_running_stats) or bn.momentum is None:
             return "BatchNorm without affine/running stats/momentum"
@@ -48,6 +52,11 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
 
 def _tiles_struct(s: BatchStructure, meta, dis: torch.Tensor):
     return s.tiles_struct(meta, dis)
+
+
+def _narrow0(num_layers: int, in_channels: int) -> bool:
+    """Layer 0 runs in the narrow (factored) form of csrc/fused_gcn_l0.hip."""
+    return num_layers >= 2 and in_channels <= 8
 
 
 _ZEROS = {}
@@ -136,7 +145,8 @@ def _tail_bwd(bn_mod, dev, count, zero_coef, dgamma, dbeta, bwc) -> "_lib.CgnnBn
 
 
 class FusedGCNEncode(torch.autograd.Function):
-    """P[B,64] = mean-pool(GCN stack(x0)); args = x0, then (W, b, gamma, beta) per layer."""
+    """P[B,64] = mean-pool(GCN stack(x0)); args = x0, then (W, b, gamma, beta) per layer.  Differentiable
+    in the parameters and, with the narrow layer 0, in x0."""
 
     @staticmethod
     def forward(ctx, x0, meta, *params):
@@ -165,7 +175,10 @@ class FusedGCNEncode(torch.autograd.Function):
         masks: List[Optional[torch.Tensor]] = []
         local_count = count = float(nn_)
         count_dev = None                           # device copy of the global row count (sync-BN)
-        narrow0 = L >= 2 and x0.shape[1] <= 8      # layer-0 narrow form (fused_gcn_l0.hip)
+        narrow0 = _narrow0(L, x0.shape[1])         # layer-0 narrow form (fused_gcn_l0.hip)
+        if ctx.needs_input_grad[0] and not narrow0:
+            raise RuntimeError("FusedGCNEncode: the input gradient exists for the narrow layer 0 only "
+                               "(in_channels <= 8, num_layers >= 2)")
         p0 = l0src = l0keep = None
         _sp = _lib.stream_ptr(dev)          # one lookup per pass (torch.cuda.current_stream is ~10 us)
         st = lambda: _sp
@@ -276,7 +289,7 @@ class FusedGCNEncode(torch.autograd.Function):
             seed = _lib.next_seed(dev) if p > 0 else 0
             pooled = torch.empty(B, HID, **f32)
             # per-graph factor sums: the readout backward needs no second pass over Y
-            want_grad = any(ctx.needs_input_grad[2:])
+            want_grad = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:])
             fsum = torch.empty(2, B, HID, **f32) if want_grad else None
             with _lib.timed("cgnn_gcn_fused_pool_fwd"):
                 _lib.check(lib.cgnn_gcn_fused_pool_fwd(
@@ -407,16 +420,29 @@ class FusedGCNEncode(torch.autograd.Function):
                     bwc = bn_backward(l - 1)
                 dz, dz_prev = dz_prev, dz
             dw0, db0 = out(0, HID, c.f0), out(1, HID)
+            dx0 = None
             if c.p0 is not None:
                 # dW0 = dY0^T P0, db0 = sum dY0: streaming, no aggregation (fused_gcn_l0.hip)
                 g0 = lib.cgnn_l0_grid(nn_)
                 dw_slab0 = torch.empty(g0, HID * 8, **f32)
                 db_slab0 = torch.empty(g0, HID, **f64)
-                with _lib.timed("cgnn_gcn_l0_bwd"):
-                    _lib.check(lib.cgnn_gcn_l0_bwd(
-                        _lib.ptr(dz), None, ctypes.byref(c.l0src), _lib.ptr(c.bns[0]), _lib.ptr(bwc),
-                        _lib.ptr(c.p0), nn_, _lib.ptr(dw_slab0), _lib.nbytes(dw_slab0), _lib.ptr(db_slab0), _lib.nbytes(db_slab0), _lib.ptr(c.l0keep[2]), st()),
-                        "cgnn_gcn_l0_bwd")
+                l0_args = (ctypes.byref(c.l0src), _lib.ptr(c.bns[0]), _lib.ptr(bwc), _lib.ptr(c.p0), nn_,
+                           _lib.ptr(dw_slab0), _lib.nbytes(dw_slab0), _lib.ptr(db_slab0), _lib.nbytes(db_slab0),
+                           _lib.ptr(c.l0keep[2]))
+                if ctx.needs_input_grad[0]:
+                    # ... and the node-feature gradient dX0 = A_hat^T G0 with G0 = dY0 W0 [Nn, 8]: the 64 -> F0
+                    # narrowing rides in the same streaming pass, then one narrow transposed aggregate
+                    gbuf = torch.empty(nn_, 8, **f32)
+                    dx0 = torch.empty(nn_, c.f0, **f32)
+                    with _lib.timed("cgnn_gcn_l0_bwd_dx"):
+                        _lib.check(lib.cgnn_gcn_l0_bwd_dx(_lib.ptr(dz), *l0_args, _lib.ptr(gbuf), _lib.nbytes(gbuf), st()),
+                                   "cgnn_gcn_l0_bwd_dx")
+                    with _lib.timed("cgnn_gcn_l0_dx"):
+                        _lib.check(lib.cgnn_gcn_l0_dx(tp, _lib.ptr(gbuf), c.f0, _lib.ptr(dx0), _lib.nbytes(dx0), st()),
+                                   "cgnn_gcn_l0_dx")
+                else:
+                    with _lib.timed("cgnn_gcn_l0_bwd"):
+                        _lib.check(lib.cgnn_gcn_l0_bwd(_lib.ptr(dz), None, *l0_args, st()), "cgnn_gcn_l0_bwd")
                 jobs.append((dw_slab0, db_slab0, g0, 8, c.f0, dw0, db0))
             else:
                 extra = pool_args if L == 1 else none_args
@@ -439,7 +465,7 @@ class FusedGCNEncode(torch.autograd.Function):
                     jb.dW[i], jb.db[i] = dw_o.data_ptr(), db_o.data_ptr()
                 _lib.check(lib.cgnn_dw_db_reduce_multi(ctypes.byref(jb), st()), "cgnn_dw_db_reduce_multi")
         ctx.c = None
-        return (None, None, *ops.undelivered(grads, dst))
+        return (dx0, None, *ops.undelivered(grads, dst))
 
 
 def encode(model, batch, structure: BatchStructure) -> torch.Tensor:

@@ -63,6 +63,10 @@ def twin_view(structure, x: torch.Tensor):
     twin = getattr(structure, "__dict__", {}).get("_degree_twin")
     if twin is None:
         return structure, x, None
+    if x.requires_grad and torch.is_grad_enabled():
+        # a differentiable gather is made per pass and never cached (a second backward would walk the cached
+        # node again); its backward returns the encoder's dX0 to the batch's own node order
+        return twin, x.index_select(0, twin.perm), twin
     return twin, twin.permuted_features(x), twin
 
 
@@ -237,7 +241,7 @@ class BatchStructure:
         key = (x.data_ptr(), x._version, tuple(x.shape))
         hit = self.__dict__.get("_xperm")
         if hit is None or hit[0] != key:
-            hit = (key, x.index_select(0, self.perm).contiguous())
+            hit = (key, x.detach().index_select(0, self.perm).contiguous())
             self.__dict__["_xperm"] = hit
         return hit[1]
 

@@ -630,6 +630,18 @@ int cgnn_gcn_l0_fwd(const cgnn_tiles* t, const float* X0, int32_t F0, const floa
 int cgnn_gcn_l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const float* bn,
                     const float* bwc, const float* P0, int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes,
                     double* db_slab, int64_t db_slab_bytes, const float* center, void* stream);
+/* Node-feature gradient of the narrow layer 0 (ROI saliency).  With Y0 = (A_hat X0) W0^T + b:
+ *     G0  = dY0 W0          [Nn, 8] fp32, columns >= F0 zero: the 64 -> F0 narrowing of dY0 = BatchNorm'(dZ0)
+ *     dX0 = A_hat^T G0      [Nn, F0]: one narrow transposed aggregate over the source-side blocked-ELL
+ * cgnn_gcn_l0_bwd_dx is cgnn_gcn_l0_bwd in its rebuilding form (Y == NULL) that also writes G0
+ * (G0_bytes >= num_nodes * 8 * 4); the slabs it fills are those of cgnn_gcn_l0_bwd, bit for bit.  In the
+ * centred form (same `center`, l0->F0 = F0 + 1) G0 uses the first F0 columns of l0->W0 (`w_eff`): the
+ * function does not depend on the centring constants.  cgnn_gcn_l0_dx then writes dX0 unpadded
+ * (dX0_bytes >= num_nodes * F0 * 4) with F0 the TRUE feature count, 1..8; `t` as in cgnn_gcn_l0_fwd. */
+int cgnn_gcn_l0_bwd_dx(const float* dZ, const cgnn_l0src* l0, const float* bn, const float* bwc, const float* P0,
+                       int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes, double* db_slab,
+                       int64_t db_slab_bytes, const float* center, float* G0, int64_t G0_bytes, void* stream);
+int cgnn_gcn_l0_dx(const cgnn_tiles* t, const float* G0, int32_t F0, float* dX0, int64_t dX0_bytes, void* stream);
 
 /* fp16-storage forms of the BatchNorm(+ReLU)+dropout kernels (cgnn_bn_act_*): the [M,N] activation
  * arrays (Y, X, dX, dY) are IEEE half, the arithmetic is fp32, the statistics fp64, coefficient
