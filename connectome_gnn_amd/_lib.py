@@ -87,6 +87,10 @@ class CgnnGatherJobs(ctypes.Structure):
                 ("row_bytes", c_int64 * GATHER_MAX_JOBS)]
 
 
+# cgnn_collate_edges (include/cgnn.h): edges a thread moves with 16-byte accesses, edges per chunk of the
+# batch's flat edge range, and the batch size up to which the edge offsets are searched in LDS
+COLLATE_VEC, COLLATE_CHUNK, COLLATE_LDS_GRAPHS = 4, 1024, 4096
+
 REDUCE_MAX_JOBS = 8
 
 
@@ -191,6 +195,7 @@ PROTOTYPES = {
     "cgnn_gather_f32": (c_int, [P, P, I64, P, P]),
     "cgnn_gather_rows": (c_int, [ctypes.POINTER(CgnnGatherJobs), P, I32, P, P]),
     "cgnn_epoch_advance": (c_int, [P, I64, P, F32, P, P]),
+    "cgnn_collate_edges": (c_int, [P, P, P, I64, I64, P, I32, I32, I64, P, I64, P, I64, P, I64, P]),
     "cgnn_gcn_dis": (c_int, [P, P, I64, P, P]),
     "cgnn_fused_grid": (c_int, []),
     "cgnn_set_fused_grid": (c_int, [I32]),

@@ -76,6 +76,8 @@ class ConnectomeBatch:
     # host int64 [B+1]: edges of graph g are the COO run [_eptr[g], _eptr[g+1]) -- set by
     # collate_graphs / the resident assembler, lets the structure be built per graph in LDS
     _eptr: object = field(default=None, init=False, repr=False, compare=False)
+    # the same offsets on the device as int32, when the assembler already left them there (cgnn_collate_edges)
+    _eptr_dev: object = field(default=None, init=False, repr=False, compare=False)
 
     @property
     def num_graphs(self) -> int:
@@ -94,6 +96,8 @@ class ConnectomeBatch:
         if out.edge_index.data_ptr() == self.edge_index.data_ptr():
             out._structure, out._structure_key = self._structure, self._structure_key
         out._eptr = self._eptr
+        if out.edge_index.data_ptr() == self.edge_index.data_ptr():
+            out._eptr_dev = self._eptr_dev
         return out
 
     def _edge_key(self):
@@ -116,7 +120,7 @@ class ConnectomeBatch:
         if self._structure is None or self._structure_key != key:
             from .structure import BatchStructure
             if self._structure is not None:
-                self._eptr = None            # the per-graph edge offsets described the old COO
+                self._eptr = self._eptr_dev = None    # the per-graph edge offsets described the old COO
             self._structure = BatchStructure.build(self)
             self._structure_key = key
         return self._structure

@@ -2,9 +2,14 @@
 
 The reference collates on the host in a per-graph Python loop (graph.py:149-158, 0.19 s per
 512 graphs) and copies six tensors per step (train.py:46; 454 MB at 4096 x 360 ROI).  For
-regular datasets (every graph n nodes, e edges -- true of the Watts-Strogatz connectomes) the
-whole dataset sits in HBM as dense arrays and a batch is a gather by subject id plus the
-block-diagonal node offset: same int64 content as ``collate_graphs``, no host work.
+same-atlas datasets (every graph n nodes) the whole dataset sits in HBM and a batch is assembled
+there, same int64 content as ``collate_graphs``, no host work:
+
+  * every graph e edges (true of the Watts-Strogatz connectomes; ``PackedDataset``, dense
+    [S, 2, e] arrays): a gather by subject id plus the block-diagonal node offset;
+  * edge counts that differ per subject (thresholded matrices; ``RaggedPackedDataset``, flat edge
+    arrays + an edge pointer): one HIP launch copies every subject's run (cgnn_collate_edges,
+    csrc/collate.hip) and writes the batch's device edge offsets for the grouped CSR build.
 """
 from __future__ import annotations
 
@@ -12,11 +17,18 @@ import torch
 
 from .graph import ConnectomeBatch, shard_slice
 from .structure import call_prepare
-from .synthetic import PackedDataset
+from .synthetic import PackedDataset, RaggedPackedDataset
 
 
-def assemble_batch(ds: PackedDataset, subject_ids: torch.Tensor) -> ConnectomeBatch:
-    """Bit-identical to ``collate_graphs([ds.graph(i) for i in subject_ids])``."""
+def assemble_batch(ds, subject_ids: torch.Tensor, host_ids: torch.Tensor = None) -> ConnectomeBatch:
+    """Bit-identical to ``collate_graphs([ds.graph(i) for i in subject_ids])``.
+
+    A ``RaggedPackedDataset`` needs the batch's edge count on the host to allocate the COO: it comes from
+    the host copy of ``edge_ptr`` and ``host_ids`` (the same ids on the host, which ``ResidentDataLoader``
+    carries along with the device slice of its permutation) or from ``subject_ids`` itself when that is a
+    host tensor; ids that exist on the device only cost one read-back of the ids."""
+    if isinstance(ds, RaggedPackedDataset):
+        return _assemble_ragged(ds, subject_ids, host_ids)
     dev = ds.x.device
     ids = subject_ids.to(dev)
     b = int(ids.numel())
@@ -35,12 +47,51 @@ def assemble_batch(ds: PackedDataset, subject_ids: torch.Tensor) -> ConnectomeBa
     return out
 
 
+def _assemble_ragged(ds: RaggedPackedDataset, subject_ids: torch.Tensor, host_ids) -> ConnectomeBatch:
+    from . import _lib
+    dev = ds.x.device
+    if dev.type != "cuda":
+        raise ValueError("a RaggedPackedDataset is collated by a HIP kernel: move it to the GPU first (ds.to('cuda'))")
+    if host_ids is None:
+        host_ids = subject_ids.cpu()                  # device-only ids: the one read-back
+    host_ids = host_ids.to(torch.long)
+    ids = subject_ids.to(device=dev, dtype=torch.long).contiguous()
+    b = int(ids.numel())
+    n = int(ds.x.shape[1])
+    if b and not (0 <= int(host_ids.min()) and int(host_ids.max()) < ds.num_subjects):
+        raise IndexError(f"subject ids must lie in [0, {ds.num_subjects})")
+    eptr = torch.zeros(b + 1, dtype=torch.long)
+    eptr[1:] = torch.cumsum(ds.edge_ptr[host_ids + 1] - ds.edge_ptr[host_ids], 0)
+    ne = int(eptr[-1])
+    edge_index = torch.empty(2, ne, dtype=torch.long, device=dev)
+    edge_weight = torch.empty(ne, dtype=torch.float32, device=dev)
+    # all zeros when the batch has no edge: the library then launches and writes nothing
+    eptr_dev = (torch.empty if ne else torch.zeros)(b + 1, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(_lib.load().cgnn_collate_edges(
+            _lib.ptr(ds.edge_local), _lib.ptr(ds.edge_weight), _lib.ptr(ds.edge_ptr_dev), ds.num_subjects,
+            int(ds.edge_weight.numel()), _lib.ptr(ids), b, n, ne, _lib.ptr(edge_index), _lib.nbytes(edge_index),
+            _lib.ptr(edge_weight), _lib.nbytes(edge_weight), _lib.ptr(eptr_dev), _lib.nbytes(eptr_dev),
+            _lib.stream_ptr(dev)), "cgnn_collate_edges")
+    out = ConnectomeBatch(
+        node_features=ds.x.index_select(0, ids).reshape(b * n, -1),
+        edge_index=edge_index,
+        edge_weight=edge_weight,
+        batch=torch.arange(b, device=dev, dtype=torch.long).repeat_interleave(n),
+        labels=ds.labels.index_select(0, ids),
+        ptr=torch.arange(b + 1, device=dev, dtype=torch.long) * n,
+    )
+    out._eptr = eptr                                  # host: the grouped CSR build's per-graph edge runs
+    out._eptr_dev = eptr_dev                          # ... and the same offsets as the kernel left them (int32)
+    return out
+
+
 class ResidentDataLoader:
     """``ConnectomeDataLoader`` semantics (len = ceil, partial last batch, global-RNG shuffle)
-    over a PackedDataset that already lives on the device.  rank/world_size select this
+    over a PackedDataset / RaggedPackedDataset that already lives on the device.  rank/world_size select this
     rank's contiguous shard of every global batch (graph-sharded data parallelism)."""
 
-    def __init__(self, dataset: PackedDataset, batch_size: int = 16, shuffle=True,
+    def __init__(self, dataset, batch_size: int = 16, shuffle=True,
                  rank: int = 0, world_size: int = 1, prefetch: bool = False, prepare=None,
                  cache_batches: bool = False, structure_cache: bool = False):
         """shuffle: True (new random composition of every batch each epoch, the reference's
@@ -80,6 +131,12 @@ class ResidentDataLoader:
         """Subject ids of this rank's batches.  The permutation is drawn on the host (the global CPU
         generator, as the reference's loader does) and uploaded ONCE per epoch; a batch's ids are a
         slice of that device array, so handing a batch over costs no host-to-device copy."""
+        for chunk, _ in self._chunk_pairs():
+            yield chunk
+
+    def _chunk_pairs(self):
+        """(device ids, the same ids on the host) per batch: the host slice sizes a ragged batch's COO
+        from the dataset's host edge pointer, without reading the ids back."""
         n = self.dataset.num_subjects
         if self.shuffle == "batches":
             if self._fixed_order is None:
@@ -87,6 +144,7 @@ class ResidentDataLoader:
             order = self._fixed_order
         else:
             order = torch.randperm(n) if self.shuffle else torch.arange(n)
+        host = order
         dev = self.dataset.x.device
         if dev.type == "cuda":
             # (from pinned memory, asynchronously: a pageable upload would make the host wait for every
@@ -100,7 +158,7 @@ class ResidentDataLoader:
                     continue          # a tail smaller than the world: dropped on every rank
                 run = shard_slice(range(lo, hi), self.rank, self.world_size)   # a contiguous run
                 lo, hi = run.start, run.stop
-            yield order[lo:hi]
+            yield order[lo:hi], host[lo:hi]
 
     def _upload(self, order: torch.Tensor, dev) -> torch.Tensor:
         ring = self.__dict__.setdefault("_pinned", [])
@@ -121,16 +179,18 @@ class ResidentDataLoader:
         if self.structure_cache is not None and not self.cache_batches:
             from .structure_cache import ResidentBatch
 
-            def build(chunk):                       # three gathers; the structure is the cache's
-                return ResidentBatch(self.structure_cache, chunk)
+            def build(pair):                        # three gathers; the structure is the cache's
+                rb = ResidentBatch(self.structure_cache, pair[0])
+                rb._host_ids = pair[1]
+                return rb
         else:
-            def build(chunk):
-                return assemble_batch(self.dataset, chunk)
+            def build(pair):
+                return assemble_batch(self.dataset, pair[0], pair[1])
         if self.cache_batches:
             if self._cache is None:
                 self._cache = []
-                for chunk in self._chunks():
-                    b = assemble_batch(self.dataset, chunk)
+                for chunk, host in self._chunk_pairs():
+                    b = assemble_batch(self.dataset, chunk, host)
                     if self.prepare is not None:
                         call_prepare(self.prepare, b)        # kept batches: amortised structure work pays
                     self._cache.append(b)
@@ -140,8 +200,8 @@ class ResidentDataLoader:
                 yield self._cache[i]
             return
         if not self.prefetch or self.dataset.x.device.type != "cuda":
-            for chunk in self._chunks():
-                b = build(chunk)
+            for pair in self._chunk_pairs():
+                b = build(pair)
                 if self.prepare is not None:
                     self.prepare(b)
                 yield b
@@ -166,7 +226,7 @@ class ResidentDataLoader:
             return b, ev
 
         main = torch.cuda.current_stream(dev)
-        chunks = list(self._chunks())
+        chunks = list(self._chunk_pairs())
         nxt = make(chunks[0], main.record_event()) if chunks else None
         for i in range(len(chunks)):
             cur, ev = nxt

@@ -168,8 +168,11 @@ class BatchStructure:
                     and int(eptr[-1]) == ne and batch.num_graphs > 0):
                 # COO grouped by graph: whole graphs are built in LDS by one workgroup each
                 emax = int((eptr[1:] - eptr[:-1]).max())
+                eptr_dev = getattr(batch, "_eptr_dev", None)      # left on the device by the ragged collate
+                if eptr_dev is None or eptr_dev.device != dev or eptr_dev.numel() != eptr.numel():
+                    eptr_dev = eptr.to(device=dev, dtype=torch.int32)
                 rc = lib.cgnn_csr_build_grouped(
-                    _lib.ptr(ei), _lib.ptr(s.gptr), _lib.ptr(eptr.to(device=dev, dtype=torch.int32)),
+                    _lib.ptr(ei), _lib.ptr(s.gptr), _lib.ptr(eptr_dev),
                     batch.num_graphs, nn_, ne, s.max_nodes_per_graph, emax,
                     _lib.ptr(s.rowptr_dst), _lib.ptr(s.eid_dst), _lib.ptr(s.col_dst),
                     _lib.ptr(s.rowptr_src), _lib.ptr(s.eid_src), _lib.ptr(s.col_src),

@@ -26,8 +26,9 @@ issuing ~45 launches per step from Python, which is what a freshly shuffled batc
 (`Trainer(graph=True)` replays ONE captured step per batch size over such a loader).
 
 Scope: the per-tile fused GCN path (hidden 64) and the GraphSAGE encoder (sage_path.py; its own ELL
-family without self-loops and `den` per subject, built on first use) on regular datasets (<= 384 nodes
-per graph); anything else keeps the ordinary per-batch build.
+family without self-loops and `den` per subject, built on first use) on same-atlas datasets (<= 384 nodes
+per graph; the subjects' edge counts may differ -- a subject's entries sit at absolute, variable-length
+offsets of the cache arrays anyway); anything else keeps the ordinary per-batch build.
 """
 from __future__ import annotations
 
@@ -39,7 +40,6 @@ import torch
 from . import _lib
 from .graph import ConnectomeBatch
 from .structure import FusedMeta
-from .synthetic import PackedDataset
 
 MAX_ROWS = 384
 
@@ -59,7 +59,8 @@ class SubjectStructureCache:
     of a dataset, per model family (GCN: self-loop entry + `dis`; GraphSAGE: no self-loop + `den`).  The
     GCN family is built with the cache, the GraphSAGE one on first use."""
 
-    def __init__(self, ds: PackedDataset, chunk: int = 2048):
+    def __init__(self, ds, chunk: int = 2048):
+        """ds: a PackedDataset or RaggedPackedDataset on the device."""
         n = int(ds.x.shape[1])
         if not (0 < n <= MAX_ROWS):
             raise ValueError(f"structure cache: a graph must fit one LDS tile (<= {MAX_ROWS} nodes), got {n}")
@@ -84,7 +85,7 @@ class SubjectStructureCache:
         base = {"dst": 0, "src": 0}
         for lo in range(0, S, self._chunk):
             ids = torch.arange(lo, min(S, lo + self._chunk), device=dev)
-            b = assemble_batch(ds, ids)
+            b = assemble_batch(ds, ids, torch.arange(lo, min(S, lo + self._chunk)))
             s = b.structure()
             if not s.block_diagonal:
                 raise ValueError("structure cache: a subject has edges outside its graph")
@@ -217,6 +218,7 @@ class ResidentBatch(ConnectomeBatch):
         captured step walks an epoch's permutation without any per-step host copy."""
         self._cache, self._ids_src = cache, ids      # as handed in (host ids of a loader: no copy yet)
         self._ids_offset = ids_offset
+        self._host_ids = None                        # the same ids on the host, when the loader has them
         self._b = int(ids.numel())
         self._lazy = {}
         self._coo = None
@@ -298,7 +300,7 @@ class ResidentBatch(ConnectomeBatch):
             raise RuntimeError("a cursor-addressed ResidentBatch (captured epoch replay) has no fixed COO fields")
         if self._coo is None:
             from .resident import assemble_batch
-            full = assemble_batch(self._cache.dataset, self._ids)
+            full = assemble_batch(self._cache.dataset, self._ids, self._host_ids)
             self._coo = (full.edge_index, full.edge_weight, full.batch)
         return self._coo
 

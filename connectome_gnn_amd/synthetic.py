@@ -190,6 +190,92 @@ class PackedDataset:
                              torch.stack([torch.as_tensor(g.label, dtype=torch.long).reshape(()) for g in graphs]))
 
 
+@dataclass
+class RaggedPackedDataset:
+    """A same-atlas dataset whose subjects keep different numbers of edges (thresholded structural or
+    functional matrices): S subjects of n nodes each, subject i's directed edges the run
+    [edge_ptr[i], edge_ptr[i+1]) of the flat edge arrays, in its own COO order.  Same interface as
+    ``PackedDataset``; ``resident.assemble_batch`` collates it on the device with one HIP launch
+    (csrc/collate.hip)."""
+    x: torch.Tensor             # [S, n, F]   f32
+    edge_local: torch.Tensor    # [2, E_tot]  i64, node ids local to the graph
+    edge_weight: torch.Tensor   # [E_tot]     f32
+    labels: torch.Tensor        # [S]         i64
+    edge_ptr: torch.Tensor      # [S+1]       i64, on the HOST: sizes a batch without a read-back
+    edge_ptr_dev: Optional[torch.Tensor] = None      # the same offsets next to the data (the collate reads them)
+
+    def __post_init__(self):
+        self.edge_ptr = self.edge_ptr.to("cpu", torch.long).contiguous()
+        if self.edge_ptr_dev is None or self.edge_ptr_dev.device != self.x.device:
+            self.edge_ptr_dev = self.edge_ptr.to(self.x.device)
+
+    @property
+    def num_subjects(self) -> int:
+        return int(self.x.shape[0])
+
+    def to(self, device) -> "RaggedPackedDataset":
+        return RaggedPackedDataset(self.x.to(device), self.edge_local.to(device), self.edge_weight.to(device),
+                                   self.labels.to(device), self.edge_ptr, self.edge_ptr_dev.to(device))
+
+    def graph(self, i: int) -> ConnectomeGraph:
+        lo, hi = int(self.edge_ptr[i]), int(self.edge_ptr[i + 1])
+        return ConnectomeGraph(self.x[i], self.edge_local[:, lo:hi], self.edge_weight[lo:hi], self.labels[i],
+                               f"sub-{i:04d}")
+
+    def relabel_by_degree(self) -> "RaggedPackedDataset":
+        """``PackedDataset.relabel_by_degree`` on the flat layout (flat node id = subject * n + local):
+        every subject's nodes renumbered by decreasing degree (in + out, ties in the old order)."""
+        S, n, f = self.x.shape
+        dev = self.x.device
+        counts = (self.edge_ptr[1:] - self.edge_ptr[:-1]).to(dev)
+        base = torch.repeat_interleave(torch.arange(S, device=dev) * n, counts)        # [E_tot]
+        src, dst = self.edge_local[0] + base, self.edge_local[1] + base
+        one = torch.ones_like(src)
+        deg = torch.zeros(S * n, dtype=torch.long, device=dev).scatter_add_(0, dst, one).scatter_add_(0, src, one)
+        perm = torch.argsort(deg.view(S, n), dim=1, descending=True, stable=True)      # new id -> old id
+        inv = torch.empty_like(perm).scatter_(1, perm, torch.arange(n, device=dev).expand(S, n)).view(-1)
+        x = torch.gather(self.x, 1, perm[..., None].expand(S, n, f))
+        e = torch.stack([inv[src], inv[dst]])
+        return RaggedPackedDataset(x.contiguous(), e.contiguous(), self.edge_weight, self.labels, self.edge_ptr,
+                                   self.edge_ptr_dev)
+
+    @staticmethod
+    def from_graphs(graphs) -> "RaggedPackedDataset":
+        """Pack a list of labelled ConnectomeGraphs of one node count and feature width; their edge counts
+        may differ (zero included)."""
+        if not graphs:
+            raise ValueError("empty dataset")
+        n, f = graphs[0].num_nodes, graphs[0].num_features
+        for g in graphs:
+            if g.num_nodes != n or g.num_features != f:
+                raise ValueError("RaggedPackedDataset needs graphs of one node count and feature width")
+            if g.label is None:
+                raise ValueError("RaggedPackedDataset needs labelled graphs")
+        edge_ptr = torch.zeros(len(graphs) + 1, dtype=torch.long)
+        edge_ptr[1:] = torch.cumsum(torch.tensor([g.num_edges for g in graphs], dtype=torch.long), 0)
+        return RaggedPackedDataset(torch.stack([g.node_features for g in graphs]),
+                                   torch.cat([g.edge_index for g in graphs], dim=1).contiguous(),
+                                   torch.cat([g.edge_weight for g in graphs]),
+                                   torch.stack([torch.as_tensor(g.label, dtype=torch.long).reshape(()) for g in graphs]),
+                                   edge_ptr)
+
+
+def pack_graphs(graphs):
+    """``PackedDataset.from_graphs(graphs)`` when every graph has the same number of edges, else a
+    ``RaggedPackedDataset``."""
+    if graphs and any(g.num_edges != graphs[0].num_edges for g in graphs):
+        return RaggedPackedDataset.from_graphs(graphs)
+    return PackedDataset.from_graphs(graphs)
+
+
+def threshold_edges(graph: ConnectomeGraph, min_weight: float) -> ConnectomeGraph:
+    """The graph with only the edges whose weight is greater than ``min_weight``, in their order: the
+    absolute-threshold preprocessing that gives the subjects of one atlas different edge counts."""
+    keep = graph.edge_weight > min_weight
+    return ConnectomeGraph(graph.node_features, graph.edge_index[:, keep], graph.edge_weight[keep], graph.label,
+                           graph.subject_id)
+
+
 def _packed_arrays(args):
     seeds, num_regions, k, beta, trait_idx = args
     e = num_regions * (k // 2) * 2

@@ -13,13 +13,14 @@ different is how the host and the GPU are kept apart:
   * the default device is "cuda" (this package has no CPU path);
   * the UNCHANGED reference script -- a list of ``ConnectomeGraph`` behind a ``ConnectomeDataLoader`` and
     ``Trainer(model, torch.optim.Adam(...), device)`` (examples/demo.py:92-134) -- does not collate on the
-    host: on first sight of such a loader its dataset is packed once into HBM (``PackedDataset``), every
+    host: on first sight of such a loader its dataset is packed once into HBM (``synthetic.pack_graphs``), every
     epoch's permutation is drawn by the same global ``torch.randperm`` call the loader would make
     (graph.py:192-194, so seeded runs and golden G7 do not change), batches are assembled on the device
     bit-identically to ``collate_graphs``, and where the model's one-node encoder is served by the per-subject
     structure cache the step is captured once per batch size and replayed (``graph=None`` = "where capture
     succeeds"; a plain ``torch.optim.Adam`` that has not stepped yet is switched to ``capturable=True`` for
-    that).  Irregular datasets (graphs of different sizes) keep the host loader;
+    that).  The graphs' edge counts may differ (one HIP launch collates such a batch, csrc/collate.hip);
+    datasets whose graphs differ in their NODE count keep the host loader;
   * data-parallel use: ``grad_sync`` (see dist.GradSync) runs between backward and the step,
     weighted by this rank's graph count so that unequal shards (partial tails) still give the
     global-batch gradient; epoch tallies (loss, hits, graphs) are summed over ranks before they
@@ -104,7 +105,7 @@ class Trainer:
                  grad_sync: Optional[Callable[[], None]] = None, loss_fn: Optional[nn.Module] = None,
                  graph: Optional[bool] = None, graph_collectives: str = "split", max_graphs: int = 32,
                  resident: bool = True):
-        """``resident`` (default on): a list-backed ``ConnectomeDataLoader`` of equally sized graphs is packed
+        """``resident`` (default on): a list-backed ``ConnectomeDataLoader`` of graphs of one node count is packed
         into HBM on first sight and iterated on the device (module docstring); ``graph=None`` (default) then
         replays a captured step where the model's encoder allows it and falls back to eager launches where
         capture fails; ``graph=False`` never captures.
@@ -145,7 +146,7 @@ class Trainer:
     def _resident_loader(self, loader, training: bool):
         """The device-resident twin of a list-backed ``ConnectomeDataLoader`` (same batch size, shuffle flag,
         rank / world size; its permutation comes from the same global-RNG call), built once per loader; None
-        when `loader` is anything else, the device is not a GPU or the graphs are not all one size."""
+        when `loader` is anything else, the device is not a GPU or the graphs differ in their node count."""
         from .graph import ConnectomeDataLoader
         if not self.resident or type(loader) is not ConnectomeDataLoader:
             return None
@@ -173,16 +174,16 @@ class Trainer:
 
     def _pack(self, loader, data, dev):
         from .resident import ResidentDataLoader
-        from .synthetic import PackedDataset
+        from .synthetic import pack_graphs
         g0 = data[0]
-        n, e, f = g0.num_nodes, g0.num_edges, g0.num_features
+        n, f = g0.num_nodes, g0.num_features
         for g in data:
             lab = g.label
-            if g.num_nodes != n or g.num_edges != e or g.num_features != f or not torch.is_tensor(lab) \
+            if g.num_nodes != n or g.num_features != f or not torch.is_tensor(lab) \
                     or lab.dim() != 0 or lab.dtype != torch.long or g.node_features.dtype != torch.float32 \
                     or g.edge_weight.dtype != torch.float32 or g.edge_index.dtype != torch.long:
                 return None                  # irregular (or unlabelled) data: the host loader stays
-        packed = PackedDataset.from_graphs(list(data))
+        packed = pack_graphs(list(data))     # (edge counts may differ per subject: RaggedPackedDataset)
         # torch's cross-entropy raises on a target outside [0, C) (the reference's behaviour, train.py:49); the
         # one-launch loss kernel cannot raise and turns it into a NaN loss, so the check is made here, once,
         # on the host, where the labels still are

@@ -327,6 +327,32 @@ int cgnn_gather_rows(const cgnn_gather_jobs* jobs, const int64_t* ids, int32_t n
 int cgnn_epoch_advance(int64_t* cursor, int64_t step, const float* loss, float weight, float* tally,
                        void* stream);
 
+/* The COO of a batch from a device-resident dataset whose subjects keep different numbers of edges -- the
+ * on-device form of collate_graphs (graph.py:143-167), bit-identical to it.  The dataset holds subject i's
+ * edges as the run [edge_ptr[i], edge_ptr[i+1]) of edge_local (int64 [2, ds_edges], node ids local to the
+ * graph) and edge_weight_ds (float [ds_edges]); every subject has n nodes.  For the b subject ids:
+ *     eptr[g+1] - eptr[g]           = edge_ptr[ids[g]+1] - edge_ptr[ids[g]],  eptr[0] = 0   (int32 [b+1])
+ *     edge_index[r][eptr[g] + j]    = edge_local[r][edge_ptr[ids[g]] + j] + g * n           (r = 0, 1)
+ *     edge_weight[eptr[g] + j]      = edge_weight_ds[edge_ptr[ids[g]] + j]
+ * eptr is COMPUTED HERE, on the device (one workgroup scans the counts ahead of the copy, same stream): it is
+ * an output -- the form cgnn_csr_build_grouped takes -- not an input.  num_edges is the batch's edge count as
+ * the caller's host copy of edge_ptr gives it: it sizes the launch, is the row stride of edge_index
+ * ([2, num_edges]) and bounds every write (sums beyond it are cut off; a subject id outside [0, num_subjects)
+ * or a run outside [0, ds_edges] counts as empty).  The three outputs come with their byte counts; a short or
+ * NULL buffer, b < 0, n <= 0, b * n or num_edges >= 2^31 return CGNN_EINVAL before any launch.  b == 0 or
+ * num_edges == 0: CGNN_OK, nothing launched, nothing written (eptr of such a batch is all zeros).
+ * edge_index and edge_weight 16-byte aligned.  The copy walks chunks of CGNN_COLLATE_CHUNK edges of the
+ * batch's flat edge range with a grid stride over 4 * cgnn_fused_grid() workgroups, a thread moving
+ * CGNN_COLLATE_VEC edges with 16-byte accesses; eptr is searched in LDS for b <= CGNN_COLLATE_LDS_GRAPHS. */
+#define CGNN_COLLATE_VEC 4
+#define CGNN_COLLATE_CHUNK 1024
+#define CGNN_COLLATE_LDS_GRAPHS 4096
+int cgnn_collate_edges(const int64_t* edge_local, const float* edge_weight_ds, const int64_t* edge_ptr,
+                       int64_t num_subjects, int64_t ds_edges, const int64_t* ids, int32_t b, int32_t n,
+                       int64_t num_edges, int64_t* edge_index, int64_t edge_index_bytes,
+                       float* edge_weight, int64_t edge_weight_bytes, int32_t* eptr, int64_t eptr_bytes,
+                       void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
