@@ -196,6 +196,9 @@ PROTOTYPES = {
     "cgnn_gather_rows": (c_int, [ctypes.POINTER(CgnnGatherJobs), P, I32, P, P]),
     "cgnn_epoch_advance": (c_int, [P, I64, P, F32, P, P]),
     "cgnn_collate_edges": (c_int, [P, P, P, I64, I64, P, I32, I32, I64, P, I64, P, I64, P, I64, P]),
+    "cgnn_ingest_select": (c_int, [P, I64, I32, I64, P, I64, P]),
+    "cgnn_ingest_count": (c_int, [P, I64, I32, I32, I64, P, I64, P, I64, P, I64, P]),
+    "cgnn_ingest_fill": (c_int, [P, I64, I32, P, P, I64, P, I64, P, I64, P]),
     "cgnn_gcn_dis": (c_int, [P, P, I64, P, P]),
     "cgnn_fused_grid": (c_int, []),
     "cgnn_set_fused_grid": (c_int, [I32]),

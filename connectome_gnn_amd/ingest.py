@@ -1,0 +1,141 @@
+"""Resident datasets from connectivity matrices, built on the device.
+
+Real cohorts start as one dense ``n x n`` connectivity matrix per subject (structural FA or streamline
+counts, functional correlations); the reference README ("Extending to real HCP data") thresholds each to
+its strongest connections, turns what is left into a COO edge list and derives a strength feature, per
+subject in Python.  Here the cohort ``[S, n, n]`` sits in HBM and that step is three HIP launches
+(csrc/ingest.hip) whose result is a ``RaggedPackedDataset`` -- what ``ResidentDataLoader``,
+``SubjectStructureCache``, the ragged collate, captured steps and ``Trainer`` already take.
+
+Semantics, per subject with matrix ``A`` (fp32, any sign, not necessarily symmetric):
+
+* candidates are the ``m = n (n - 1)`` off-diagonal entries; a NaN candidate ranks as -inf; the diagonal is
+  never a candidate and never an edge;
+* the threshold ``t`` is exactly one of: ``keep=f`` (proportional: ``k = int(f * n * (n - 1) + 0.5)``),
+  ``num_edges=k`` -- for both ``t`` is the candidate of descending rank ``k``, 0-based (the (k+1)-th
+  largest), -inf when ``k >= m`` -- or ``min_weight=t`` (absolute: a float or a ``[S]`` tensor);
+* ``i -> j`` is an edge iff ``i != j``, ``A[i, j] > t`` and ``A[i, j] > 0`` (both strict, as in
+  ``synthetic.threshold_edges``; a NaN fails both): at most ``k`` edges, fewer when ties straddle the
+  threshold, and a symmetric matrix gives a symmetric edge set;
+* edges are in row-major order (``torch.nonzero`` of the mask), ``edge_weight = A[i, j]``;
+* node features: the caller's ``[S, n, F]``, or by default ``[S, n, 1]`` with
+  ``x[s, i, 0] = strength_i / (max_i strength_i + 1e-8)``, ``strength_i`` the sum over ``j`` of the kept
+  ``A[i, j]`` (``ConnectomeGraph.degree()``); zeros for a subject without edges.
+
+A density sweep is ``from_matrices`` called again on the same resident matrices; nothing is cached.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from .synthetic import RaggedPackedDataset
+
+_LIMIT = 2 ** 31
+
+
+def _check_matrices(matrices) -> tuple:
+    if not isinstance(matrices, torch.Tensor):
+        raise TypeError(f"matrices must be a torch.Tensor, got {type(matrices).__name__}")
+    if matrices.dtype != torch.float32:
+        raise TypeError(f"matrices must be float32, got {matrices.dtype}")
+    if matrices.dim() != 3 or matrices.shape[1] != matrices.shape[2] or matrices.shape[1] == 0:
+        raise ValueError(f"matrices must be [S, n, n] with n >= 1, got {tuple(matrices.shape)}")
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
+    if S * n >= _LIMIT:
+        raise ValueError(f"S * n = {S * n} >= 2^31: ingest the cohort in slices of subjects")
+    if n * n >= _LIMIT:
+        raise ValueError(f"n * n = {n * n} >= 2^31: matrices this large are not supported")
+    return S, n
+
+
+def _rank(n: int, keep, num_edges) -> int:
+    if (keep is None) == (num_edges is None):
+        raise ValueError("give exactly one of keep= and num_edges=")
+    if keep is not None:
+        keep = float(keep)
+        if not 0.0 <= keep <= 1.0:                    # (a NaN is refused here too)
+            raise ValueError(f"keep must lie in [0, 1], got {keep}")
+        return int(keep * n * (n - 1) + 0.5)
+    if isinstance(num_edges, bool) or not isinstance(num_edges, int):
+        raise TypeError(f"num_edges must be an int, got {type(num_edges).__name__}")
+    if num_edges < 0:
+        raise ValueError(f"num_edges must be >= 0, got {num_edges}")
+    return min(num_edges, _LIMIT)                     # anything >= n (n - 1) keeps every positive entry
+
+
+def _require_resident(matrices: torch.Tensor) -> None:
+    if not matrices.is_contiguous():
+        raise ValueError("matrices must be contiguous")
+    if not matrices.is_cuda:
+        raise RuntimeError(
+            f"matrices are on {matrices.device}: connectome_gnn_amd thresholds connectivity matrices on a "
+            "ROCm device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> torch.Tensor:
+    """Per subject, the off-diagonal entry of descending rank ``k`` (``[S]`` float32 on the matrices'
+    device): the threshold that ``from_matrices`` applies for the same ``keep`` / ``num_edges``."""
+    S, n = _check_matrices(matrices)
+    k = _rank(n, keep, num_edges)
+    _require_resident(matrices)
+    dev = matrices.device
+    thr = torch.empty(S, dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(_lib.load().cgnn_ingest_select(_lib.ptr(matrices), S, n, k, _lib.ptr(thr), _lib.nbytes(thr),
+                                                  _lib.stream_ptr(dev)), "cgnn_ingest_select")
+    return thr
+
+
+def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
+                  node_features=None) -> RaggedPackedDataset:
+    """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).
+
+    One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
+    the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
+    S, n = _check_matrices(matrices)
+    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
+        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
+    k = 0 if min_weight is not None else _rank(n, keep, num_edges)
+    if isinstance(min_weight, torch.Tensor):
+        if min_weight.shape != (S,) or not min_weight.is_floating_point():
+            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
+                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    elif min_weight is not None:
+        min_weight = float(min_weight)
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
+        raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
+    if node_features is not None:
+        if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
+                or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (S, n):
+            raise ValueError(f"node_features must be a float32 tensor [S, n, F] = [{S}, {n}, F]")
+        if node_features.device != matrices.device:
+            raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
+    _require_resident(matrices)
+    dev = matrices.device
+    lib = _lib.load()
+    if min_weight is None:
+        thr = torch.empty(S, dtype=torch.float32, device=dev)
+    elif isinstance(min_weight, torch.Tensor):
+        thr = min_weight.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        thr = torch.full((S,), min_weight, dtype=torch.float32, device=dev)
+    row_count = torch.empty(S * n, dtype=torch.int32, device=dev)
+    x = node_features if node_features is not None else torch.empty(S, n, 1, dtype=torch.float32, device=dev)
+    strength = None if node_features is not None else x
+    row_off = torch.zeros(S * n + 1, dtype=torch.long, device=dev)
+    with _lib.device_guard(dev):
+        sp = _lib.stream_ptr(dev)
+        _lib.check(lib.cgnn_ingest_count(_lib.ptr(matrices), S, n, int(min_weight is None), k, _lib.ptr(thr),
+                                         _lib.nbytes(thr), _lib.ptr(row_count), _lib.nbytes(row_count),
+                                         _lib.ptr(strength), _lib.nbytes(strength), sp), "cgnn_ingest_count")
+        torch.cumsum(row_count, 0, dtype=torch.long, out=row_off[1:])
+        edge_ptr_dev = row_off[::n].contiguous()          # [S + 1]: every subject's first row
+        edge_ptr = edge_ptr_dev.cpu()                     # the one read-back
+        E = int(edge_ptr[-1])
+        edge_local = torch.empty(2, E, dtype=torch.long, device=dev)
+        edge_weight = torch.empty(E, dtype=torch.float32, device=dev)
+        _lib.check(lib.cgnn_ingest_fill(_lib.ptr(matrices), S, n, _lib.ptr(thr), _lib.ptr(row_off), E,
+                                        _lib.ptr(edge_local), _lib.nbytes(edge_local), _lib.ptr(edge_weight),
+                                        _lib.nbytes(edge_weight), sp), "cgnn_ingest_fill")
+    return RaggedPackedDataset(x, edge_local, edge_weight, labels.to(dev), edge_ptr, edge_ptr_dev)

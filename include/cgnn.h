@@ -353,6 +353,45 @@ int cgnn_collate_edges(const int64_t* edge_local, const float* edge_weight_ds, c
                        float* edge_weight, int64_t edge_weight_bytes, int32_t* eptr, int64_t eptr_bytes,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A device-resident cohort of dense connectivity matrices -> the flat edge arrays above (DESIGN.md 4.3b;
+ * the step the reference README's "Extending to real HCP data" leaves to a host loop).
+ * matrices: float [S, n, n], contiguous, any sign, not necessarily symmetric.  For subject s with matrix A:
+ *   candidates  the n(n-1) off-diagonal entries; a NaN candidate ranks as -inf
+ *   threshold   t_s = the candidate of descending rank k, 0-based (the (k+1)-th largest); -inf when
+ *               k >= n(n-1) or when the rank falls on a NaN -- or t_s is given (absolute thresholding)
+ *   edges       i -> j  iff  i != j, A[i,j] > t_s and A[i,j] > 0, compared as floats, both strict (a NaN
+ *               fails both): at most k edges, fewer when ties straddle the threshold
+ *   order       row-major (i ascending, then j ascending)
+ * Three calls, each enqueued on `stream`; every written buffer comes with its byte count; a NULL or short
+ * buffer, S < 0, n <= 0, k < 0, S * n >= 2^31 or n * n >= 2^31 return CGNN_EINVAL before any launch;
+ * S == 0 returns CGNN_OK with nothing launched.  Element offsets into `matrices` are 64-bit.
+ *
+ * cgnn_ingest_select: thr[s] = t_s (float [S]).  An exact radix select per subject on an order-preserving
+ *   uint32 image of the floats (three passes of 11/11/10 bits, histogram in LDS): no sort, no workspace.  One
+ *   workgroup owns a subject; 3 * cgnn_fused_grid() workgroups walk the subjects with a grid stride.
+ * cgnn_ingest_count: row_count[s * n + i] (int32 [S * n]) = edges leaving node i of subject s.  select != 0:
+ *   thr is an OUTPUT, selected as above for k by the same workgroup just before it counts (one pass over HBM
+ *   per subject); select == 0: thr is an INPUT (k must still be >= 0 and is not used).
+ *   strength (nullable, float [S * n] = the default node feature [S, n, 1]): strength_i / (max_i strength_i +
+ *   1e-8) with strength_i = the sum of the kept A[i, j] over j (ConnectomeGraph.degree()); zeros for a subject
+ *   without edges.
+ * cgnn_ingest_fill: row_off (int64 [S * n + 1]) = the exclusive running sum of row_count over all rows of all
+ *   subjects, num_edges = row_off[S * n] as the caller read it back: edge_local[0][p] = i, edge_local[1][p] = j
+ *   (int64 [2, num_edges]), edge_weight[p] = A[i,j] for the kept entries of row (s, i) at p = row_off[s*n + i]
+ *   onwards in column order, placed by ballot + lane prefix (a wave per row; no atomics: the same bits on
+ *   every run).  Positions outside [0, num_edges) are not written.  num_edges == 0: CGNN_OK, nothing launched;
+ *   num_edges > S n (n-1): CGNN_EINVAL.  The edge pointer of a RaggedPackedDataset is row_off[0 :: n].
+ * ------------------------------------------------------------------------------------- */
+int cgnn_ingest_select(const float* matrices, int64_t S, int32_t n, int64_t k, float* thr, int64_t thr_bytes,
+                       void* stream);
+int cgnn_ingest_count(const float* matrices, int64_t S, int32_t n, int32_t select, int64_t k, float* thr,
+                      int64_t thr_bytes, int32_t* row_count, int64_t row_count_bytes, float* strength,
+                      int64_t strength_bytes, void* stream);
+int cgnn_ingest_fill(const float* matrices, int64_t S, int32_t n, const float* thr, const int64_t* row_off,
+                     int64_t num_edges, int64_t* edge_local, int64_t edge_local_bytes, float* edge_weight,
+                     int64_t edge_weight_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
