@@ -1,4 +1,4 @@
-"""Resident datasets from connectivity matrices, built on the device.
+"""Resident datasets from connectivity matrices or ROI time series, built on the device.
 
 Real cohorts start as one dense ``n x n`` connectivity matrix per subject (structural FA or streamline
 counts, functional correlations); the reference README ("Extending to real HCP data") thresholds each to
@@ -23,6 +23,27 @@ Semantics, per subject with matrix ``A`` (fp32, any sign, not necessarily symmet
   ``A[i, j]`` (``ConnectomeGraph.degree()``); zeros for a subject without edges.
 
 A density sweep is ``from_matrices`` called again on the same resident matrices; nothing is cached.
+
+Functional cohorts start one step earlier, as one ROI time series per subject:
+``correlation_matrices`` / ``from_timeseries`` take ``timeseries`` -- float32, contiguous, ``[S, T, n]``, one row
+per frame, on a ROCm device -- and build the Pearson correlation matrices there (csrc/timeseries.hip).
+
+* A *unit* is one (subject, window) pair.  Without ``window`` there is one unit per subject over all ``T``
+  frames.  With ``window=L`` (``2 <= L <= T``) and ``stride=st`` (``>= 1``, default ``L``) subject ``s`` has
+  ``W = (T - L) // st + 1`` units; unit ``u = s * W + w`` covers frames ``[w * st, w * st + L)``.
+* Per unit, with its ``L`` frames ``x[t, i]``: ``m_i`` is the mean of column ``i`` and
+  ``q_i = sum_t (x[t, i] - m_i)^2``, both accumulated in fp64 from the fp32 inputs as centred sums (blocked Welford,
+  never ``E[x^2] - E[x]^2``); ``r[i, j] = sum_t z[t, i] z[t, j]`` with ``z[t, i] = (x[t, i] - m_i) / sqrt(q_i)``,
+  operands centred and scaled in fp32, products exact to fp32 rounding on the fp32 matrix pipe, accumulation in
+  fp32 over ``t`` ascending.  No atomics: two calls give the same bits.
+* ``r[i, j]`` and ``r[j, i]`` are the same bits; off-diagonals are clamped to ``[-1, 1]``; ``r[i, i]`` is
+  exactly ``1.0``.  A column with ``q_i == 0`` (a constant or masked ROI) has ``1 / sqrt(q_i)`` taken as 0: its
+  whole row and column, diagonal included, are exactly ``0.0``, not NaN.
+* ``absolute=True`` stores ``|r|``: anticorrelations are then kept by the strict ``> 0`` test of
+  ``from_matrices``; by default they are dropped there, as any non-positive entry is.
+* Non-finite inputs are not checked; they propagate as IEEE says.
+
+A window sweep is ``from_timeseries`` called again on the same resident time series.
 """
 from __future__ import annotations
 
@@ -71,6 +92,95 @@ def _require_resident(matrices: torch.Tensor) -> None:
         raise RuntimeError(
             f"matrices are on {matrices.device}: connectome_gnn_amd thresholds connectivity matrices on a "
             "ROCm device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+def _check_timeseries(timeseries, window, stride) -> tuple:
+    """(S, T, n, L, st, W) of a valid request: L frames per unit, st frames between units, W units a subject."""
+    if not isinstance(timeseries, torch.Tensor):
+        raise TypeError(f"timeseries must be a torch.Tensor, got {type(timeseries).__name__}")
+    if timeseries.dtype != torch.float32:
+        raise TypeError(f"timeseries must be float32, got {timeseries.dtype}")
+    for name, v in (("window", window), ("stride", stride)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise TypeError(f"{name} must be an int or None, got {type(v).__name__}")
+    if timeseries.dim() != 3 or timeseries.shape[2] == 0:
+        raise ValueError(f"timeseries must be [S, T, n] with n >= 1, got {tuple(timeseries.shape)}")
+    S, T, n = (int(v) for v in timeseries.shape)
+    if T < 2:
+        raise ValueError(f"a correlation needs T >= 2 frames, got T = {T}")
+    if window is None:
+        if stride is not None:
+            raise ValueError("stride= is the step between windows: give window= with it")
+        L, st = T, T
+    else:
+        if not 2 <= window <= T:
+            raise ValueError(f"window must lie in [2, T] = [2, {T}], got {window}")
+        st = window if stride is None else stride
+        if st < 1:
+            raise ValueError(f"stride must be >= 1, got {st}")
+        L = window
+    W = (T - L) // st + 1
+    if S * W * n >= _LIMIT:
+        raise ValueError(f"units * n = {S * W * n} >= 2^31: ingest the cohort in slices of subjects")
+    if n * n >= _LIMIT:
+        raise ValueError(f"n * n = {n * n} >= 2^31: matrices this large are not supported")
+    return S, T, n, L, st, W
+
+
+def _require_resident_timeseries(timeseries: torch.Tensor) -> None:
+    if not timeseries.is_contiguous():
+        raise ValueError("timeseries must be contiguous")
+    if not timeseries.is_cuda:
+        raise RuntimeError(
+            f"timeseries are on {timeseries.device}: connectome_gnn_amd correlates ROI time series on a ROCm "
+            "device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool) -> torch.Tensor:
+    dev = timeseries.device
+    U = S * W
+    out = torch.empty(U, n, n, dtype=torch.float32, device=dev)
+    stats = torch.empty(U, n, 2, dtype=torch.float32, device=dev)      # (mean, 1 / sqrt(q)) per unit and ROI
+    with _lib.device_guard(dev):
+        _lib.check(_lib.load().cgnn_ingest_corr(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
+                                                st if windowed else 0, int(bool(absolute)), _lib.ptr(stats),
+                                                _lib.nbytes(stats), _lib.ptr(out), _lib.nbytes(out),
+                                                _lib.stream_ptr(dev)), "cgnn_ingest_corr")
+    return out
+
+
+def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False) -> torch.Tensor:
+    """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
+    (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics."""
+    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    _require_resident_timeseries(timeseries)
+    return _correlate(timeseries, S, T, n, L, W, st, window is not None, absolute)
+
+
+def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
+                    window=None, stride=None, absolute=False, node_features=None) -> RaggedPackedDataset:
+    """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
+    unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
+    if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``.  The one read-back is ``from_matrices``'s."""
+    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    U = S * W
+    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
+        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
+    if min_weight is None:
+        _rank(n, keep, num_edges)
+    elif isinstance(min_weight, torch.Tensor) and (min_weight.shape != (U,) or not min_weight.is_floating_point()):
+        raise ValueError(f"a min_weight tensor must be floating point [U] = [{U}], got "
+                         f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
+        raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
+    if node_features is not None:
+        if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
+                or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (U, n):
+            raise ValueError(f"node_features must be a float32 tensor [U, n, F] = [{U}, {n}, F]")
+    _require_resident_timeseries(timeseries)
+    matrices = _correlate(timeseries, S, T, n, L, W, st, window is not None, absolute)
+    return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
+                         num_edges=num_edges, min_weight=min_weight, node_features=node_features)
 
 
 def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> torch.Tensor:

@@ -392,6 +392,32 @@ int cgnn_ingest_fill(const float* matrices, int64_t S, int32_t n, const float* t
                      int64_t num_edges, int64_t* edge_local, int64_t edge_local_bytes, float* edge_weight,
                      int64_t edge_weight_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A device-resident cohort of ROI time series -> Pearson correlation matrices, the input of the three calls
+ * above.  ts: float [S, T, n], contiguous, one row per frame.
+ *   units    without a window (window == 0) one unit per subject over all T frames; with window = L in [2, T]
+ *            and stride >= 1, W = (T - L) / stride + 1 units per subject, unit u = s * W + w covering frames
+ *            [w * stride, w * stride + L).  U = S * W.
+ *   per unit m_i = the mean of column i and q_i = sum_t (x[t,i] - m_i)^2, both accumulated in fp64 as centred
+ *            sums (blocks of 8 frames centred in registers and merged pairwise: one read, no E[x^2] - E[x]^2);
+ *            r[i,j] = sum_t z[t,i] z[t,j], z[t,i] = (x[t,i] - m_i) / sqrt(q_i), operands centred and scaled in
+ *            fp32, products on the fp32 matrix pipe, fp32 accumulation over t ascending.  No atomics: the same
+ *            bits on every run and for every grid.
+ *   output   out: float [U, n, n].  r[i,j] and r[j,i] are the same bits (one is the mirror store of the other);
+ *            off-diagonals are clamped to [-1, 1]; r[i,i] is exactly 1.  A column with q_i == 0 has 1/sqrt(q_i)
+ *            taken as 0: its row and column, diagonal included, are exactly 0.  absolute != 0 stores |r|.
+ *            Non-finite inputs are not checked and propagate.
+ *   stats    workspace, float [U, n, 2] = (m_i, 1/sqrt(q_i)) per unit and column, written by the first of the
+ *            two launches and read by the second (a persistent grid of 2 * cgnn_fused_grid() workgroups over
+ *            the (unit, 96 x 96 tile pair bi <= bj) items).
+ * A NULL or short buffer, S < 0, n <= 0, T < 2, window outside {0} u [2, T], stride < 1 with a window,
+ * U * n >= 2^31 or n * n >= 2^31 return CGNN_EINVAL before any launch; S == 0 returns CGNN_OK with nothing
+ * launched and nothing written.  Element offsets into ts and out are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+int cgnn_ingest_corr(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                     int32_t absolute, float* stats, int64_t stats_bytes, float* out, int64_t out_bytes,
+                     void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
