@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "ingest_rows.h"
 
 extern "C" int cgnn_fused_grid(void);
 
@@ -36,8 +37,8 @@ constexpr int kPerThread = kBins / kThreads;  // bins a thread scans
 constexpr int kFillThreads = 256;             // k_ingest_fill: 4 waves, a row each
 static_assert(kPerThread * kThreads == kBins, "every bin has one owner");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4_e __attribute__((aligned(4)));      // 16 bytes at element alignment
+typedef cgnn_f32x4 f32x4;
+typedef cgnn_f32x4_e f32x4_e;                           // 16 bytes at element alignment
 
 // floats -> uint32 keys of the same order; every NaN is the smallest key
 __device__ __forceinline__ uint32_t key_of(float v) {
@@ -49,17 +50,11 @@ __device__ __forceinline__ float value_of(uint32_t key) {
   if (key == 0u) return -INFINITY;            // the rank fell on a NaN
   return __uint_as_float((key >> 31) ? (key ^ 0x80000000u) : ~key);
 }
-// THE edge predicate (diagonal aside), the same expression in count and fill
-__device__ __forceinline__ bool kept(float v, float t) { return v > t && v > 0.0f; }
-
-// 4 consecutive entries of a row from column j0 on; columns >= n read as -inf (never kept)
+// THE edge predicate (diagonal aside) and the row reads, the same expressions in count, fill and measures.hip
+// (ingest_rows.h)
+__device__ __forceinline__ bool kept(float v, float t) { return cgnn_kept(v, t); }
 __device__ __forceinline__ f32x4 load_row4(const float* __restrict__ row, int j0, int n) {
-  if (j0 + 4 <= n) return *reinterpret_cast<const f32x4_e*>(row + j0);
-  f32x4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  if (j0 < n) v[0] = row[j0];
-  if (j0 + 1 < n) v[1] = row[j0 + 1];
-  if (j0 + 2 < n) v[2] = row[j0 + 2];
-  return v;
+  return cgnn_load_row4(row, j0, n);
 }
 
 struct SelectShared {
@@ -176,21 +171,9 @@ __global__ __launch_bounds__(kThreads) void k_ingest(const float* __restrict__ m
     float wmax = 0.0f;
     for (int i = wave; i < n; i += kWaves) {
       const float* __restrict__ row = A + (int64_t)i * n;
-      int cnt = 0;
-      float sum = 0.0f;
-      for (int j0 = 4 * lane; j0 < n; j0 += 256) {
-        const f32x4 v = load_row4(row, j0, n);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (j0 + q != i && kept(v[q], thr_s)) {
-            ++cnt;
-            sum += v[q];
-          }
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-      sum = cgnn_wave_sum(sum);
+      int cnt;
+      float sum, unused;
+      cgnn_row_kept<false>(row, i, n, thr_s, lane, cnt, sum, unused);
       if (lane == 0) {
         row_count[s * n + i] = cnt;
         if (x) x[s * n + i] = sum;
@@ -204,8 +187,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(const float* __restrict__ m
       float mx = sh.wave_max[0];
 #pragma unroll
       for (int w = 1; w < kWaves; ++w) mx = fmaxf(mx, sh.wave_max[w]);
-      const float den = mx + 1e-8f;
-      for (int i = t; i < n; i += kThreads) x[s * n + i] = x[s * n + i] / den;
+      for (int i = t; i < n; i += kThreads) x[s * n + i] = cgnn_strength_feature(x[s * n + i], mx);
       __syncthreads();
     }
   }

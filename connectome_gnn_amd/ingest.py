@@ -24,6 +24,28 @@ Semantics, per subject with matrix ``A`` (fp32, any sign, not necessarily symmet
 
 A density sweep is ``from_matrices`` called again on the same resident matrices; nothing is cached.
 
+Graph-theoretic node features: ``node_measures(matrices, keep=..., measures=MEASURES)`` gives
+``[S, n, len(measures)]`` at the same thresholds, and ``from_matrices(..., measures=...)`` /
+``from_timeseries(..., measures=...)`` serve it as the dataset's ``x`` (``True`` stands for ``MEASURES``), with the
+thresholds selected once.  Per subject, on the edge test above (``e_ij``): ``a_ij = A_ij`` and ``b_ij = 1`` where
+``e_ij``, else 0; ``k_i = sum_j b_ij``; ``s_i = sum_j a_ij``; ``wmax = max a_ij``; ``u_ij = cbrt(a_ij / wmax)`` where
+``e_ij``, else 0; and for a value map ``v``, ``T_i(v) = sum_{j,k} v_ki v_kj v_ij``.
+
+* ``strength``: ``s_i / (max_i s_i + 1e-8)``, the same bits as the default feature;
+* ``degree``: ``k_i / (n - 1)``, and 0 for ``n == 1``;
+* ``mean_weight``: ``s_i / (k_i + 1e-8)``;
+* ``clustering``: ``T_i(b) / (k_i (k_i - 1))`` if ``k_i >= 2``, else 0;
+* ``weighted_clustering``: ``T_i(u) / (k_i (k_i - 1))`` if ``k_i >= 2``, else 0 -- Onnela's geometric-mean form on
+  weights scaled by the subject's maximum.
+
+For a symmetric kept set ``T_i(v) = diag(V^3)_i`` and the two clustering measures are ``networkx.clustering(G)`` and
+``networkx.clustering(G, weight="weight")``.  For an asymmetric matrix the formula is the definition: nothing is
+symmetrised or checked, and the value is not bounded by 1.  A subject without edges gives zeros; NaN entries are never
+edges; a kept ``+inf`` propagates as IEEE says through the weight-valued measures, while ``degree`` and ``clustering``
+do not see weights and stay exact (``T_i(b)`` is an integer below ``2^24`` on the exact fp32 matrix pipe).  The
+triangle sums are two dense products per subject on the device (csrc/measures.hip); nothing cohort-sized exists
+besides the output.  No atomics: two calls give the same bits, and so do two grids.
+
 Functional cohorts start one step earlier, as one ROI time series per subject:
 ``correlation_matrices`` / ``from_timeseries`` take ``timeseries`` -- float32, contiguous, ``[S, T, n]``, one row
 per frame, on a ROCm device -- and build the Pearson correlation matrices there (csrc/timeseries.hip).
@@ -47,12 +69,15 @@ A window sweep is ``from_timeseries`` called again on the same resident time ser
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
 from .synthetic import RaggedPackedDataset
 
 _LIMIT = 2 ** 31
+MEASURES = ("strength", "degree", "mean_weight", "clustering", "weighted_clustering")   # ids: include/cgnn.h
 
 
 def _check_matrices(matrices) -> tuple:
@@ -158,12 +183,15 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                    window=None, stride=None, absolute=False, node_features=None) -> RaggedPackedDataset:
+                    window=None, stride=None, absolute=False, node_features=None,
+                    measures=None) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
-    if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``.  The one read-back is ``from_matrices``'s."""
+    if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s.  The one
+    read-back is ``from_matrices``'s."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
+    _check_measures_argument(measures, node_features)
     if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
         raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
     if min_weight is None:
@@ -180,7 +208,82 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     _require_resident_timeseries(timeseries)
     matrices = _correlate(timeseries, S, T, n, L, W, st, window is not None, absolute)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
-                         num_edges=num_edges, min_weight=min_weight, node_features=node_features)
+                         num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
+
+
+def _measure_ids(measures) -> list:
+    """The ids (positions in MEASURES) of a valid request: a non-empty tuple of distinct names."""
+    if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
+        raise TypeError(f"measures must be a tuple of names from {MEASURES}, got {measures!r}")
+    if len(measures) == 0:
+        raise ValueError(f"measures is empty: name at least one of {MEASURES}")
+    ids = []
+    for name in measures:
+        if name not in MEASURES:
+            raise ValueError(f"unknown measure {name!r}: the measures are {MEASURES}")
+        if MEASURES.index(name) in ids:
+            raise ValueError(f"measure {name!r} is named twice")
+        ids.append(MEASURES.index(name))
+    return ids
+
+
+def _check_measures_argument(measures, node_features):
+    """The ids of from_matrices's measures= (None: not asked for; True: all of MEASURES)."""
+    if measures is None:
+        return None
+    if node_features is not None:
+        raise ValueError("give either measures= or node_features=, not both")
+    return _measure_ids(MEASURES if measures is True else measures)
+
+
+def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
+    dev = matrices.device
+    lib = _lib.load()
+    F = len(ids)
+    arr = (ctypes.c_int32 * F)(*ids)
+    x = torch.empty(S, n, F, dtype=torch.float32, device=dev)
+    if S == 0:
+        return x
+    need = lib.cgnn_ingest_measures_workspace_bytes(S, n, arr, F)
+    if need < 0:
+        raise _lib.CgnnError(f"cgnn_ingest_measures_workspace_bytes({S}, {n}) refused its arguments")
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(lib.cgnn_ingest_measures(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, F, _lib.ptr(work),
+                                            _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x), _lib.stream_ptr(dev)),
+                   "cgnn_ingest_measures")
+    return x
+
+
+def _threshold_tensor(min_weight, S: int, dev) -> torch.Tensor:
+    if isinstance(min_weight, torch.Tensor):
+        return min_weight.to(device=dev, dtype=torch.float32).contiguous()
+    return torch.full((S,), min_weight, dtype=torch.float32, device=dev)
+
+
+def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
+                  measures=MEASURES) -> torch.Tensor:
+    """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
+    ``matrices.device``, one column per name in ``measures`` (module docstring).  The thresholds are those
+    ``from_matrices`` applies for the same ``keep`` / ``num_edges`` / ``min_weight``.  No read-back."""
+    S, n = _check_matrices(matrices)
+    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
+        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
+    if min_weight is None:
+        _rank(n, keep, num_edges)
+    elif isinstance(min_weight, torch.Tensor):
+        if min_weight.shape != (S,) or not min_weight.is_floating_point():
+            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
+                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    else:
+        min_weight = float(min_weight)
+    ids = _measure_ids(measures)
+    _require_resident(matrices)
+    if min_weight is None:
+        thr = select_thresholds(matrices, keep=keep, num_edges=num_edges)
+    else:
+        thr = _threshold_tensor(min_weight, S, matrices.device)
+    return _measures(matrices, S, n, thr, ids)
 
 
 def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> torch.Tensor:
@@ -198,8 +301,10 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  node_features=None) -> RaggedPackedDataset:
-    """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).
+                  node_features=None, measures=None) -> RaggedPackedDataset:
+    """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
+    ``measures`` (a tuple of names from ``MEASURES``, or ``True`` for all of them) ``x`` is ``node_measures`` at the
+    thresholds of this call, which are selected once.
 
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
@@ -221,18 +326,19 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
             raise ValueError(f"node_features must be a float32 tensor [S, n, F] = [{S}, {n}, F]")
         if node_features.device != matrices.device:
             raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
+    ids = _check_measures_argument(measures, node_features)
     _require_resident(matrices)
     dev = matrices.device
     lib = _lib.load()
     if min_weight is None:
         thr = torch.empty(S, dtype=torch.float32, device=dev)
-    elif isinstance(min_weight, torch.Tensor):
-        thr = min_weight.to(device=dev, dtype=torch.float32).contiguous()
     else:
-        thr = torch.full((S,), min_weight, dtype=torch.float32, device=dev)
+        thr = _threshold_tensor(min_weight, S, dev)
     row_count = torch.empty(S * n, dtype=torch.int32, device=dev)
-    x = node_features if node_features is not None else torch.empty(S, n, 1, dtype=torch.float32, device=dev)
-    strength = None if node_features is not None else x
+    strength = None                                   # the default feature, unless x comes from elsewhere
+    if node_features is None and ids is None:
+        strength = torch.empty(S, n, 1, dtype=torch.float32, device=dev)
+    x = node_features if node_features is not None else strength
     row_off = torch.zeros(S * n + 1, dtype=torch.long, device=dev)
     with _lib.device_guard(dev):
         sp = _lib.stream_ptr(dev)
@@ -248,4 +354,6 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
         _lib.check(lib.cgnn_ingest_fill(_lib.ptr(matrices), S, n, _lib.ptr(thr), _lib.ptr(row_off), E,
                                         _lib.ptr(edge_local), _lib.nbytes(edge_local), _lib.ptr(edge_weight),
                                         _lib.nbytes(edge_weight), sp), "cgnn_ingest_fill")
+    if ids is not None:
+        x = _measures(matrices, S, n, thr, ids)       # at the thresholds cgnn_ingest_count selected
     return RaggedPackedDataset(x, edge_local, edge_weight, labels.to(dev), edge_ptr, edge_ptr_dev)

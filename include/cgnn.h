@@ -418,6 +418,50 @@ int cgnn_ingest_corr(const float* ts, int64_t S, int32_t T, int32_t n, int32_t w
                      int32_t absolute, float* stats, int64_t stats_bytes, float* out, int64_t out_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Graph-theoretic node features of the thresholded cohort.  matrices: float [S, n, n] as above;
+ * thr: float [S], the thresholds cgnn_ingest_select / cgnn_ingest_count left or the caller's.  Per subject with
+ * matrix A and threshold t:
+ *   e_ij    iff i != j, A_ij > t and A_ij > 0 (the edge test above; a NaN is never an edge)
+ *   a_ij = A_ij, b_ij = 1 where e_ij, else 0;  k_i = sum_j b_ij;  s_i = sum_j a_ij;  wmax = max a_ij;
+ *   u_ij = cbrt(a_ij / wmax) where e_ij, else 0 (evaluated in fp32 as cbrt(a_ij) * (1 / cbrt(wmax)));
+ *   for a value map v:  T_i(v) = sum_{j,k} v_ki v_kj v_ij
+ *   CGNN_MEASURE_STRENGTH             s_i / (max_i s_i + 1e-8): the bits of cgnn_ingest_count's strength
+ *   CGNN_MEASURE_DEGREE               k_i / (n - 1); 0 for n == 1
+ *   CGNN_MEASURE_MEAN_WEIGHT          s_i / (k_i + 1e-8)
+ *   CGNN_MEASURE_CLUSTERING           T_i(b) / (k_i (k_i - 1)) if k_i >= 2, else 0
+ *   CGNN_MEASURE_WEIGHTED_CLUSTERING  T_i(u) / (k_i (k_i - 1)) if k_i >= 2, else 0 (Onnela's geometric-mean form
+ *                                     on weights scaled by the subject's maximum)
+ * For a symmetric kept set T_i(v) = diag(V^3)_i and the two clustering measures are the local clustering
+ * coefficients of the graph; for an asymmetric matrix the formula is the definition (nothing is symmetrised, the
+ * value is not bounded by 1).  A subject without edges gives zeros.  A kept +inf propagates as IEEE says through the
+ * weight-valued measures; degree and clustering do not see weights: T_i(b) is an exact integer below 2^24.
+ *   measures   HOST array of num_measures distinct ids, 1 <= num_measures <= CGNN_NUM_MEASURES: the columns of x
+ *   x          float [S, n, num_measures]
+ *   workspace  cgnn_ingest_measures_workspace_bytes(S, n, measures, num_measures) bytes, 16-byte aligned: k_i, s_i,
+ *              (max_i s_i, wmax) and, per clustering measure asked for, the partial sums float [S, nt, nt * 96],
+ *              nt = ceil(n / 96)
+ * Launches on `stream`: a row pass (k_i, s_i, wmax; the row summation of cgnn_ingest_count); per clustering measure
+ * asked for one product kernel -- a persistent grid of 2 * cgnn_fused_grid() workgroups over the (subject, 96 x 96
+ * tile pair bi <= bj) items of V^T V, K-steps of 32 matrix rows on the fp32 matrix pipe, the edge test and the
+ * value map applied as the panels are staged; the item (min(blk(i), b), max(blk(i), b)) writes partial [s][b][i],
+ * exactly once -- and a finish that sums each node's nt partials in ascending b.  No atomics: the same bits on every
+ * run and for every grid.  A NULL, misaligned or short buffer, S < 0, n <= 0, S * n >= 2^31, n * n >= 2^31,
+ * num_measures outside [1, CGNN_NUM_MEASURES], an id outside [0, CGNN_NUM_MEASURES) or a repeated id return
+ * CGNN_EINVAL before any launch (the byte count: a negative value); S == 0 returns CGNN_OK with nothing launched.
+ * Element offsets into `matrices` are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_MEASURE_STRENGTH 0
+#define CGNN_MEASURE_DEGREE 1
+#define CGNN_MEASURE_MEAN_WEIGHT 2
+#define CGNN_MEASURE_CLUSTERING 3
+#define CGNN_MEASURE_WEIGHTED_CLUSTERING 4
+#define CGNN_NUM_MEASURES 5
+int64_t cgnn_ingest_measures_workspace_bytes(int64_t S, int32_t n, const int32_t* measures, int32_t num_measures);
+int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n, const float* thr, const int32_t* measures,
+                         int32_t num_measures, void* workspace, int64_t workspace_bytes, float* x, int64_t x_bytes,
+                         void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
