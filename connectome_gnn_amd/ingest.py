@@ -46,6 +46,34 @@ do not see weights and stay exact (``T_i(b)`` is an integer below ``2^24`` on th
 triangle sums are two dense products per subject on the device (csrc/measures.hip); nothing cohort-sized exists
 besides the output.  No atomics: two calls give the same bits, and so do two grids.
 
+Shortest-path node measures: the names of ``PATH_MEASURES`` are taken wherever ``measures=`` is, in any
+order and mix with those of ``MEASURES``; the columns follow the order given, the thresholds are selected once, and a
+request without a path name launches what it launched before and gives the same bits (``measures=True`` still stands
+for the five of ``MEASURES``).  Per subject, on the same edge test and with nothing symmetrised: ``d_ij`` is the number
+of edges on a shortest directed path ``i -> ... -> j`` along kept edges (the out-neighbours of a row, as in the BFS of
+``synthetic.small_world_stats``), infinite if there is none; ``R_i = {j != i : d_ij finite}``, ``r_i = |R_i|``;
+``N_i = {j : e_ij}``, ``k_i = |N_i|``; ``d^(i)`` are the distances inside the subgraph induced on ``N_i`` (only edges
+``e_jh`` with both ends in ``N_i``).
+
+* ``nodal_efficiency``: ``(1 / (n - 1)) sum_{j in R_i} 1 / d_ij``, and 0 for ``n == 1``;
+* ``closeness``: ``(r_i / (n - 1)) (r_i / sum_{j in R_i} d_ij)`` if ``r_i > 0``, else 0 (Wasserman-Faust);
+* ``eccentricity``: ``max_{j in R_i} d_ij / (n - 1)``, and 0 if ``r_i == 0`` or ``n == 1``;
+* ``local_efficiency``: ``(1 / (k_i (k_i - 1))) sum_{j != h in N_i} 1 / d^(i)_jh`` if ``k_i >= 2``, else 0 (unreachable
+  pairs add 0).
+
+For a symmetric kept set ``closeness`` is ``networkx.closeness_centrality(G, wf_improved=True)`` (for an asymmetric one
+that of ``G.reverse()``: networkx takes incoming distances), ``local_efficiency`` is
+``networkx.global_efficiency(G.subgraph(G[v]))``, and the means of ``nodal_efficiency`` and ``local_efficiency`` are
+``networkx.global_efficiency(G)`` and ``networkx.local_efficiency(G)``.  A subject without edges gives zeros; NaN entries
+are never edges; weights play no part beyond the edge test, so a kept ``+inf`` is an ordinary edge; all values lie in
+``[0, 1]``.  Level counts, ``r_i``, ``sum d`` and the eccentricity are exact integers on the device: ``eccentricity`` is
+the correctly rounded fp32 quotient, the other three are formed in fp64 from the integers and rounded to fp32 once.  One
+launch (csrc/paths.hip): a workgroup keeps a subject's adjacency as a bitset in LDS and runs a BFS per node, so
+``n <= PATH_MAX_NODES = 1024`` (a ``ValueError`` beyond); the cost of ``local_efficiency`` grows with the density
+(``~ n k^2`` row reads per subject against ``n^2`` for the other three together).  No atomics: two calls give the same
+bits, and so do two grids.  The fused GCN path takes ``in_channels <= 8``: a request of more than 8 columns trains on
+the wide path.
+
 Functional cohorts start one step earlier, as one ROI time series per subject:
 ``correlation_matrices`` / ``from_timeseries`` take ``timeseries`` -- float32, contiguous, ``[S, T, n]``, one row
 per frame, on a ROCm device -- and build the Pearson correlation matrices there (csrc/timeseries.hip).
@@ -78,6 +106,8 @@ from .synthetic import RaggedPackedDataset
 
 _LIMIT = 2 ** 31
 MEASURES = ("strength", "degree", "mean_weight", "clustering", "weighted_clustering")   # ids: include/cgnn.h
+PATH_MEASURES = ("nodal_efficiency", "closeness", "eccentricity", "local_efficiency")      # ids: include/cgnn.h
+PATH_MAX_NODES = 1024                                 # CGNN_PATH_MAX_NODES: the adjacency bitset must fit LDS
 
 
 def _check_matrices(matrices) -> tuple:
@@ -191,7 +221,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     read-back is ``from_matrices``'s."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
-    _check_measures_argument(measures, node_features)
+    _check_path_size(_check_measures_argument(measures, node_features), n)
     if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
         raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
     if min_weight is None:
@@ -212,23 +242,34 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
 
 
 def _measure_ids(measures) -> list:
-    """The ids (positions in MEASURES) of a valid request: a non-empty tuple of distinct names."""
+    """A valid request, a non-empty tuple of distinct names, as one ``(is_path, id)`` per column: the id is the
+    position in PATH_MEASURES or in MEASURES."""
     if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
-        raise TypeError(f"measures must be a tuple of names from {MEASURES}, got {measures!r}")
+        raise TypeError(f"measures must be a tuple of names from {MEASURES + PATH_MEASURES}, got {measures!r}")
     if len(measures) == 0:
-        raise ValueError(f"measures is empty: name at least one of {MEASURES}")
+        raise ValueError(f"measures is empty: name at least one of {MEASURES + PATH_MEASURES}")
     ids = []
     for name in measures:
-        if name not in MEASURES:
-            raise ValueError(f"unknown measure {name!r}: the measures are {MEASURES}")
-        if MEASURES.index(name) in ids:
+        if name in MEASURES:
+            entry = (False, MEASURES.index(name))
+        elif name in PATH_MEASURES:
+            entry = (True, PATH_MEASURES.index(name))
+        else:
+            raise ValueError(f"unknown measure {name!r}: the measures are {MEASURES + PATH_MEASURES}")
+        if entry in ids:
             raise ValueError(f"measure {name!r} is named twice")
-        ids.append(MEASURES.index(name))
+        ids.append(entry)
     return ids
 
 
+def _check_path_size(ids, n: int) -> None:
+    if ids is not None and n > PATH_MAX_NODES and any(is_path for is_path, _ in ids):
+        raise ValueError(f"the path measures {PATH_MEASURES} take n <= {PATH_MAX_NODES} nodes (the adjacency bitset "
+                         f"of a subject must fit LDS), got n = {n}")
+
+
 def _check_measures_argument(measures, node_features):
-    """The ids of from_matrices's measures= (None: not asked for; True: all of MEASURES)."""
+    """The request of from_matrices's measures= (None: not asked for; True: all of MEASURES)."""
     if measures is None:
         return None
     if node_features is not None:
@@ -236,7 +277,7 @@ def _check_measures_argument(measures, node_features):
     return _measure_ids(MEASURES if measures is True else measures)
 
 
-def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
+def _classic_measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
     dev = matrices.device
     lib = _lib.load()
     F = len(ids)
@@ -255,6 +296,39 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
     return x
 
 
+def _path_measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, cols: list,
+                   x: torch.Tensor) -> None:
+    """Path measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]``; the other columns stay as they are."""
+    if S == 0:
+        return
+    dev = matrices.device
+    lib = _lib.load()
+    num = len(ids)
+    arr, carr = (ctypes.c_int32 * num)(*ids), (ctypes.c_int32 * num)(*cols)
+    need = lib.cgnn_ingest_paths_workspace_bytes(S, n, arr, num)
+    if need < 0:
+        raise _lib.CgnnError(f"cgnn_ingest_paths_workspace_bytes({S}, {n}) refused its arguments")
+    work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with _lib.device_guard(dev):
+        _lib.check(lib.cgnn_ingest_paths(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num, carr, x.shape[2],
+                                         _lib.ptr(work), _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x),
+                                         _lib.stream_ptr(dev)), "cgnn_ingest_paths")
+
+
+def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
+    """``[S, n, len(ids)]``.  A request without path names is one cgnn_ingest_measures call, as before; otherwise the
+    path columns are written in place (cols / ldx) and the classic ones, if any, are that call's columns copied in."""
+    classic = [(c, i) for c, (is_path, i) in enumerate(ids) if not is_path]
+    paths = [(c, i) for c, (is_path, i) in enumerate(ids) if is_path]
+    if not paths:
+        return _classic_measures(matrices, S, n, thr, [i for _, i in classic])
+    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
+    if classic:
+        x[:, :, [c for c, _ in classic]] = _classic_measures(matrices, S, n, thr, [i for _, i in classic])
+    _path_measures(matrices, S, n, thr, [i for _, i in paths], [c for c, _ in paths], x)
+    return x
+
+
 def _threshold_tensor(min_weight, S: int, dev) -> torch.Tensor:
     if isinstance(min_weight, torch.Tensor):
         return min_weight.to(device=dev, dtype=torch.float32).contiguous()
@@ -264,8 +338,9 @@ def _threshold_tensor(min_weight, S: int, dev) -> torch.Tensor:
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   measures=MEASURES) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
-    ``matrices.device``, one column per name in ``measures`` (module docstring).  The thresholds are those
-    ``from_matrices`` applies for the same ``keep`` / ``num_edges`` / ``min_weight``.  No read-back."""
+    ``matrices.device``, one column per name in ``measures``: names from ``MEASURES`` and ``PATH_MEASURES`` in any
+    order and mix (module docstring).  The thresholds are those ``from_matrices`` applies for the same ``keep`` /
+    ``num_edges`` / ``min_weight``, selected once.  No read-back."""
     S, n = _check_matrices(matrices)
     if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
         raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
@@ -278,6 +353,7 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     else:
         min_weight = float(min_weight)
     ids = _measure_ids(measures)
+    _check_path_size(ids, n)
     _require_resident(matrices)
     if min_weight is None:
         thr = select_thresholds(matrices, keep=keep, num_edges=num_edges)
@@ -303,8 +379,8 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   node_features=None, measures=None) -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
-    ``measures`` (a tuple of names from ``MEASURES``, or ``True`` for all of them) ``x`` is ``node_measures`` at the
-    thresholds of this call, which are selected once.
+    ``measures`` (a tuple of names from ``MEASURES`` and ``PATH_MEASURES``, or ``True`` for all of ``MEASURES``) ``x``
+    is ``node_measures`` at the thresholds of this call, which are selected once.
 
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
@@ -327,6 +403,7 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
         if node_features.device != matrices.device:
             raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
     ids = _check_measures_argument(measures, node_features)
+    _check_path_size(ids, n)
     _require_resident(matrices)
     dev = matrices.device
     lib = _lib.load()

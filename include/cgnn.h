@@ -462,6 +462,52 @@ int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n, const floa
                          int32_t num_measures, void* workspace, int64_t workspace_bytes, float* x, int64_t x_bytes,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Shortest-path node measures of the thresholded cohort.  matrices and thr as for
+ * cgnn_ingest_measures; weights play no part beyond the edge test.  Per subject with matrix A and threshold t:
+ *   e_ij    iff i != j, A_ij > t and A_ij > 0 (the edge test above; a NaN is never an edge, a kept +inf is an
+ *           ordinary edge); nothing is symmetrised
+ *   d_ij    the number of edges on a shortest directed path i -> ... -> j along kept edges (the out-neighbours of
+ *           a row), infinite if there is none
+ *   R_i = { j != i : d_ij finite }, r_i = |R_i|;  N_i = { j : e_ij }, k_i = |N_i|
+ *   d^(i)   the distances inside the subgraph induced on N_i (only edges e_jh with both ends in N_i)
+ *   CGNN_PATH_NODAL_EFFICIENCY  (1 / (n - 1)) sum_{j in R_i} 1 / d_ij; 0 for n == 1
+ *   CGNN_PATH_CLOSENESS         (r_i / (n - 1)) (r_i / sum_{j in R_i} d_ij) if r_i > 0, else 0 (Wasserman-Faust)
+ *   CGNN_PATH_ECCENTRICITY      max_{j in R_i} d_ij / (n - 1); 0 if r_i == 0 or n == 1
+ *   CGNN_PATH_LOCAL_EFFICIENCY  (1 / (k_i (k_i - 1))) sum_{j != h in N_i} 1 / d^(i)_jh if k_i >= 2, else 0
+ *                               (unreachable pairs add 0)
+ * All values lie in [0, 1]; a subject without edges gives zeros.  Level counts, r_i, sum d (<= n (n - 1) / 2 < 2^24)
+ * and the eccentricity are exact integers: eccentricity is the correctly rounded fp32 quotient of two of them; the
+ * other three are formed in fp64 from the integers (sum_l count_l / l in ascending l) and rounded to fp32 once.
+ *   measures   HOST array of num_measures distinct ids, 1 <= num_measures <= CGNN_NUM_PATH_MEASURES
+ *   cols, ldx  HOST array of num_measures distinct columns in [0, ldx): measure m of node i of subject s is written
+ *              to x[(s * n + i) * ldx + cols[m]]; the other columns of x are not touched, so the path measures land
+ *              inside a wider feature tensor
+ *   x          float [S, n, ldx]
+ *   workspace  cgnn_ingest_paths_workspace_bytes(S, n, measures, num_measures) bytes, 16-byte aligned.  The one
+ *              kernel keeps its state in LDS and registers: the count is 0 today and workspace may then be NULL.
+ * One launch on `stream`: min(S, w * cgnn_fused_grid()) workgroups of 8 waves (w = what the LDS of a CU admits, at
+ * most 4), a workgroup per subject with a grid stride.  It builds the subject's out-neighbour bitset [n][ceil(n / 64)]
+ * x 64 bits in LDS (one wave-wide ballot of the edge test per word), runs a level-synchronous BFS from every source
+ * over word-wide OR / AND-NOT and popcounts (2^ceil(log2 ceil(n / 64)) lanes own a source), and for the local
+ * efficiency the same BFS confined to N_i from every j in N_i: ~ n k^2 ceil(n / 64) word reads per subject, which grows
+ * with the density.  No atomics, nothing depends on the grid: the same bits on every run and for every grid.
+ * n > CGNN_PATH_MAX_NODES (the bitset must fit LDS: 128 KB at 1024), a NULL, misaligned or short buffer, S < 0,
+ * n <= 0, S * n >= 2^31, num_measures outside [1, CGNN_NUM_PATH_MEASURES], an unknown or repeated id, ldx < 1, a
+ * column outside [0, ldx) or a repeated column return CGNN_EINVAL before any launch (the byte count: a negative
+ * value); S == 0 returns CGNN_OK with nothing launched.  Element offsets into `matrices` and `x` are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_PATH_NODAL_EFFICIENCY 0
+#define CGNN_PATH_CLOSENESS 1
+#define CGNN_PATH_ECCENTRICITY 2
+#define CGNN_PATH_LOCAL_EFFICIENCY 3
+#define CGNN_NUM_PATH_MEASURES 4
+#define CGNN_PATH_MAX_NODES 1024
+int64_t cgnn_ingest_paths_workspace_bytes(int64_t S, int32_t n, const int32_t* measures, int32_t num_measures);
+int cgnn_ingest_paths(const float* matrices, int64_t S, int32_t n, const float* thr, const int32_t* measures,
+                      int32_t num_measures, const int32_t* cols, int32_t ldx, void* workspace,
+                      int64_t workspace_bytes, float* x, int64_t x_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
