@@ -31,6 +31,21 @@ static inline int cgnn_device_ordinal() {
 
 static inline int64_t cgnn_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
+// A persistent grid over `items` work items: at most per_cu workgroups per cgnn_fused_grid() (cgnn.h) unit.
+static inline int cgnn_grid_for(int64_t items, int per_cu) {
+  const int64_t cap = per_cu * (int64_t)cgnn_fused_grid();
+  return (int)(items < cap ? items : cap);
+}
+
+// What every cohort entry point [S, n, n] requires before anything else: row and element indices of one subject
+// and the row index S * n of the cohort fit an int32.  CGNN_OK or CGNN_EINVAL; S == 0 is valid (nothing to do).
+static inline int cgnn_check_cohort(int64_t S, int32_t n) {
+  constexpr int64_t kLimit = (int64_t)1 << 31;
+  if (S < 0 || S >= kLimit || n <= 0) return CGNN_EINVAL;
+  if ((int64_t)n * n >= kLimit || S * (int64_t)n >= kLimit) return CGNN_EINVAL;
+  return CGNN_OK;
+}
+
 // Wave-uniform value made provably uniform for the compiler (-> SGPR, scalar loads).
 __device__ __forceinline__ int cgnn_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 

@@ -25,8 +25,6 @@
 #include "common.h"
 #include "ingest_rows.h"
 
-extern "C" int cgnn_fused_grid(void);
-
 namespace {
 
 constexpr int kThreads = 512;                 // k_ingest: 8 waves
@@ -239,9 +237,7 @@ __global__ __launch_bounds__(kFillThreads) void k_ingest_fill(const float* __res
 
 // the checks every entry point shares; CGNN_OK when there is something to launch
 int check_cohort(const float* matrices, int64_t S, int32_t n) {
-  constexpr int64_t kLimit = (int64_t)1 << 31;
-  if (S < 0 || S >= kLimit || n <= 0) return CGNN_EINVAL;
-  if ((int64_t)n * n >= kLimit || S * (int64_t)n >= kLimit) return CGNN_EINVAL;
+  if (cgnn_check_cohort(S, n) != CGNN_OK) return CGNN_EINVAL;
   if (S > 0 && (!matrices || (reinterpret_cast<uintptr_t>(matrices) & 3))) return CGNN_EINVAL;
   return CGNN_OK;
 }
@@ -256,10 +252,7 @@ int check_cohort(const float* matrices, int64_t S, int32_t n) {
 #ifndef CGNN_INGEST_FILL_PER_CU
 #define CGNN_INGEST_FILL_PER_CU 8
 #endif
-int subject_grid(int64_t S) {
-  const int64_t cap = CGNN_INGEST_WG_PER_CU * (int64_t)cgnn_fused_grid();
-  return (int)(S < cap ? S : cap);
-}
+int subject_grid(int64_t S) { return cgnn_grid_for(S, CGNN_INGEST_WG_PER_CU); }
 
 }  // namespace
 
@@ -303,8 +296,7 @@ extern "C" int cgnn_ingest_fill(const float* matrices, int64_t S, int32_t n, con
   CGNN_NEED_BYTES(edge_weight, edge_weight_bytes, num_edges * (int64_t)sizeof(float));
   const int64_t rows = S * (int64_t)n;
   const int64_t blocks = (rows + kFillThreads / 64 - 1) / (kFillThreads / 64);
-  const int64_t cap = CGNN_INGEST_FILL_PER_CU * (int64_t)cgnn_fused_grid();
-  k_ingest_fill<<<(int)(blocks < cap ? blocks : cap), kFillThreads, 0, cgnn_stream(stream)>>>(
+  k_ingest_fill<<<cgnn_grid_for(blocks, CGNN_INGEST_FILL_PER_CU), kFillThreads, 0, cgnn_stream(stream)>>>(
       matrices, rows, n, thr, row_off, num_edges, edge_local, edge_local + num_edges, edge_weight);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;

@@ -11,43 +11,32 @@
 //   k_measure_rows        a workgroup of 8 waves owns a subject, grid stride: a wave per row counts and sums the kept
 //                         entries with THE row summation of ingest.hip (ingest_rows.h: the same bits) and takes their
 //                         maximum; the workgroup then folds the largest strength and the largest weight.
-//   k_measure_tri<map>    T_i(v) for v = b or u.  V^T V is a product of the shape k_corr solved (timeseries.hip): a
-//                         row-major matrix is its own frame-major panel with the rows k as the frames.  A persistent
-//                         grid walks the items (subject, tile pair bi <= bj) of 96 x 96 entries of G = V^T V; per
-//                         item it steps through the rows k 32 at a time, the two [32, 96] column panels going
-//                         global -> registers -> LDS (the NEXT step's loads are issued before this step's MFMAs) with
-//                         the edge test and the value map applied on the way; rows and columns past n and the
-//                         diagonal are zeros.  Products on v_mfma_f32_16x16x4_f32, the wave / block layout of k_corr
-//                         (a diagonal tile computes the 21 blocks on or above the diagonal).  Epilogue: G_ij v_ij summed
-//                         over j is the partial of T_i for i in bi; for a block off the diagonal G_ij v_ji summed over i
-//                         is the partial of T_j for j in bj (G is symmetric, so this is the mirrored block's row sum).
-//                         Lanes fold by shuffles, waves through LDS in wave order, and the item writes
-//                         part[s][bj][i in bi] and part[s][bi][j in bj] (one slot, both sums, when bi == bj): every
-//                         slot [s][b][i] is written exactly once, by the item (min(blk(i), b), max(blk(i), b)).
+//   k_measure_tri<map>    T_i(v) for v = b or u.  G = V^T V on the tile walk of gram_tile.h: a row-major matrix is
+//                         its own frame-major panel with the rows k as the frames.  Stage: the edge test and the
+//                         value map, applied on the way into LDS; rows and columns past n and the diagonal are zeros.
+//                         Epilogue: G_ij v_ij summed over j is the partial of T_i for i in bi; for a block off the
+//                         diagonal G_ij v_ji summed over i is the partial of T_j for j in bj (G is symmetric, so this
+//                         is the mirrored block's row sum).  Lanes fold by shuffles, waves through LDS in wave order,
+//                         and the item writes part[s][bj][i in bi] and part[s][bi][j in bj] (one slot, both sums, when
+//                         bi == bj): every slot [s][b][i] is written exactly once, by the item
+//                         (min(blk(i), b), max(blk(i), b)).
 //   k_measure_finish      a thread per (subject, node): the nt partials in ascending b, the measures, x[s, i, column].
 //
 // No atomics: the same bits on every run and for every grid.  Element offsets into `matrices` are 64-bit.
 #include <math.h>
 
 #include "common.h"
+#include "gram_tile.h"
 #include "ingest_rows.h"
-
-extern "C" int cgnn_fused_grid(void);
 
 namespace {
 
-constexpr int kTile = 96;                     // G tile: 96 x 96 (360 -> 4 tiles, 84 -> 1)
-constexpr int kKS = 32;                       // matrix rows per K-step
-constexpr int kLd = 112;                      // LDS row stride in floats: 112 % 64 == 48 (timeseries.hip)
-constexpr int kThreads = 256;                 // 4 waves, 2 x 2 over the tile, 48 x 48 entries each
-constexpr int kSlots = kKS * (kTile / 4) / kThreads;
+using namespace gram;
+
 constexpr int kRowThreads = 512;              // k_measure_rows: 8 waves
 constexpr int kRowWaves = kRowThreads / 64;
 constexpr int kFinishThreads = 256;
-static_assert(kSlots * kThreads == kKS * (kTile / 4), "a panel is a whole number of slots per thread");
 static_assert(2 * kTile <= kThreads, "a thread per reduced row and per reduced column");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum {
   kStrength = CGNN_MEASURE_STRENGTH,
@@ -62,7 +51,7 @@ struct Layout {
   int64_t k, s, sub, part_b, part_u, total;
 };
 Layout layout_of(int64_t S, int32_t n, bool need_b, bool need_u) {
-  const int64_t nt = (n + kTile - 1) / kTile;
+  const int64_t nt = tiles_of(n);
   const int64_t part = cgnn_align_up(S * nt * nt * kTile * (int64_t)sizeof(float), 256);
   Layout l;
   l.k = 0;
@@ -124,148 +113,38 @@ __device__ __forceinline__ float value_of(float a, bool off_diagonal, float thr,
 }
 
 struct alignas(16) TriShared {
-  float panel[2][2][kKS * kLd];               // [buffer][side: bi | bj][matrix row k][column]
+  Panels panel;                               // the rows k are the matrix rows
   float red[2][4][kTile / 2];                 // [row sums | column sums][wave][entry of the wave's quadrant]
 };
-
-// 4 consecutive columns of matrix row k from column `col` on; rows and columns >= n read as 0 (never kept)
-template <bool kVec>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ A, int k, int col, int n) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (k < n) {
-    const float* __restrict__ p = A + (int64_t)k * n + col;
-    if (kVec) {
-      if (col < n) v = *reinterpret_cast<const f32x4*>(p);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (col + e < n) v[e] = p[e];
-    }
-  }
-  return v;
-}
-
-// Which of its 3 x 3 blocks a wave computes (bit 3 a + b), as in k_corr: everything off the diagonal; in a diagonal
-// tile the 21 blocks on or above the diagonal, 6 / 5 / 4 / 6 over the waves.
-constexpr int kAll = 0x1FF, kUpper = 0x137, kFirst5 = 0x01F, kLast4 = 0x1E0;
-
-template <int kMask>
-__device__ __forceinline__ void mma_step(const float* __restrict__ pa, const float* __restrict__ pb,
-                                         f32x4 (&acc)[3][3]) {
-#pragma unroll
-  for (int kk = 0; kk < kKS / 4; ++kk) {
-    float fa[3], fb[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      fa[a] = (kMask >> (3 * a)) & 7 ? pa[kk * 4 * kLd + a * 16] : 0.0f;
-      fb[a] = (kMask >> a) & 0x49 ? pb[kk * 4 * kLd + a * 16] : 0.0f;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b)
-        if ((kMask >> (3 * a + b)) & 1)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a], fb[b], acc[a][b], 0, 0, 0);
-  }
-}
-
-// quadrant row / column of wave w in a tile (k_corr's assignment)
-__device__ __forceinline__ int quad_row(int w, bool diag) { return diag ? w == 3 : w >> 1; }
-__device__ __forceinline__ int quad_col(int w, bool diag) { return diag ? w != 0 : w & 1; }
 
 template <bool kWeights, bool kVec>
 __global__ __launch_bounds__(kThreads, 2) void k_measure_tri(const float* __restrict__ matrices, int64_t S, int n,
                                                           const float* __restrict__ thr,
                                                           const float* __restrict__ sub, float* __restrict__ part) {
   __shared__ TriShared sh;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nt = (n + kTile - 1) / kTile;
-  const int pairs = nt * (nt + 1) / 2;
-  const int64_t items = S * pairs;
-  const int nks = (n + kKS - 1) / kKS;
-  // the pairs of one subject on workgroups that share an L2 (blockIdx % 8), where the grid allows it
-  int64_t first = blockIdx.x;
-  if (gridDim.x % 8 == 0) first = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  int srow[kSlots], scol[kSlots];
-#pragma unroll
-  for (int q = 0; q < kSlots; ++q) {
-    const int e = tid + kThreads * q;
-    srow[q] = e / (kTile / 4);
-    scol[q] = 4 * (e % (kTile / 4));
-  }
-  const int frow = lane >> 4, fcol = lane & 15;
+  const Thread th;
+  const int nt = tiles_of(n);
+  const int64_t items = S * pairs_of(nt);
 
-  for (int64_t item = first; item < items; item += gridDim.x) {
-    const int64_t s = item / pairs;
-    int rem = (int)(item - s * pairs), bi = 0;
-    while (rem >= nt - bi) {
-      rem -= nt - bi;
-      ++bi;
-    }
-    const int bj = bi + rem;
-    const bool diag = bi == bj;
+  for (int64_t item = first_item(); item < items; item += gridDim.x) {
+    const Item it(item, nt, th.wave);
+    const int64_t s = it.unit;
     const float* __restrict__ A = matrices + s * (int64_t)n * n;
     const float thr_s = thr[s];
     const float rcw = kWeights ? 1.0f / cbrtf(sub[2 * s + 1]) : 1.0f;
-    const int col0[2] = {bi * kTile, bj * kTile};
-    const int wr = quad_row(wave, diag), wc = quad_col(wave, diag);
-    const int mask = !diag ? kAll : (wave == 0 || wave == 3) ? kUpper : wave == 1 ? kFirst5 : kLast4;
 
-    f32x4 pre[2][kSlots];
-#pragma unroll
-    for (int q = 0; q < kSlots; ++q) {
-      pre[0][q] = load4<kVec>(A, srow[q], col0[0] + scol[q], n);
-      if (!diag) pre[1][q] = load4<kVec>(A, srow[q], col0[1] + scol[q], n);
-    }
+    f32x4 pre[2][kSlots], acc[3][3];
+    load_panels<kVec>(pre, A, n, n, 0, it, th);
     __syncthreads();                          // the previous item's epilogue still reads sh.red and a panel
 
-    // registers -> LDS buffer `buf` through the value map; what load4 read as 0 is never kept
-    auto stage = [&](int buf, int ks) {
+    // through the value map; what load4 read as 0 is never kept
+    run<kVec>(sh.panel, pre, acc, A, n, n, it, th, [&](int side, int k, int c, f32x4 v) {
+      f32x4 z;
 #pragma unroll
-      for (int side = 0; side < 2; ++side) {
-        if (side == 1 && diag) break;
-#pragma unroll
-        for (int q = 0; q < kSlots; ++q) {
-          const int k = ks * kKS + srow[q], c = col0[side] + scol[q];
-          f32x4 z;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) z[e] = value_of<kWeights>(pre[side][q][e], k != c + e, thr_s, rcw);
-          *reinterpret_cast<f32x4*>(&sh.panel[buf][side][srow[q] * kLd + scol[q]]) = z;
-        }
-      }
-    };
-    stage(0, 0);
-    __syncthreads();
+      for (int e = 0; e < 4; ++e) z[e] = value_of<kWeights>(v[e], k != it.col0(side) + c + e, thr_s, rcw);
+      return z;
+    });
 
-    f32x4 acc[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    int cur = 0;
-    for (int ks = 0; ks < nks; ++ks) {
-      const bool more = ks + 1 < nks;
-      if (more) {
-#pragma unroll
-        for (int q = 0; q < kSlots; ++q) {
-          const int k = (ks + 1) * kKS + srow[q];
-          pre[0][q] = load4<kVec>(A, k, col0[0] + scol[q], n);
-          if (!diag) pre[1][q] = load4<kVec>(A, k, col0[1] + scol[q], n);
-        }
-      }
-      const float* __restrict__ pa = &sh.panel[cur][0][frow * kLd + wr * 48 + fcol];
-      const float* __restrict__ pb = &sh.panel[cur][diag ? 0 : 1][frow * kLd + wc * 48 + fcol];
-      if (mask == kAll) mma_step<kAll>(pa, pb, acc);
-      else if (mask == kUpper) mma_step<kUpper>(pa, pb, acc);
-      else if (mask == kFirst5) mma_step<kFirst5>(pa, pb, acc);
-      else mma_step<kLast4>(pa, pb, acc);
-      if (more) stage(cur ^ 1, ks + 1);
-      __syncthreads();
-      cur ^= 1;
-    }
-
-    // G[i][j] of a 16 x 16 block: lane l, register r holds i = 4 (l >> 4) + r, j = l & 15
     float rsum[3][4], csum[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -273,25 +152,17 @@ __global__ __launch_bounds__(kThreads, 2) void k_measure_tri(const float* __rest
 #pragma unroll
       for (int r = 0; r < 4; ++r) rsum[a][r] = 0.0f;
     }
+    for_each_block(it, th, [&](int a, int b, bool tri, int, int gi0, int gj) {
+      f32x4 mir = {0.f, 0.f, 0.f, 0.f};                       // A[gj][gi0 .. gi0 + 3], zeros outside the matrix
+      if (!tri) mir = load4<kVec>(A, gj, n, gi0, n);         // (a block on the diagonal holds its own mirror)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        if (!((mask >> (3 * a + b)) & 1)) continue;           // another wave's, or below the diagonal
-        const int rb = wr * 3 + a, cb = wc * 3 + b;           // block row / column inside the tile
-        const bool both = !(diag && rb == cb);                // a block on the diagonal holds its own mirror
-        const int gi0 = col0[0] + rb * 16 + 4 * frow, gj = col0[1] + cb * 16 + fcol;
-        f32x4 mir = {0.f, 0.f, 0.f, 0.f};                     // A[gj][gi0 .. gi0 + 3], zeros outside the matrix
-        if (both) mir = load4<kVec>(A, gj, gi0, n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int gi = gi0 + r;
-          const float aij = gi < n && gj < n ? A[(int64_t)gi * n + gj] : 0.0f;
-          rsum[a][r] += acc[a][b][r] * value_of<kWeights>(aij, gi != gj, thr_s, rcw);
-          if (both) csum[b] += acc[a][b][r] * value_of<kWeights>(mir[r], gi != gj, thr_s, rcw);
-        }
+      for (int r = 0; r < 4; ++r) {
+        const int gi = gi0 + r;
+        const float aij = gi < n && gj < n ? A[(int64_t)gi * n + gj] : 0.0f;
+        rsum[a][r] += acc[a][b][r] * value_of<kWeights>(aij, gi != gj, thr_s, rcw);
+        if (!tri) csum[b] += acc[a][b][r] * value_of<kWeights>(mir[r], gi != gj, thr_s, rcw);
       }
-    }
+    });
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -299,30 +170,30 @@ __global__ __launch_bounds__(kThreads, 2) void k_measure_tri(const float* __rest
         float v = rsum[a][r];
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-        if (fcol == 0) sh.red[0][wave][a * 16 + 4 * frow + r] = v;
+        if (th.fcol == 0) sh.red[0][th.wave][a * 16 + 4 * th.frow + r] = v;
       }
       float c = csum[a];
       c += __shfl_xor(c, 16, 64);
       c += __shfl_xor(c, 32, 64);
-      if (frow == 0) sh.red[1][wave][a * 16 + fcol] = c;
+      if (th.frow == 0) sh.red[1][th.wave][a * 16 + th.fcol] = c;
     }
     __syncthreads();
     // the waves of a quadrant row (column), in wave order; a diagonal tile adds both into the one slot it owns
-    if (tid < 2 * kTile) {
-      const int kind = tid / kTile, c = tid - kind * kTile;
+    if (th.tid < 2 * kTile) {
+      const int kind = th.tid / kTile, c = th.tid - kind * kTile;
       const int quad = c / (kTile / 2), e = c - quad * (kTile / 2);
-      if (!(diag && kind == 1)) {
+      if (!(it.diag && kind == 1)) {
         float v = 0.0f;
 #pragma unroll
         for (int w = 0; w < 4; ++w)
-          if ((kind == 0 ? quad_row(w, diag) : quad_col(w, diag)) == quad) v += sh.red[kind][w][e];
-        if (diag) {
+          if ((kind == 0 ? quad_row(w, it.diag) : quad_col(w, it.diag)) == quad) v += sh.red[kind][w][e];
+        if (it.diag) {
 #pragma unroll
           for (int w = 0; w < 4; ++w)
             if (quad_col(w, true) == quad) v += sh.red[1][w][e];
         }
         // row sums: nodes of tile bi, summed over the columns of tile bj; column sums the other way round
-        const int node_tile = kind == 0 ? bi : bj, over_tile = kind == 0 ? bj : bi;
+        const int node_tile = kind == 0 ? it.bi : it.bj, over_tile = kind == 0 ? it.bj : it.bi;
         part[((s * nt + over_tile) * nt + node_tile) * (int64_t)kTile + c] = v;
       }
     }
@@ -340,7 +211,7 @@ __global__ __launch_bounds__(kFinishThreads) void k_measure_finish(int64_t S, in
                                                                    const float* __restrict__ part_b,
                                                                    const float* __restrict__ part_u, Columns cols,
                                                                    float* __restrict__ x) {
-  const int nt = (n + kTile - 1) / kTile;
+  const int nt = tiles_of(n);
   const int64_t rows = S * n;
   for (int64_t r = (int64_t)blockIdx.x * kFinishThreads + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * kFinishThreads) {
@@ -373,11 +244,6 @@ __global__ __launch_bounds__(kFinishThreads) void k_measure_finish(int64_t S, in
 #define CGNN_MEASURE_ROWS_PER_CU 4
 #endif
 
-int grid_for(int64_t items, int per_cu) {
-  const int64_t cap = per_cu * (int64_t)cgnn_fused_grid();
-  return (int)(items < cap ? items : cap);
-}
-
 // (CGNN_OK, the bitmask of the measures) of a valid list: 1 to 5 distinct ids
 int check_measures(const int32_t* measures, int32_t num, int* mask) {
   if (!measures || num < 1 || num > CGNN_NUM_MEASURES) return CGNN_EINVAL;
@@ -390,18 +256,10 @@ int check_measures(const int32_t* measures, int32_t num, int* mask) {
   return CGNN_OK;
 }
 
-int check_cohort(int64_t S, int32_t n) {
-  constexpr int64_t kLimit = (int64_t)1 << 31;
-  if (S < 0 || S >= kLimit || n <= 0) return CGNN_EINVAL;
-  if ((int64_t)n * n >= kLimit || S * (int64_t)n >= kLimit) return CGNN_EINVAL;
-  return CGNN_OK;
-}
-
 template <bool kWeights>
 void launch_tri(const float* matrices, int64_t S, int32_t n, const float* thr, const float* sub, float* part,
                 hipStream_t hs) {
-  const int64_t nt = (n + kTile - 1) / kTile;
-  const int grid = grid_for(S * (nt * (nt + 1) / 2), CGNN_MEASURE_WG_PER_CU);
+  const int grid = cgnn_grid_for(S * pairs_of(tiles_of(n)), CGNN_MEASURE_WG_PER_CU);
   if (n % 4 == 0 && !(reinterpret_cast<uintptr_t>(matrices) & 15))
     k_measure_tri<kWeights, true><<<grid, kThreads, 0, hs>>>(matrices, S, n, thr, sub, part);
   else
@@ -413,7 +271,8 @@ void launch_tri(const float* matrices, int64_t S, int32_t n, const float* thr, c
 extern "C" int64_t cgnn_ingest_measures_workspace_bytes(int64_t S, int32_t n, const int32_t* measures,
                                                         int32_t num_measures) {
   int mask = 0;
-  if (check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK) return CGNN_EINVAL;
+  if (cgnn_check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK)
+    return CGNN_EINVAL;
   return layout_of(S, n, (mask >> kClustering) & 1, (mask >> kWeighted) & 1).total;
 }
 
@@ -421,7 +280,8 @@ extern "C" int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n,
                                     const int32_t* measures, int32_t num_measures, void* workspace,
                                     int64_t workspace_bytes, float* x, int64_t x_bytes, void* stream) {
   int mask = 0;
-  if (check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK) return CGNN_EINVAL;
+  if (cgnn_check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK)
+    return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
   if (!matrices || !thr || !workspace || !x) return CGNN_EINVAL;
   if ((reinterpret_cast<uintptr_t>(matrices) & 3) || (reinterpret_cast<uintptr_t>(thr) & 3) ||
@@ -438,7 +298,8 @@ extern "C" int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n,
   float* part_b = need_b ? reinterpret_cast<float*>(ws + l.part_b) : nullptr;
   float* part_u = need_u ? reinterpret_cast<float*>(ws + l.part_u) : nullptr;
   hipStream_t hs = cgnn_stream(stream);
-  k_measure_rows<<<grid_for(S, CGNN_MEASURE_ROWS_PER_CU), kRowThreads, 0, hs>>>(matrices, S, n, thr, deg, strength, sub);
+  k_measure_rows<<<cgnn_grid_for(S, CGNN_MEASURE_ROWS_PER_CU), kRowThreads, 0, hs>>>(matrices, S, n, thr, deg, strength,
+                                                                                     sub);
   CGNN_CHECK_LAUNCH();
   if (need_b) {
     launch_tri<false>(matrices, S, n, thr, sub, part_b, hs);
@@ -453,7 +314,8 @@ extern "C" int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n,
   for (int c = 0; c < num_measures; ++c) cols.col[measures[c]] = c;
   cols.F = num_measures;
   const int64_t blocks = (S * n + kFinishThreads - 1) / kFinishThreads;
-  k_measure_finish<<<grid_for(blocks, 8), kFinishThreads, 0, hs>>>(S, n, deg, strength, sub, part_b, part_u, cols, x);
+  k_measure_finish<<<cgnn_grid_for(blocks, 8), kFinishThreads, 0, hs>>>(S, n, deg, strength, sub, part_b, part_u, cols,
+                                                                        x);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

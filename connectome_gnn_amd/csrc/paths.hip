@@ -41,8 +41,6 @@
 #include "common.h"
 #include "ingest_rows.h"
 
-extern "C" int cgnn_fused_grid(void);
-
 namespace {
 
 constexpr int kThreads = 512;
@@ -264,11 +262,9 @@ int check_request(const int32_t* measures, int32_t num, const int32_t* cols, int
   return CGNN_OK;
 }
 
+// (n <= CGNN_PATH_MAX_NODES is the stricter bound on n * n)
 int check_cohort(int64_t S, int32_t n) {
-  constexpr int64_t kLimit = (int64_t)1 << 31;
-  if (S < 0 || S >= kLimit || n <= 0 || n > CGNN_PATH_MAX_NODES) return CGNN_EINVAL;
-  if (S * (int64_t)n >= kLimit) return CGNN_EINVAL;
-  return CGNN_OK;
+  return n > CGNN_PATH_MAX_NODES ? CGNN_EINVAL : cgnn_check_cohort(S, n);
 }
 
 bool paths_attr() {
@@ -313,8 +309,7 @@ extern "C" int cgnn_ingest_paths(const float* matrices, int64_t S, int32_t n, co
   // workgroups a CU holds: by LDS, and 8 waves each against 32 wave slots
   int per_cu = (int)((size_t)kLdsBytes / lds);
   per_cu = per_cu > 4 ? 4 : per_cu;
-  const int64_t cap = per_cu * (int64_t)cgnn_fused_grid();
-  k_paths<<<(int)(S < cap ? S : cap), kThreads, lds, cgnn_stream(stream)>>>(matrices, S, n, thr, c, x);
+  k_paths<<<cgnn_grid_for(S, per_cu), kThreads, lds, cgnn_stream(stream)>>>(matrices, S, n, thr, c, x);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

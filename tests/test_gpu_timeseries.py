@@ -18,7 +18,10 @@ from tests import timeseries_data as D
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 S = 3
-SHAPES = [(2, 1), (2, 5), (3, 2), (7, 20), (31, 63), (32, 64), (33, 65), (70, 84), (33, 130), (40, 360)]
+SHAPES = [(2, 1), (2, 5), (3, 2), (7, 20), (31, 63), (32, 64), (33, 65), (70, 84), (33, 130), (40, 360),
+          # the 96 x 96 tile walk: one full tile on the vector path; two tiles, one live column in the second, and
+          # three tiles, both on the element path
+          (5, 96), (33, 97), (9, 193)]
 
 
 @functools.lru_cache(maxsize=None)
