@@ -226,6 +226,8 @@ PROTOTYPES = {
     "cgnn_l0_grid": (c_int, [c_int64]),
     "cgnn_gcn_l0_center": (c_int, [TP, P, I32, P, P]),
     "cgnn_gcn_l0_fwd": (c_int, [TP, P, I32, P, P, P, P, P, I64, P, P, P, BP, P]),
+    "cgnn_gcn_l0_agg": (c_int, [TP, P, I32, P, P, P, I64, P]),
+    "cgnn_gcn_l0_stats": (c_int, [P, I32, I32, P, P, P, P, P, P, I64, BP, P]),
     "cgnn_gcn_l0_bwd": (c_int, [P, P, LP, P, P, P, I64, P, I64, P, I64, P, P]),
     "cgnn_gcn_l0_bwd_dx": (c_int, [P, LP, P, P, P, I64, P, I64, P, I64, P, P, I64, P]),
     "cgnn_gcn_l0_dx": (c_int, [TP, P, I32, P, I64, P]),

@@ -58,19 +58,44 @@ static_assert(sizeof(cgnn_bn_tail) == 120, "cgnn.h: struct cgnn_bn_tail (ctypes 
 
 #define CGNN_AGENT __HIP_MEMORY_SCOPE_AGENT
 
-// column `c`'s partial of this workgroup -> accumulator.  Returns a value that depends on both atomics'
-// return values (consume it, e.g. store it to LDS, before bnacc_arrive: that is the wait).
-__device__ __forceinline__ unsigned long long bnacc_add(BnAcc* acc, int c, double x) {
-  if (!(fabs(x) < 4.0e18)) {                       // inf / nan / beyond 2^62: flagged, not added
-    return (unsigned long long)__hip_atomic_fetch_or(&acc->nonfinite, 1u, __ATOMIC_RELAXED, CGNN_AGENT);
-  }
-  const int sub = blockIdx.x & (BN_SUB - 1);
+// a partial as the accumulator's fixed-point pair; false = inf / nan / beyond 2^62 (flagged, not added)
+__device__ __forceinline__ bool bn_fixed(double x, long long& hi, long long& lo) {
+  if (!(fabs(x) < 4.0e18)) return false;
   const double fl = floor(x);
-  const long long hi = (long long)fl;
-  const long long lo = (long long)((x - fl) * 4503599627370496.0);                // [0, 2^52)
+  hi = (long long)fl;
+  lo = (long long)((x - fl) * 4503599627370496.0);                                // [0, 2^52)
+  return true;
+}
+
+// a pair (or a sum of pairs) of column `c` -> accumulator
+__device__ __forceinline__ unsigned long long bnacc_add_fixed(BnAcc* acc, int c, long long hi, long long lo) {
+  const int sub = blockIdx.x & (BN_SUB - 1);
   const long long a = __hip_atomic_fetch_add(&acc->hi[sub][c], hi, __ATOMIC_RELAXED, CGNN_AGENT);
   const long long b = __hip_atomic_fetch_add(&acc->lo[sub][c], lo, __ATOMIC_RELAXED, CGNN_AGENT);
   return (unsigned long long)(a ^ b);
+}
+
+// column `c`'s partial of this workgroup -> accumulator.  Returns a value that depends on both atomics'
+// return values (consume it, e.g. store it to LDS, before bnacc_arrive: that is the wait).
+__device__ __forceinline__ unsigned long long bnacc_add(BnAcc* acc, int c, double x) {
+  long long hi, lo;
+  if (!bn_fixed(x, hi, lo))
+    return (unsigned long long)__hip_atomic_fetch_or(&acc->nonfinite, 1u, __ATOMIC_RELAXED, CGNN_AGENT);
+  return bnacc_add_fixed(acc, c, hi, lo);
+}
+
+// A workgroup that owns SEVERAL partials of a column (k_l0_stats: one per stored moment set) splits each one
+// exactly as bnacc_add does and sums the pairs in 64-bit integer registers: integer addition is associative,
+// so after ONE atomic pair per column the accumulator holds the bits that one atomic pair per partial would
+// have left (a sum of the partials in fp64 would not).  `bad` collects the non-finite flag.
+__device__ __forceinline__ void bn_fixed_accumulate(double x, long long& hi, long long& lo, unsigned int& bad) {
+  long long h, l;
+  if (bn_fixed(x, h, l)) {
+    hi += h;
+    lo += l;
+  } else {
+    bad = 1u;
+  }
 }
 
 // Call from ALL threads of the workgroup after every bnacc_add of the workgroup has returned (its return
@@ -131,6 +156,24 @@ __device__ __forceinline__ void bn_tail_run(const cgnn_bn_tail& t, const double*
   BnAcc* acc = static_cast<BnAcc*>(t.acc);
   if (threadIdx.x < 128) {
     const unsigned long long r = bnacc_add(acc, threadIdx.x, wg_sums[threadIdx.x]);
+    scratch[1 + threadIdx.x] = (int)(r & 1u);      // consuming the returns = waiting for the atomics
+  }
+  __syncthreads();
+  if (!bnacc_arrive(acc, scratch)) return;
+  if (threadIdx.x < 64) bn_tail_finalize(t, acc, threadIdx.x, mean_off_of(threadIdx.x));
+  __syncthreads();
+  if (threadIdx.x == 0) bnacc_reset(acc);
+}
+
+// The same tail for a workgroup whose threads t < 128 hold column t's partials as a summed fixed-point pair
+// (bn_fixed_accumulate); arrivals are counted against the calling kernel's own grid, as above.
+template <typename MeanOff>
+__device__ __forceinline__ void bn_tail_run_fixed(const cgnn_bn_tail& t, long long hi, long long lo, unsigned int bad,
+                                                  int* scratch, MeanOff mean_off_of) {
+  BnAcc* acc = static_cast<BnAcc*>(t.acc);
+  if (threadIdx.x < 128) {
+    unsigned long long r = bnacc_add_fixed(acc, threadIdx.x, hi, lo);
+    if (bad) r ^= (unsigned long long)__hip_atomic_fetch_or(&acc->nonfinite, 1u, __ATOMIC_RELAXED, CGNN_AGENT);
     scratch[1 + threadIdx.x] = (int)(r & 1u);      // consuming the returns = waiting for the atomics
   }
   __syncthreads();

@@ -36,8 +36,96 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 #define L0STNT stnt4
 __device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 
+// -- pieces of the factored layer 0 shared by k_l0_fwd<false> and k_l0_stats (one source, so that the two
+//    kernels produce the same bits) --------------------------------------------------------------------
+constexpr int L0NM = FP + 1;          // the 9 "columns" of the second moments: p_0..p_7 and 1
+constexpr int L0RC = FP - 1;          // the ones column / center[7] = rbar
+
+// the centred form's W' = [W0 | W0 c] row and constant b + rbar W0 c of channel c (one thread per channel)
+__device__ __forceinline__ void l0_write_weff(const float* __restrict__ W0, const float* __restrict__ bias,
+                                              const float* __restrict__ center, int F0, int c,
+                                              float* __restrict__ w_eff, float* __restrict__ mean_offset) {
+  double last = 0.0;
+  for (int k = 0; k < F0; ++k) {
+    const float wv = W0[c * F0 + k];
+    w_eff[c * (F0 + 1) + k] = wv;
+    last += (double)wv * (double)center[k];
+  }
+  w_eff[c * (F0 + 1) + F0] = (float)last;
+  if (mean_offset)
+    mean_offset[c] = (float)((double)bias[c] + (double)(float)last * (double)center[L0RC]);
+}
+
+// ... the same constant, recomputed by the BatchNorm tail's threads exactly as l0_write_weff wrote it
+__device__ __forceinline__ float l0_mean_off(const float* __restrict__ W0, const float* __restrict__ bias,
+                                             const float* __restrict__ center, int F0, int c) {
+  double last = 0.0;
+  for (int k = 0; k < F0; ++k) last += (double)W0[c * F0 + k] * (double)center[k];
+  return (float)((double)bias[c] + (double)(float)last * (double)center[L0RC]);
+}
+
+// moments -> sums, in fp64, with the moments M of the stored rows p' (M[k][l] at M[k * 9 + l]) and the weights
+// W' the consumers use (fp32-rounded last column):
+//   S1[c] = sum_k W'[c][k] M[k][8] + M[8][8] b[c]                 (b = 0 in the centred form:
+//   S2[c] = sum_kl W'[c][k] W'[c][l] M[k][l] + 2 b[c] sum_k W'[c][k] M[k][8] + M[8][8] b[c]^2    sums of y_c)
+// l0_wrow: channel c's row of W' -> wc[k * WS], k < 8 (LDS);  l0_sums: thread t < 128 -> S1[t] (t < 64) or S2[t - 64].
+// WS: the stride of a row's elements (1 = a thread's own 64 bytes, as k_l0_fwd has room for; k_l0_stats, whose
+// 16 waves share the rows, interleaves them by thread: no bank conflicts).  WIDE: all of the row's loads of W0 in
+// flight at once instead of one per trip (registers k_l0_fwd does not have); the same chain of operations.
+template <int WS, bool WIDE>
+__device__ __forceinline__ void l0_wrow(double* wc, const float* __restrict__ W0, const float* cvec, int F0, int c,
+                                        bool centred) {
+  double last = 0.0;
+  if (WIDE) {
+    float wv[FP];
+#pragma unroll
+    for (int k = 0; k < FP; ++k) wv[k] = k < F0 ? W0[c * F0 + k] : 0.f;
+#pragma unroll
+    for (int k = 0; k < FP; ++k)
+      if (k < F0) {
+        wc[k * WS] = (double)wv[k];
+        last += (double)wv[k] * (double)cvec[k];
+      }
+  } else {
+#pragma unroll 1
+    for (int k = 0; k < F0; ++k) {
+      wc[k * WS] = (double)W0[c * F0 + k];
+      last += wc[k * WS] * (double)cvec[k];
+    }
+  }
+  if (centred) wc[F0 * WS] = (double)(float)last;      // exactly the w_eff value
+}
+
+template <int WS>
+__device__ __forceinline__ double l0_sums(const double* M, const double* wc, double bc, double cnt, int F0, int t,
+                                          bool centred) {
+  constexpr int NM = L0NM;
+  const int FA = centred ? F0 + 1 : F0;
+  double lin = 0.0;                              // sum_k W'[c][k] M1[k]
+#pragma unroll 1
+  for (int k = 0; k < FA; ++k) lin += wc[k * WS] * M[k * NM + FP];
+  double out = lin + cnt * bc;
+  if (t >= 64) {
+    double quad = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < FA; ++k) {
+      double rowsum = 0.0;
+#pragma unroll 1
+      for (int l = 0; l < FA; ++l) rowsum += wc[l * WS] * M[k * NM + l];
+      quad += wc[k * WS] * rowsum;
+    }
+    out = quad + 2.0 * bc * lin + cnt * bc * bc;
+  }
+  return out;
+}
+
+// WRITE_Y = false has two forms.  The full one (AGG_ONLY = false) ends with the layer's BatchNorm sums; the
+// aggregate-only one runs the same phases 1-3 and the same fixed-order fold of the waves' moments, then writes
+// the workgroup's 81 fp64 moments to `stat_slab` (there: moments[gridDim.x][81]) and returns -- everything in it
+// is a function of the batch alone (cgnn_gcn_l0_agg; k_l0_stats turns the stored moments into the sums).  It
+// takes no W0, bias, w_eff, mean_offset or tail.
 #define CGNN_L0_MINW 8
-template <bool WRITE_Y>
+template <bool WRITE_Y, bool AGG_ONLY = false>
 __global__ void __launch_bounds__(L0THR, WRITE_Y ? 5 : CGNN_L0_MINW) k_l0_fwd(cgnn_tiles t, const float* __restrict__ X0, int F0,
                                                   const float* __restrict__ W0,
                                                   const float* __restrict__ bias,
@@ -90,17 +178,8 @@ __global__ void __launch_bounds__(L0THR, WRITE_Y ? 5 : CGNN_L0_MINW) k_l0_fwd(cg
   if (!WRITE_Y) {
     if (threadIdx.x < FP)
       cvec[threadIdx.x] = (center && (threadIdx.x < F0 || threadIdx.x == RC)) ? center[threadIdx.x] : 0.f;
-    if (w_eff && blockIdx.x == 0 && threadIdx.x < HID) {
-      double last = 0.0;
-      for (int k = 0; k < F0; ++k) {
-        const float wv = W0[threadIdx.x * F0 + k];
-        w_eff[threadIdx.x * (F0 + 1) + k] = wv;
-        last += (double)wv * (double)center[k];
-      }
-      w_eff[threadIdx.x * (F0 + 1) + F0] = (float)last;
-      if (mean_offset)
-        mean_offset[threadIdx.x] = (float)((double)bias[threadIdx.x] + (double)(float)last * (double)center[RC]);
-    }
+    if (!AGG_ONLY && w_eff && blockIdx.x == 0 && threadIdx.x < HID)
+      l0_write_weff(W0, bias, center, F0, threadIdx.x, w_eff, mean_offset);
     __syncthreads();
   }
   const bool centred = !WRITE_Y && center != nullptr;
@@ -229,44 +308,22 @@ __global__ void __launch_bounds__(L0THR, WRITE_Y ? 5 : CGNN_L0_MINW) k_l0_fwd(cg
   if (!stat_slab && !tail.acc) return;
   __syncthreads();
   if (!WRITE_Y) {
-    // moments -> sums: the waves' accumulators folded in fixed order, then, with the moments M of
-    // the stored rows p' and the weights W' the consumers use (fp32-rounded last column), in fp64:
-    //   S1[c] = sum_k W'[c][k] M[k][8] + M[8][8] b[c]                 (b = 0 in the centred form:
-    //   S2[c] = sum_kl W'[c][k] W'[c][l] M[k][l] + 2 b[c] sum_k W'[c][k] M[k][8] + M[8][8] b[c]^2    sums of y_c)
+    // moments -> sums: the waves' accumulators folded in fixed order, then l0_sums
     if (threadIdx.x < NM * NM) {
       double tsum = 0.0;
 #pragma unroll
       for (int w2 = 0; w2 < NWV; ++w2) tsum += macc[w2 * NM * NM + threadIdx.x];
-      red[threadIdx.x] = tsum;                       // M[k][l] at red[k * NM + l]
+      if (AGG_ONLY) stat_slab[(int64_t)blockIdx.x * (NM * NM) + threadIdx.x] = tsum;
+      else red[threadIdx.x] = tsum;                  // M[k][l] at red[k * NM + l]
     }
+    if (AGG_ONLY) return;
     __syncthreads();
     if (threadIdx.x < 128) {
       const int c = threadIdx.x & 63;
       const double bc = centred ? 0.0 : (double)bias[c], cnt = red[FP * NM + FP];
       double* wc = red + 128 + FP * threadIdx.x;      // (smem is dead here; M occupies red[0..80])
-      double last = 0.0;
-#pragma unroll 1
-      for (int k = 0; k < F0; ++k) {
-        wc[k] = (double)W0[c * F0 + k];
-        last += wc[k] * (double)cvec[k];
-      }
-      if (centred) wc[F0] = (double)(float)last;      // exactly the w_eff value
-      const int FA = centred ? F0 + 1 : F0;
-      double lin = 0.0;                              // sum_k W'[c][k] M1[k]
-#pragma unroll 1
-      for (int k = 0; k < FA; ++k) lin += wc[k] * red[k * NM + FP];
-      double out = lin + cnt * bc;
-      if (threadIdx.x >= 64) {
-        double quad = 0.0;
-#pragma unroll 1
-        for (int k = 0; k < FA; ++k) {
-          double rowsum = 0.0;
-#pragma unroll 1
-          for (int l = 0; l < FA; ++l) rowsum += wc[l] * red[k * NM + l];
-          quad += wc[k] * rowsum;
-        }
-        out = quad + 2.0 * bc * lin + cnt * bc * bc;
-      }
+      l0_wrow<1, false>(wc, W0, cvec, F0, c, centred);
+      const double out = l0_sums<1>(red, wc, bc, cnt, F0, threadIdx.x, centred);
       if (tail.acc) red[1280 + threadIdx.x] = out;     // (red[0..1152) hold M and the threads' weight rows)
       else stat_slab[(int64_t)blockIdx.x * 128 + threadIdx.x] = out;
     }
@@ -275,12 +332,8 @@ __global__ void __launch_bounds__(L0THR, WRITE_Y ? 5 : CGNN_L0_MINW) k_l0_fwd(cg
       // constant b + rbar W0 c -- which the statistics were taken without and only the running mean sees --
       // is recomputed by the tail's threads exactly as workgroup 0 wrote it to `mean_offset`
       __syncthreads();
-      bn_tail_run(tail, red + 1280, reinterpret_cast<int*>(red + 1408), [&](int c) {
-        if (!centred) return 0.f;
-        double last = 0.0;
-        for (int k = 0; k < F0; ++k) last += (double)W0[c * F0 + k] * (double)center[k];
-        return (float)((double)bias[c] + (double)(float)last * (double)center[RC]);
-      });
+      bn_tail_run(tail, red + 1280, reinterpret_cast<int*>(red + 1408),
+                  [&](int c) { return centred ? l0_mean_off(W0, bias, center, F0, c) : 0.f; });
     }
     return;
   }
@@ -557,6 +610,76 @@ int l0_grid(int64_t nn) {
   return (int)(want < cus ? cus : (want > CGNN_L0_GRID_MULT * cus ? CGNN_L0_GRID_MULT * cus : want));
 }
 
+// The per-step half of the factored layer 0 on a KEPT batch: the stored moment sets of cgnn_gcn_l0_agg (one
+// per k_l0_fwd workgroup, moments[sets][81]) -> the same 128 BatchNorm sums per set that k_l0_fwd<false> ends
+// with (l0_wrow / l0_sums), to stat_slab[set][128] or through the BatchNorm tail.  A workgroup is
+// CGNN_L0_GRID_MULT groups of 128 threads, each group on a set of its own (set = workgroup + group * grid, ...),
+// so at most one workgroup per CU covers every set in one pass; with a tail, a thread adds up the fixed-point
+// pairs of its sets, the groups' pairs are added in LDS and ONE atomic pair per column leaves the workgroup
+// (bn_tail.h) instead of one per set.  Workgroup 0 writes w_eff and mean_offset as k_l0_fwd does; with neither
+// a slab nor a tail (eval mode) that is all.
+constexpr int L0SG = CGNN_L0_GRID_MULT;      // groups (sets in flight) per workgroup
+constexpr int L0STHR = 128 * L0SG;
+__global__ void __launch_bounds__(L0STHR) k_l0_stats(const double* __restrict__ moments, int sets, int F0,
+                                                     const float* __restrict__ W0, const float* __restrict__ bias,
+                                                     const float* __restrict__ center, float* __restrict__ w_eff,
+                                                     float* __restrict__ mean_offset, double* __restrict__ stat_slab,
+                                                     cgnn_bn_tail tail) {
+  constexpr int NM = L0NM;
+  __shared__ double M[L0SG][NM * NM + 7];
+  __shared__ double wrow[FP * 128];                 // W'[c][k] of thread t at wrow[k * 128 + t]
+  __shared__ float cvec[FP];
+  __shared__ long long fh[L0SG][128], fl[L0SG][128];
+  __shared__ unsigned int fb[L0SG][128];
+  __shared__ int scratch[132];
+  const int t = threadIdx.x & 127, g = threadIdx.x >> 7, c = t & 63;
+  const bool centred = center != nullptr;
+  if (threadIdx.x < FP)
+    cvec[threadIdx.x] = (center && (threadIdx.x < F0 || threadIdx.x == L0RC)) ? center[threadIdx.x] : 0.f;
+  if (w_eff && blockIdx.x == 0 && threadIdx.x < HID)
+    l0_write_weff(W0, bias, center, F0, threadIdx.x, w_eff, mean_offset);
+  if (!stat_slab && !tail.acc) return;
+  __syncthreads();
+  // (the first pass's moments are in flight while the W' rows are read)
+  int s0 = blockIdx.x, s = s0 + g * gridDim.x;
+  double mv = (s < sets && t < NM * NM) ? moments[(int64_t)s * (NM * NM) + t] : 0.0;
+  const double bc = centred ? 0.0 : (double)bias[c];
+  if (g == 0) l0_wrow<128, true>(wrow + t, W0, cvec, F0, c, centred);
+  long long hi = 0, lo = 0;
+  unsigned int bad = 0u;
+  for (;;) {                                            // (every condition on s0 is uniform over the workgroup)
+    if (s < sets && t < NM * NM) M[g][t] = mv;
+    __syncthreads();
+    if (s < sets) {
+      const double out = l0_sums<128>(M[g], wrow + t, bc, M[g][FP * NM + FP], F0, t, centred);
+      if (tail.acc) bn_fixed_accumulate(out, hi, lo, bad);
+      else stat_slab[(int64_t)s * 128 + t] = out;
+    }
+    s0 += gridDim.x * L0SG;
+    if (s0 >= sets) break;
+    s = s0 + g * gridDim.x;
+    mv = (s < sets && t < NM * NM) ? moments[(int64_t)s * (NM * NM) + t] : 0.0;
+    __syncthreads();                                    // the pass before has read M
+  }
+  if (!tail.acc) return;
+  fh[g][t] = hi; fl[g][t] = lo; fb[g][t] = bad;
+  __syncthreads();
+  if (threadIdx.x < 128) {
+#pragma unroll
+    for (int g2 = 1; g2 < L0SG; ++g2) {
+      hi += fh[g2][t]; lo += fl[g2][t]; bad |= fb[g2][t];
+    }
+  }
+  bn_tail_run_fixed(tail, hi, lo, bad, scratch,
+                    [&](int ch) { return centred ? l0_mean_off(W0, bias, center, F0, ch) : 0.f; });
+}
+
+// workgroups of k_l0_stats: at most one per CU, none without a set
+int l0_stats_grid(int sets) {
+  const int cus = cgnn_fused_grid();
+  return sets < cus ? sets : cus;
+}
+
 }  // namespace
 
 extern "C" {
@@ -597,6 +720,48 @@ int cgnn_gcn_l0_fwd(const cgnn_tiles* t, const float* X0, int32_t F0, const floa
   else
     k_l0_fwd<false><<<l0_grid(t->num_nodes), L0THR, 0, cgnn_stream(stream)>>>(*t, X0, F0, W0, bias, P0, Y, stat_slab,
                                                                               center, w_eff, mean_offset, tl);
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
+}
+
+int cgnn_gcn_l0_agg(const cgnn_tiles* t, const float* X0, int32_t F0, const float* center, float* P0,
+                    double* moments, int64_t moments_bytes, void* stream) {
+  if (!t || F0 <= 0 || F0 > FP || t->max_tile_rows > CGNN_FUSED_MAX_ROWS) return t && F0 > FP ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (center && F0 >= FP) return CGNN_EINVAL;                      // column 7 must be spare
+  if (t->num_nodes < 0 || t->num_tiles < 0 || !moments) return CGNN_EINVAL;
+  const int grid = l0_grid(t->num_nodes);
+  CGNN_NEED_BYTES(moments, moments_bytes, (int64_t)grid * L0NM * L0NM * (int64_t)sizeof(double));
+  if (t->num_tiles > 0 && (!X0 || !P0 || !t->tile_ptr || !t->tile_blk || !t->blk_off_dst || !t->ent_dst || !t->dis))
+    return CGNN_EINVAL;
+  // (a batch without tiles still gets its -- zero -- moment sets: every set is written by every call)
+  k_l0_fwd<false, true><<<grid, L0THR, 0, cgnn_stream(stream)>>>(*t, X0, F0, nullptr, nullptr, P0, nullptr, moments,
+                                                                 center, nullptr, nullptr, cgnn_bn_tail{});
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
+}
+
+int cgnn_gcn_l0_stats(const double* moments, int32_t sets, int32_t F0, const float* W0, const float* bias,
+                      const float* center, float* w_eff, float* mean_offset, double* stat_slab,
+                      int64_t stat_slab_bytes, const cgnn_bn_tail* tail, void* stream) {
+  if (F0 <= 0 || F0 > FP) return F0 > FP ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (center && (!w_eff || !mean_offset || F0 >= FP)) return CGNN_EINVAL;   // as cgnn_gcn_l0_fwd
+  if (!center && (w_eff || mean_offset)) return CGNN_EINVAL;
+  // `sets` is a row count cgnn_l0_grid can return, and the one of this batch where the call says how many rows
+  // the batch has (a tail's count)
+  const int cus = cgnn_fused_grid();
+  if (sets < cus || sets > CGNN_L0_GRID_MULT * cus) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(stat_slab, stat_slab_bytes, (int64_t)sets * 128 * (int64_t)sizeof(double));
+  if (tail && (!tail->acc || tail->mode != 0 || !(tail->count > 0.0) || !tail->gamma || !tail->beta ||
+               !tail->running_mean || !tail->running_var || !tail->bn_out || tail->rng_n < 0 || tail->rng_n > 64 ||
+               (tail->rng_n > 0 && !tail->rng_state)))
+    return CGNN_EINVAL;
+  if (tail && (tail->count >= 9.0e15 || sets != l0_grid((int64_t)tail->count))) return CGNN_EINVAL;
+  if (!moments || !W0 || !bias) return CGNN_EINVAL;
+  const bool sums = stat_slab || tail;
+  if (!sums && !center) return CGNN_OK;               // eval mode, raw form: nothing to write
+  const cgnn_bn_tail tl = tail ? *tail : cgnn_bn_tail{};
+  k_l0_stats<<<sums ? l0_stats_grid(sets) : 1, L0STHR, 0, cgnn_stream(stream)>>>(moments, sets, F0, W0, bias, center,
+                                                                                w_eff, mean_offset, stat_slab, tl);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

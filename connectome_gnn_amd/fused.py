@@ -99,6 +99,60 @@ def _l0_center(lib, s, x0: torch.Tensor, tiles_ref, stream) -> torch.Tensor:
     return hit[1]
 
 
+# diagnostic A/B switch (never set in the product): recompute dis, P0 and its moments on every step of a kept
+# batch (cgnn_gcn_dis + cgnn_gcn_l0_fwd), as on a batch that is not kept
+_NO_L0_CACHE = bool(os.environ.get("CGNN_DIAG_NO_L0_CACHE"))
+
+
+def _kept(s) -> bool:
+    """`s` belongs to a batch that is trained on repeatedly (prepare_batch(reuse=True) -> keep_batch): what
+    layer 0 derives from the batch alone -- dis, P0 and the moments of its rows -- is kept with it."""
+    return not _NO_L0_CACHE and isinstance(s, BatchStructure) and bool(s.__dict__.get("_kept"))
+
+
+def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, stream):
+    """(P0, moments) of the factored layer 0 on a kept structure, or None = run the full kernel.  Cached as
+    `_l0_center` / `permuted_features` are: per (feature tensor, its version, shape), per centre tensor (None
+    for the raw form) and per cgnn_l0_grid (the cgnn_set_fused_grid test hook changes it).  A miss aggregates
+    again (cgnn_gcn_l0_agg) -- except while a stream is capturing, where nothing may be allocated into the
+    graph's pool and kept: the step then runs cgnn_gcn_l0_fwd."""
+    key = (x0.data_ptr(), x0._version, tuple(x0.shape), None if center is None else center.data_ptr(), sets)
+    hit = s.__dict__.get("_l0_batch")
+    if hit is not None and hit[0] == key:
+        return hit[3], hit[4]
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    p0 = torch.empty(s.num_nodes, 8, dtype=torch.float32, device=x0.device)
+    moments = torch.empty(sets, 81, dtype=torch.float64, device=x0.device)
+    with _lib.timed("cgnn_gcn_l0_agg"):
+        _lib.check(lib.cgnn_gcn_l0_agg(tiles_ref, _lib.ptr(x0), x0.shape[1], _lib.ptr(center), _lib.ptr(p0),
+                                       _lib.ptr(moments), _lib.nbytes(moments), stream), "cgnn_gcn_l0_agg")
+    # (x0 and the centre are held so that their addresses stay theirs while the entry lives)
+    s.__dict__["_l0_batch"] = (key, x0, center, p0, moments)
+    return p0, moments
+
+
+def keep_batch(model, s, x0: torch.Tensor) -> None:
+    """prepare_batch(reuse=True): mark the structure the encoder will run on as kept and, when the narrow
+    layer 0 applies, fill its batch constants now -- eagerly, outside any capture."""
+    if not isinstance(s, BatchStructure) or s.num_nodes == 0:
+        return
+    s.__dict__["_kept"] = True
+    if _NO_L0_CACHE or x0.requires_grad or not x0.is_cuda:
+        return
+    lib = _lib.load()
+    fmeta = s.fused_meta(MAX_ROWS, lib.cgnn_fused_grid())
+    with _lib.device_guard(x0.device):
+        dis = s.gcn_dis(fmeta)
+        if not _narrow0(len(model.convs), x0.shape[1]):
+            return
+        x0 = x0.detach().contiguous()
+        tp = ctypes.byref(_tiles_struct(s, fmeta, dis))
+        sp = _lib.stream_ptr(x0.device)
+        center = _l0_center(lib, s, x0, tp, sp) if (x0.shape[1] < 8 and bn_stage.sync_group_of(model) is None) else None
+        _l0_batch_constants(lib, s, x0, center, tp, lib.cgnn_l0_grid(s.num_nodes), sp)
+
+
 class _Ctx:
     """Everything of one forward pass that backward needs and autograd must not track."""
     __slots__ = ("s", "meta", "dis", "tiles", "grid", "ys", "bns", "masks", "p", "x0", "f0", "p0", "count_dev", "fsum", "l0src", "l0keep",
@@ -162,7 +216,8 @@ class FusedGCNEncode(torch.autograd.Function):
         nn_, B = s.num_nodes, s.num_graphs
         grid = lib.cgnn_fused_grid()
         fmeta = s.fused_meta(MAX_ROWS, grid)      # static per batch (cached on the structure)
-        dis = s.gcn_dis(fmeta)                    # the normalisation itself: every forward
+        # the normalisation itself: every forward -- on a kept batch a batch constant, like the CSR
+        dis = s.gcn_dis(fmeta, fresh=True) if (_NO_L0_CACHE and isinstance(s, BatchStructure)) else s.gcn_dis(fmeta)
         tiles = _tiles_struct(s, fmeta, dis)
         tp = ctypes.byref(tiles)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -218,8 +273,15 @@ class FusedGCNEncode(torch.autograd.Function):
                     # (Under sync-BN the ranks' constants would differ: raw form there.)
                     y = None
                     f0 = int(x0.shape[1])
-                    p0 = torch.empty(nn_, 8, **f32)
                     center = _l0_center(lib, s, x0, tp, st()) if (f0 < 8 and sync_group is None) else None
+                    slab_rows = lib.cgnn_l0_grid(nn_)
+                    # kept batch: P0 and the per-workgroup moments of its rows are batch constants (aggregated
+                    # once, cgnn_gcn_l0_agg); the step only turns the moments into this step's sums
+                    # (cgnn_gcn_l0_stats).  Never for a differentiable x0 (a fresh gather per pass).
+                    const = None
+                    if _kept(s) and not ctx.needs_input_grad[0] and not x0.requires_grad:
+                        const = _l0_batch_constants(lib, s, x0, center, tp, slab_rows, st())
+                    p0 = const[0] if const is not None else torch.empty(nn_, 8, **f32)
                     if center is not None:
                         w_eff, mean_off = torch.empty(HID, f0 + 1, **f32), torch.empty(HID, **f32)
                         l0src = _lib.CgnnL0Src(_lib.ptr(p0), _lib.ptr(w_eff), _lib.ptr(_zeros(dev)), f0 + 1)
@@ -228,13 +290,19 @@ class FusedGCNEncode(torch.autograd.Function):
                         w_eff = mean_off = None
                         l0src = _lib.CgnnL0Src(_lib.ptr(p0), _lib.ptr(w), _lib.ptr(b), f0)
                         l0keep = (w, b, None, None)
-                    slab_rows = lib.cgnn_l0_grid(nn_)
                     slab = torch.empty(slab_rows, 128, dtype=torch.float64, device=dev) if (training and tail is None) else None
-                    with _lib.timed("cgnn_gcn_l0_fwd"):
-                        _lib.check(lib.cgnn_gcn_l0_fwd(
-                            tp, _lib.ptr(x0), f0, _lib.ptr(w), _lib.ptr(b), _lib.ptr(p0), None, _lib.ptr(slab), _lib.nbytes(slab),
-                            _lib.ptr(center), _lib.ptr(w_eff), _lib.ptr(mean_off),
-                            ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_l0_fwd")
+                    if const is not None:
+                        with _lib.timed("cgnn_gcn_l0_stats"):
+                            _lib.check(lib.cgnn_gcn_l0_stats(
+                                _lib.ptr(const[1]), slab_rows, f0, _lib.ptr(w), _lib.ptr(b), _lib.ptr(center),
+                                _lib.ptr(w_eff), _lib.ptr(mean_off), _lib.ptr(slab), _lib.nbytes(slab),
+                                ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_l0_stats")
+                    else:
+                        with _lib.timed("cgnn_gcn_l0_fwd"):
+                            _lib.check(lib.cgnn_gcn_l0_fwd(
+                                tp, _lib.ptr(x0), f0, _lib.ptr(w), _lib.ptr(b), _lib.ptr(p0), None, _lib.ptr(slab), _lib.nbytes(slab),
+                                _lib.ptr(center), _lib.ptr(w_eff), _lib.ptr(mean_off),
+                                ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_l0_fwd")
                 elif l == 0:
                     with _lib.timed("cgnn_gcn_fused_fwd_first"):
                         _lib.check(lib.cgnn_gcn_fused_fwd_first(

@@ -256,7 +256,9 @@ class _ConnectomeModel(nn.Module):
         s = batch.structure()
         if reuse:
             self._prepare_reused(batch, s)
-            if getattr(s, "__dict__", {}).get("_degree_twin") is not None:
+            twin = getattr(s, "__dict__", {}).get("_degree_twin")
+            if twin is not None:
+                self._keep_batch(twin, twin.permuted_features(batch.node_features))
                 return                                  # the encoder runs on the twin's metadata
         if self.storage == "fp16":
             from . import gcn_half_path
@@ -269,10 +271,16 @@ class _ConnectomeModel(nn.Module):
         elif hasattr(s, "band_ops"):
             # large graphs: the dense fragments of the operator as matrix-core operands (band_aggregate.hip)
             s.band_ops("gcn" if self._relu_after_bn else "sage", self._norm(s))
-        self._try_fused(batch, s)
+        if self._try_fused(batch, s) and reuse:
+            self._keep_batch(s, batch.node_features)
 
     def _try_fused(self, batch, structure) -> bool:
         return False
+
+    def _keep_batch(self, structure, x0) -> None:
+        """prepare_batch(reuse=True): `structure` (the twin when there is one) and the node features in its
+        order are what the one-node encoder will run on, again and again; an encoder that keeps per-batch
+        constants fills them here (the per-tile GCN path: fused.keep_batch)."""
 
     def _prepare_reused(self, batch, structure) -> None:
         """prepare_batch(reuse=True): the one-node encoders over LDS tiles (per-tile GCN, wide GCN,
@@ -353,6 +361,11 @@ class GCNConnectome(_ConnectomeModel):
         if why is not None and gcn_wide_path.eligible(self, batch, structure) is None:
             self._fused_kind, why = "wide", None
         return self._decide(why)
+
+    def _keep_batch(self, structure, x0) -> None:
+        if getattr(self, "_fused_kind", None) == "tile" and self.impl != "layered" and self.storage != "fp16":
+            from . import fused
+            fused.keep_batch(self, structure, x0)
 
     def _fused_encode(self, batch, structure):
         from . import fused, gcn_half_path, gcn_wide_path

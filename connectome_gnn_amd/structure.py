@@ -401,8 +401,16 @@ class BatchStructure:
         return (width % 64 == 0 and self.block_diagonal and self.num_nodes > 0
                 and self.max_nodes_per_graph <= TILED_MAX_ROWS)
 
-    def gcn_dis(self, meta: FusedMeta) -> torch.Tensor:
-        """dis = (source-side degree + self-loop + 1e-8)^-1/2, models.py:97-105; every step."""
+    def gcn_dis(self, meta: FusedMeta, fresh: bool = False) -> torch.Tensor:
+        """dis = (source-side degree + self-loop + 1e-8)^-1/2, models.py:97-105; every step -- except on a
+        structure marked kept (``model.prepare_batch(batch, reuse=True)``), where it is a batch constant like
+        the CSR: a function of ``meta.w_src``, which is itself built once per batch.  Computed at the first
+        request outside a stream capture and returned from then on; fresh=True recomputes regardless."""
+        kept = not fresh and self.__dict__.get("_kept")
+        if kept:
+            hit = self.__dict__.get("_dis")
+            if hit is not None and hit[0] is meta:
+                return hit[1]
         lib = _lib.load()
         dev = self.rowptr_dst.device
         dis = torch.empty(self.num_nodes, dtype=torch.float32, device=dev)
@@ -410,4 +418,6 @@ class BatchStructure:
             _lib.check(lib.cgnn_gcn_dis(_lib.ptr(meta.w_src), _lib.ptr(self.rowptr_src),
                                         self.num_nodes, _lib.ptr(dis), _lib.stream_ptr()),
                        "cgnn_gcn_dis")
+        if kept and not torch.cuda.is_current_stream_capturing():
+            self.__dict__["_dis"] = (meta, dis)       # (never a tensor from a graph's pool)
         return dis

@@ -676,8 +676,8 @@ int cgnn_band_aggregate_f32(const void* bfrag, const int32_t* bstep, const int32
  *     rng_n as there (the step's dropout words, refreshed by the tail; NULL / 0 = none);
  *   mode 1 (sums of a backward layer): the arithmetic of cgnn_bn_bwd_stats_finalize -- dgamma, dbeta
  *     float[64], bwc float[2*64], zero_coef as there.
- * Passed as the last argument of cgnn_gcn_l0_fwd (mode 0; factored layer 0: the centred form's mean offset
- * is the kernel's own), cgnn_gcn_fused_fwd (mode 0) and cgnn_gcn_fused_bwd (mode 1, the sums of the layer
+ * Passed as the last argument of cgnn_gcn_l0_fwd / cgnn_gcn_l0_stats (mode 0; factored layer 0: the centred
+ * form's mean offset is the kernel's own), cgnn_gcn_fused_fwd (mode 0) and cgnn_gcn_fused_bwd (mode 1, the sums of the layer
  * BELOW); NULL = the slab protocol.  With a tail the corresponding slab argument may be NULL. */
 #define CGNN_BN_ACC_BYTES 16448
 typedef struct cgnn_bn_tail {
@@ -811,6 +811,26 @@ int cgnn_gcn_l0_fwd(const cgnn_tiles* t, const float* X0, int32_t F0, const floa
 int cgnn_gcn_l0_bwd(const float* dZ, const float* Y, const cgnn_l0src* l0, const float* bn,
                     const float* bwc, const float* P0, int64_t num_nodes, float* dW_slab, int64_t dW_slab_bytes,
                     double* db_slab, int64_t db_slab_bytes, const float* center, void* stream);
+/* The factored forward (Y == NULL) in two halves, for a batch that is kept and trained on repeatedly: what
+ * depends on the batch alone, once, and what depends on W0 / bias, per step.  Together they write, bit for
+ * bit, what cgnn_gcn_l0_fwd writes.
+ *   cgnn_gcn_l0_agg    P0 (P0' with `center`, as above) and, per workgroup of its cgnn_l0_grid(num_nodes)
+ *                      grid, the 9 x 9 fp64 second moments of the P0 rows it aggregated (columns p_0..p_7
+ *                      and 1, row-major): moments[cgnn_l0_grid][81], moments_bytes >= grid * 81 * 8.
+ *                      Every set is written by every call.
+ *   cgnn_gcn_l0_stats  moments -> the 128 sums (sum y | sum y^2) of every set, with the W0 / bias of this
+ *                      step: to stat_slab[sets][128] (stat_slab_bytes >= sets * 128 * 8; the rows
+ *                      cgnn_gcn_l0_fwd writes) or through `tail` (one atomic pair per column and workgroup of
+ *                      a grid of at most cgnn_fused_grid() workgroups; the accumulator ends as after
+ *                      cgnn_gcn_l0_fwd).  Writes w_eff and mean_offset as cgnn_gcn_l0_fwd does (`center` as
+ *                      given to cgnn_gcn_l0_agg); with neither a slab nor a tail (eval mode) only those.
+ *                      `sets` must be cgnn_l0_grid(num_nodes) of the batch: a value outside cgnn_l0_grid's
+ *                      range, or with a tail one that is not cgnn_l0_grid(tail->count), is CGNN_EINVAL. */
+int cgnn_gcn_l0_agg(const cgnn_tiles* t, const float* X0, int32_t F0, const float* center, float* P0,
+                    double* moments, int64_t moments_bytes, void* stream);
+int cgnn_gcn_l0_stats(const double* moments, int32_t sets, int32_t F0, const float* W0, const float* bias,
+                      const float* center, float* w_eff, float* mean_offset, double* stat_slab,
+                      int64_t stat_slab_bytes, const cgnn_bn_tail* tail, void* stream);
 /* Node-feature gradient of the narrow layer 0 (ROI saliency).  With Y0 = (A_hat X0) W0^T + b:
  *     G0  = dY0 W0          [Nn, 8] fp32, columns >= F0 zero: the 64 -> F0 narrowing of dY0 = BatchNorm'(dZ0)
  *     dX0 = A_hat^T G0      [Nn, F0]: one narrow transposed aggregate over the source-side blocked-ELL
