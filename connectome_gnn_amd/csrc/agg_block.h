@@ -1,5 +1,6 @@
 // agg_block.h -- LDS-tile neighbour aggregation shared by the fused GCN kernels
-// (fused_gcn.hip) and the tiled aggregate (aggregate_tiled.hip).  gfx950, wave64.
+// (fused_gcn.hip) and the tiled aggregate (aggregate_tiled.hip); the readout (fused_readout.hip) takes its
+// 16-byte accessors from here.  gfx950, wave64.
 //
 // A tile = a run of whole graphs, [rows][64] fp32 in LDS.  Each wave aggregates 16-row blocks:
 // lane (q, j) owns rows 4q..4q+3 of the block and columns 4j..4j+3.  The block's blocked-ELL

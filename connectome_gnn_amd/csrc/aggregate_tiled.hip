@@ -178,18 +178,12 @@ extern "C" int cgnn_aggregate_tiled_f32(const cgnn_tiles* t, int32_t flags, cons
                                         int64_t ldx, int32_t F, const float* pre,
                                         const float* post, const float* bias, const float* Yadd,
                                         int64_t ldadd, float* Y, int64_t ldy, void* stream) {
-  if (!t || t->num_nodes < 0 || t->num_tiles < 0 || F <= 0 || ldx < F || ldy < F) return CGNN_EINVAL;
-  if (Yadd && ldadd < F) return CGNN_EINVAL;
-  if (F % 64 || ldx % 4 || ldy % 4 || (Yadd && ldadd % 4) || t->max_tile_rows > TA_MAXR)
-    return CGNN_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
-       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(Yadd)) & 15)
-    return CGNN_EUNSUPPORTED;
-  if (t->num_nodes == 0 || t->num_tiles == 0) return CGNN_OK;
-  const bool tr = flags & CGNN_AGG_TRANSPOSED;
-  if (!X || !Y || !t->tile_ptr || !t->tile_blk || !(tr ? t->ent_src : t->ent_dst) ||
-      !(tr ? t->blk_off_src : t->blk_off_dst))
-    return CGNN_EINVAL;
+  bool launch;
+  const int rc = cgnn_check_agg_tiled(t, flags, F, {ldx, ldy, Yadd ? ldadd : (int64_t)F},
+                                      reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
+                                          reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(Yadd),
+                                      X, Y, TA_MAXR, 4, &launch);
+  if (!launch) return rc;
   k_agg_tiled<<<cgnn_fused_grid(), TA_THR, 0, cgnn_stream(stream)>>>(*t, flags, X, ldx, F / 64, pre,
                                                                      post, bias, Yadd, ldadd, Y, ldy, AggPre{});
   CGNN_CHECK_LAUNCH();
@@ -207,17 +201,14 @@ extern "C" int cgnn_aggregate_tiled_bn_f32(const cgnn_tiles* t, int32_t flags, c
                                            float p_drop, uint64_t seed, const uint32_t* seed_dev,
                                            uint8_t* mask_out, float* Xout, int64_t ldxo,
                                            void* stream) {
-  if (!t || t->num_nodes < 0 || t->num_tiles < 0 || F <= 0 || ldz < F || ldy < F || ldxo < F) return CGNN_EINVAL;
-  if (p_drop < 0.f || p_drop >= 1.f || !coef || !Xout) return CGNN_EINVAL;
-  if (F % 64 || ldz % 4 || ldy % 4 || ldxo % 4 || t->max_tile_rows > TA_MAXR) return CGNN_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(Z) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(bias) |
-       reinterpret_cast<uintptr_t>(Xout) | reinterpret_cast<uintptr_t>(coef)) & 15)
-    return CGNN_EUNSUPPORTED;
-  if (t->num_nodes == 0 || t->num_tiles == 0) return CGNN_OK;
-  const bool tr = flags & CGNN_AGG_TRANSPOSED;
-  if (!Z || !Y || !t->tile_ptr || !t->tile_blk || !(tr ? t->ent_src : t->ent_dst) ||
-      !(tr ? t->blk_off_src : t->blk_off_dst))
-    return CGNN_EINVAL;
+  if (p_drop < 0.f || p_drop >= 1.f || !coef || !Xout) return CGNN_EINVAL;   // before any CGNN_EUNSUPPORTED
+  bool launch;
+  const int rc = cgnn_check_agg_tiled(t, flags, F, {ldz, ldy, ldxo},
+                                      reinterpret_cast<uintptr_t>(Z) | reinterpret_cast<uintptr_t>(Y) |
+                                          reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(Xout) |
+                                          reinterpret_cast<uintptr_t>(coef),
+                                      Z, Y, TA_MAXR, 4, &launch);
+  if (!launch) return rc;
   AggPre pr;
   pr.coef = coef;
   pr.relu = relu;

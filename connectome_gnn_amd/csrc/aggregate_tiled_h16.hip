@@ -187,16 +187,12 @@ extern "C" int cgnn_aggregate_tiled_f16(const cgnn_tiles* t, int32_t flags, cons
                                         int64_t ldx, int32_t F, const float* pre,
                                         const float* post, const float* bias, void* Y,
                                         int64_t ldy, void* stream) {
-  if (!t || t->num_nodes < 0 || t->num_tiles < 0 || F <= 0 || ldx < F || ldy < F) return CGNN_EINVAL;
-  if (F % 64 || ldx % 8 || ldy % 8 || t->max_tile_rows > H_MAXR) return CGNN_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
-       reinterpret_cast<uintptr_t>(bias)) & 15)
-    return CGNN_EUNSUPPORTED;
-  if (t->num_nodes == 0 || t->num_tiles == 0) return CGNN_OK;
-  const bool tr = flags & CGNN_AGG_TRANSPOSED;
-  if (!X || !Y || !t->tile_ptr || !t->tile_blk || !(tr ? t->ent_src : t->ent_dst) ||
-      !(tr ? t->blk_off_src : t->blk_off_dst))
-    return CGNN_EINVAL;
+  bool launch;
+  const int rc = cgnn_check_agg_tiled(t, flags, F, {ldx, ldy},
+                                      reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
+                                          reinterpret_cast<uintptr_t>(bias),
+                                      X, Y, H_MAXR, 8, &launch);
+  if (!launch) return rc;
   k_agg_tiled_h16<<<cgnn_fused_grid(), H_THR, 0, cgnn_stream(stream)>>>(
       *t, flags, static_cast<const __half*>(X), ldx, F / 64, pre, post, bias,
       static_cast<__half*>(Y), ldy);

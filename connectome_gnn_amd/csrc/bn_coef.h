@@ -1,5 +1,5 @@
 // bn_coef.h -- BatchNorm1d's per-column finalisation, once for every kernel that does it: the
-// one-block-per-channel kernels (fused_gcn.hip), the width-N kernels of the layered path
+// one-block-per-channel kernels (fused_support.hip, fused_readout.hip), the width-N kernels of the layered path
 // (elementwise.hip) and the last workgroup's tail of the tile kernels (bn_tail.h).  Each expression is
 // written as the earlier copies had it, so contraction into FMAs -- and with it every bit of the
 // coefficient blocks -- is what it was.

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "../../include/cgnn.h"
 
 #define CGNN_WAVE 64
@@ -43,6 +44,31 @@ static inline int cgnn_check_cohort(int64_t S, int32_t n) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
   if (S < 0 || S >= kLimit || n <= 0) return CGNN_EINVAL;
   if ((int64_t)n * n >= kLimit || S * (int64_t)n >= kLimit) return CGNN_EINVAL;
+  return CGNN_OK;
+}
+
+// What the tiled aggregations (aggregate_tiled.hip, aggregate_tiled_h16.hip) check before they launch, in the
+// order their callers rely on: bad values (CGNN_EINVAL); then shapes the build does not cover (CGNN_EUNSUPPORTED:
+// F not a multiple of 64, a row stride not a multiple of ld_mult elements, tiles of more than max_rows rows, a
+// pointer that is not 16-byte aligned); then an empty batch (CGNN_OK with *launch = false); then the pointers a
+// launch dereferences (CGNN_EINVAL).  lds: the row strides of the [*, F] arrays; ptr_bits: the OR of every
+// pointer accessed 16 bytes at a time; X, Y: operand and result.
+static inline int cgnn_check_agg_tiled(const cgnn_tiles* t, int32_t flags, int32_t F, std::initializer_list<int64_t> lds,
+                                       uintptr_t ptr_bits, const void* X, const void* Y, int max_rows, int ld_mult,
+                                       bool* launch) {
+  *launch = false;
+  if (!t || t->num_nodes < 0 || t->num_tiles < 0 || F <= 0) return CGNN_EINVAL;
+  for (const int64_t ld : lds)
+    if (ld < F) return CGNN_EINVAL;
+  if (F % 64 || t->max_tile_rows > max_rows || (ptr_bits & 15)) return CGNN_EUNSUPPORTED;
+  for (const int64_t ld : lds)
+    if (ld % ld_mult) return CGNN_EUNSUPPORTED;
+  if (t->num_nodes == 0 || t->num_tiles == 0) return CGNN_OK;
+  const bool tr = flags & CGNN_AGG_TRANSPOSED;
+  if (!X || !Y || !t->tile_ptr || !t->tile_blk || !(tr ? t->ent_src : t->ent_dst) ||
+      !(tr ? t->blk_off_src : t->blk_off_dst))
+    return CGNN_EINVAL;
+  *launch = true;
   return CGNN_OK;
 }
 

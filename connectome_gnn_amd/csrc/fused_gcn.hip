@@ -1,29 +1,35 @@
 // fused_gcn.hip -- per-tile fused GCN layer kernels for gfx950 (hidden = 64, fp32).
 //
-// Reference arithmetic replaced: GCNLayer.forward (models.py:84-114), the BatchNorm1d / ReLU /
-// dropout chain and mean-pool of GCNConnectome.encode (models.py:203-211), and autograd's
-// backward of all of it.  See include/cgnn.h ("FUSED PER-TILE GCN PATH") for the contract.
+// Reference arithmetic replaced: GCNLayer.forward (models.py:84-114) with the BatchNorm1d / ReLU /
+// dropout chain of GCNConnectome.encode (models.py:203-211) folded into the next layer's prologue, and
+// autograd's backward of all of it.  See include/cgnn.h ("FUSED PER-TILE GCN PATH") for the contract.
+// The readout is in fused_readout.hip; the slab reductions, the BatchNorm finalisers and the grid size
+// are in fused_support.hip.
 //
-// Execution shape (one persistent workgroup = 8 waves per CU, one CU = one tile at a time):
+// Three kernels, all persistent (one workgroup per CU, one tile of <= 384 rows at a time), all with the
+// tile [<=384 rows][64] fp32 (96 KB) in LDS and the same two phases:
 //
-//   LDS  tile [<=384 rows][64] fp32  (96 KB)  the layer input (fwd) / dY (bwd) of the tile
-//        stg  [8 waves][16][68] fp32 (34 KB)  per-wave 16-row block handed to the matrix core
-//        Wl   [64][64] fp32          (16 KB)  projection weight (backward only)
+//   phase A  fill the tile, rows pre-scaled by dis[row] (A_hat X = dis * (A_w + I)(dis * X)).
+//   phase B  each wave owns 16-row blocks.  Lane group q (16 lanes x float4 = one 64-wide row) owns
+//            rows 4q..4q+3 of the block.  The block's blocked-ELL entries (byte offset of the
+//            neighbour's row in the tile, raw edge weight; self-loop last; zero-weight padding up to
+//            the block's width) are fetched one block ahead with one coalesced 32-byte load per lane,
+//            kept in registers and broadcast inside the 16-lane group with DPP row_newbcast; neighbour
+//            rows come straight out of the LDS tile with ds_read_b128 (agg_block.h).  Rows are scaled
+//            by dis again when they leave the aggregation, so the metadata is static per batch.
 //
-//   phase A  all 512 threads stream the tile from HBM with 16-byte loads, apply the fused
-//            elementwise prologue (BatchNorm-apply+ReLU+dropout, or BatchNorm-backward), and
-//            write it to LDS.
-//   phase B  each wave owns 16-row blocks.  Lane group q (16 lanes x float4 = one 64-wide row)
-//            owns rows 4q..4q+3 of the block.  The block's blocked-ELL entries (byte offset of
-//            the neighbour's row in the tile, raw edge weight; self-loop last; zero-weight
-//            padding up to the block's width) are fetched one block ahead with one coalesced
-//            32-byte load per lane, kept in registers and broadcast inside the 16-lane group
-//            with DPP row_newbcast; neighbour rows come straight out of the LDS tile with
-//            ds_read_b128.  The finished block goes through `stg` to v_mfma_f32_16x16x4_f32
-//            (exact fp32) and the epilogue (bias / BatchNorm statistics / ReLU' * dropout')
-//            runs on the accumulators.  The symmetric normalisation is applied as
-//            dis[d] * sum_e w_e * (dis[s_e] * x[s_e]): rows are scaled by dis when staged and
-//            again when they leave the aggregation, so the metadata is static per batch.
+//   k_gcn_fwd_first  layer 0, F0 <= 16 input columns, 8 waves.  Phase A projects first: T = X0 W0^T on
+//                    the fp32 matrix core (v_mfma_f32_16x16x4_f32, W0 in 16 registers), dis * T into the
+//                    tile.  Phase B stores dis * agg + bias and the fp64 BatchNorm sums from registers.
+//   k_gcn_fwd_pf     layers l > 0, projection first, 12 waves.  Phase A rebuilds X =
+//                    drop(relu(BatchNorm(Y_prev))) in matrix-core operand layout and multiplies by W^T
+//                    as exactly split bf16 products; phase B as above.  See the comment at the kernel.
+//   k_gcn_bwd        every layer's backward, 8 waves.  Phase A streams dY = BatchNorm'(dZ) (or the
+//                    readout's gradient, POOLIN) into the tile; phase B forms dT = A_hat^T dY per block,
+//                    hands it through `stg` [8 waves][16][68] fp32 (34 KB) to the matrix core for
+//                    dW += dT^T X and dX = dT W (split W panel in LDS, 24 KB), and applies
+//                    ReLU' * dropout' and the BatchNorm-backward sums on the accumulators.  FIRST: layer
+//                    0, dW0 only.
 //
 // The MFMA reduction index is permuted freely (lane group kk supplies k = 16*kk + s) so that
 // every operand fragment is a run of 16-byte LDS/register accesses; output tile tj holds the
@@ -36,6 +42,7 @@
 #include "bn_coef.h"
 #include "bn_tail.h"
 #include "drop_ew.h"
+#include "fused_common.h"
 #include "l0src.h"
 
 // streamed operands / results of the tile kernels (each read or written once per launch)
@@ -68,26 +75,10 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int HID = CGNN_FUSED_HIDDEN;      // 64
 constexpr int NWAVE = 8;
 constexpr int NTHR = NWAVE * 64;            // 512
 constexpr int SLD = 68;                     // staging row stride (floats)
 constexpr int STG_FLOATS = 16 * SLD;        // per wave
-
-// x = drop(relu(a*y + b)); returns x, and the combined (z>0 & keep) factor per component in f.
-__device__ __forceinline__ float4 act4(const float4& y, const float4& a, const float4& b,
-                                        uint32_t keep, float scale, float4& f) {
-  float4 z, x;
-  z.x = fmaf(a.x, y.x, b.x); z.y = fmaf(a.y, y.y, b.y);
-  z.z = fmaf(a.z, y.z, b.z); z.w = fmaf(a.w, y.w, b.w);
-  f.x = (z.x > 0.f && (keep & 1u)) ? scale : 0.f;
-  f.y = (z.y > 0.f && (keep & 2u)) ? scale : 0.f;
-  f.z = (z.z > 0.f && (keep & 4u)) ? scale : 0.f;
-  f.w = (z.w > 0.f && (keep & 8u)) ? scale : 0.f;
-  x.x = z.x * f.x; x.y = z.y * f.y; x.z = z.z * f.z; x.w = z.w * f.w;
-  return x;
-}
-
 
 // Reduce per-lane fp64 column partials (lane (q,j): columns 4j..4j+3) over the workgroup and
 // write slab_row[0..63] (= s1) and slab_row[64..127] (= s2).  `red` >= 8*128 doubles of LDS.
@@ -125,63 +116,32 @@ constexpr int FWD_G = CGNN_FWD_G;
 constexpr int BWD_G = CGNN_BWD_G;
 
 // ==========================================================================================
-// forward
+// forward, first layer (F0 <= 16 input columns)
 // ==========================================================================================
-template <int MAXR, bool FIRST>
-__global__ void __launch_bounds__(NTHR) k_gcn_fwd(
-    cgnn_tiles t, const float* __restrict__ Xin, int F0, const float* __restrict__ bn_prev,
-    DropCfg drop_in, int use_drop, uint8_t* __restrict__ mask_out, const float* __restrict__ W,
+// Y0 = A_hat (X0 W0^T) + b0, projection first: the 16-wide input is projected to 64 columns on the
+// matrix core while the tile is filled, so phase B is the aggregation and the epilogue alone.
+template <int MAXR>
+__global__ void __launch_bounds__(NTHR) k_gcn_fwd_first(
+    cgnn_tiles t, const float* __restrict__ Xin, int F0, const float* __restrict__ W,
     const float* __restrict__ bias, float* __restrict__ Y, double* __restrict__ stat_slab) {
-  const DropCfg drop = drop_resolve(drop_in);
   __shared__ __attribute__((aligned(16))) float tile[MAXR * HID];
-  __shared__ __attribute__((aligned(16))) float stg_all[NWAVE * STG_FLOATS];
   __shared__ float disl[MAXR];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, j = lane & 15;
-  float* stg = stg_all + wave * STG_FLOATS;
   const uint4* ent = static_cast<const uint4*>(t.ent_dst);
 
-  // B operand of the projection: B[k][col] = W[col][k], lane (kk=q, jj=j), tile tj <-> col 4j+tj.
-  //   first  : k = 4s + q < F0 (F0 <= 16 -> 4 k-steps), 16 registers
-  //   generic: k = 16q + s; W^T lives in LDS (one conflict-free ds_read_b128 per k-step) so that
-  //            the registers can hold the NEXT tile's rows while this tile is being processed
-  __shared__ __attribute__((aligned(16))) float Wt[FIRST ? 4 : HID * HID];
+  // B operand of the projection: B[k][col] = W[col][k], lane (kk=q, jj=j), tile tj <-> col 4j+tj,
+  // k = 4s + q < F0 (F0 <= 16 -> 4 k-steps), 16 registers
   float wreg[4][4];
-  if (FIRST) {
 #pragma unroll
-    for (int tj = 0; tj < 4; ++tj)
+  for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int k = 4 * s + q;
-        wreg[tj][s] = k < F0 ? W[(4 * j + tj) * F0 + k] : 0.f;
-      }
-  } else {
-    for (int i = threadIdx.x; i < HID * HID; i += NTHR) Wt[(i & 63) * HID + (i >> 6)] = W[i];
-  }
+    for (int s = 0; s < 4; ++s) {
+      const int k = 4 * s + q;
+      wreg[tj][s] = k < F0 ? W[(4 * j + tj) * F0 + k] : 0.f;
+    }
   const float4 bias4 = ld4(bias + 4 * j);
-  float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), pb = pa;
-  if (!FIRST) {
-    pa = ld4(bn_prev + 4 * j);
-    pb = ld4(bn_prev + HID + 4 * j);
-  }
   double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
   CGNN_STAMP_DECL
-  // cross-tile prefetch registers: row (tid>>4) + 32u, columns 4j..4j+3 of the next tile
-  constexpr int PF = FIRST ? 1 : MAXR / 32;
-  float4 pfy[PF];
-  float pfd[PF];
-  if (!FIRST && (int)blockIdx.x < t.num_tiles) {
-    const int nb2 = t.tile_ptr[blockIdx.x], nn2 = t.tile_ptr[blockIdx.x + 1] - nb2;
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int row = (threadIdx.x >> 4) + 32 * u;
-      pfy[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      pfd[u] = 0.f;
-      if (row < nn2) {
-        pfy[u] = ld4(Xin + (int64_t)(nb2 + row) * HID + 4 * j);
-        pfd[u] = t.dis[nb2 + row];
-      }
-    }
-  }
 
   for (int tid = blockIdx.x; tid < t.num_tiles; tid += gridDim.x) {
     CGNN_STAMP_BEGIN()
@@ -206,76 +166,36 @@ __global__ void __launch_bounds__(NTHR) k_gcn_fwd(
 
     // ---------------------------------------------------------------- phase A: fill the tile
     // (rows are pre-scaled by dis[row]: A_hat X = dis * (A_w + I)(dis * X))
-    if (FIRST) {
-      // T = X0 W0^T on the matrix core, written straight into the tile (all loads first).
-      for (int r = threadIdx.x; r < nblk * 16; r += NTHR) disl[r] = r < n ? t.dis[base + r] : 0.f;
-      for (int b = wave; b < nblk; b += NWAVE) {
-        const int arow = 16 * b + j;                    // A operand: row i = j, k-slot kk = q
-        f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-        float av[4], dv[4];
+    // T = X0 W0^T on the matrix core, written straight into the tile (all loads first).
+    for (int r = threadIdx.x; r < nblk * 16; r += NTHR) disl[r] = r < n ? t.dis[base + r] : 0.f;
+    for (int b = wave; b < nblk; b += NWAVE) {
+      const int arow = 16 * b + j;                    // A operand: row i = j, k-slot kk = q
+      f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      float av[4], dv[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * s + q;
-          av[s] = (arow < n && k < F0) ? Xin[(int64_t)(base + arow) * F0 + k] : 0.f;
-          const int row = 16 * b + 4 * q + s;
-          dv[s] = row < n ? t.dis[base + row] : 0.f;
+      for (int s = 0; s < 4; ++s) {
+        const int k = 4 * s + q;
+        av[s] = (arow < n && k < F0) ? Xin[(int64_t)(base + arow) * F0 + k] : 0.f;
+        const int row = 16 * b + 4 * q + s;
+        dv[s] = row < n ? t.dis[base + row] : 0.f;
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        if (4 * s < F0) {
+#pragma unroll
+          for (int tj = 0; tj < 4; ++tj)
+            acc[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], wreg[tj][s], acc[tj], 0, 0, 0);
         }
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-          if (4 * s < F0) {
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-              acc[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], wreg[tj][s], acc[tj], 0, 0, 0);
-          }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          st4(tile + (16 * b + 4 * q + r) * HID + 4 * j,
-              make_float4(acc[0][r] * dv[r], acc[1][r] * dv[r], acc[2][r] * dv[r], acc[3][r] * dv[r]));
-      }
-    } else {
-      // the tile's rows were requested a whole phase B ago (cross-tile register prefetch)
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int row = (threadIdx.x >> 4) + 32 * u;
-        if (row < nblk * 16) {
-          float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (row < n) {
-            uint32_t keep = 0xFu;
-            if (use_drop) {
-              keep = drop_bits(drop, (uint32_t)(base + row) * 16u + (uint32_t)j);
-              if (mask_out) mask_out[(int64_t)(base + row) * 16 + j] = (uint8_t)keep;
-            }
-            float4 f;
-            x = scale4(act4(pfy[u], pa, pb, keep, drop.scale, f), pfd[u]);
-          }
-          st4(tile + row * HID + 4 * j, x);
-          if (j == 0) disl[row] = pfd[u];
-        }
-      }
+      for (int r = 0; r < 4; ++r)
+        st4(tile + (16 * b + 4 * q + r) * HID + 4 * j,
+            make_float4(acc[0][r] * dv[r], acc[1][r] * dv[r], acc[2][r] * dv[r], acc[3][r] * dv[r]));
     }
     __syncthreads();
-    if (!FIRST) {
-      // request the NEXT tile's rows now; they land while this tile is aggregated/projected
-      const int nxt = tid + gridDim.x;
-      if (nxt < t.num_tiles) {
-        const int nb2 = t.tile_ptr[nxt], nn2 = t.tile_ptr[nxt + 1] - nb2;
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-          const int row = (threadIdx.x >> 4) + 32 * u;
-          pfy[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-          pfd[u] = 0.f;
-          if (row < nn2) {
-            pfy[u] = ld4(Xin + (int64_t)(nb2 + row) * HID + 4 * j);
-            pfd[u] = t.dis[nb2 + row];
-          }
-        }
-      }
-    }
     CGNN_STAMP(1)      // phase A + barrier
 
-    // ------------------------------------------------- phase B: aggregate (+ project) blocks
+    // ------------------------------------------------- phase B: aggregate blocks
     for (int b = wave; b < nblk; b += NWAVE) {
-      f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
       ++bk;
       const int off1 = bk == 1 ? boff[1] : boff[2], width1 = bk == 1 ? bwid[1] : bwid[2];
       CGNN_STAMP(2)
@@ -284,61 +204,20 @@ __global__ void __launch_bounds__(NTHR) k_gcn_fwd(
       CGNN_STAMP(3)    // aggregation
       if (b + NWAVE < nblk) pre = meta_issue<true>(ent + (off1 >> 1), width1, q, j);
       off0 = off1; width = width1;
-      if (FIRST) {
-        // tile already holds dis*T: Y = dis * (A_w + I)(dis*T) + b, straight from registers.
+      // tile already holds dis*T: Y = dis * (A_w + I)(dis*T) + b, straight from registers.
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int row = 16 * b + 4 * q + it;
-          if (row < n) {
-            const float4 a = scale4(ag[it], disl[row]);
-            const float4 y = make_float4(a.x + bias4.x, a.y + bias4.y, a.z + bias4.z, a.w + bias4.w);
-            st4(Y + (int64_t)(base + row) * HID + 4 * j, y);
-            s1[0] += y.x; s1[1] += y.y; s1[2] += y.z; s1[3] += y.w;
-            s2[0] += (double)y.x * y.x; s2[1] += (double)y.y * y.y;
-            s2[2] += (double)y.z * y.z; s2[3] += (double)y.w * y.w;
-          }
-        }
-        CGNN_STAMP(4)  // epilogue (first layer)
-        continue;
-      }
-#pragma unroll
-      for (int it = 0; it < 4; ++it)
-        st4(stg + (4 * q + it) * SLD + 4 * j, scale4(ag[it], disl[16 * b + 4 * q + it]));
-      __builtin_amdgcn_wave_barrier();
-      // A fragments: lane (i=j, kk=q) holds P[row j][k = 16q + s], s = 0..15
-      float af[16];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float4 v = ld4(stg + j * SLD + 16 * q + 4 * u);
-        af[4 * u + 0] = v.x; af[4 * u + 1] = v.y; af[4 * u + 2] = v.z; af[4 * u + 3] = v.w;
-      }
-      CGNN_STAMP(4)    // staging write + A-fragment read (+ next metadata issue)
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const float4 w4 = ld4(Wt + (16 * q + s) * HID + 4 * j);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], w4.x, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], w4.y, acc[1], 0, 0, 0);
-        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], w4.z, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], w4.w, acc[3], 0, 0, 0);
-      }
-      __builtin_amdgcn_wave_barrier();
-#ifdef CGNN_STAMPS
-      asm volatile("" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]));
-#endif
-      CGNN_STAMP(5)    // 64 MFMAs
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * b + 4 * q + r;
+      for (int it = 0; it < 4; ++it) {
+        const int row = 16 * b + 4 * q + it;
         if (row < n) {
-          const float4 y = make_float4(acc[0][r] + bias4.x, acc[1][r] + bias4.y,
-                                       acc[2][r] + bias4.z, acc[3][r] + bias4.w);
+          const float4 a = scale4(ag[it], disl[row]);
+          const float4 y = make_float4(a.x + bias4.x, a.y + bias4.y, a.z + bias4.z, a.w + bias4.w);
           st4(Y + (int64_t)(base + row) * HID + 4 * j, y);
           s1[0] += y.x; s1[1] += y.y; s1[2] += y.z; s1[3] += y.w;
           s2[0] += (double)y.x * y.x; s2[1] += (double)y.y * y.y;
           s2[2] += (double)y.z * y.z; s2[3] += (double)y.w * y.w;
         }
       }
-      CGNN_STAMP(7)    // epilogue: bias, store, fp64 statistics
+      CGNN_STAMP(4)    // epilogue: bias, store, fp64 statistics
     }
     __syncthreads();
     CGNN_STAMP(6)      // end-of-tile barrier wait
@@ -1010,402 +889,6 @@ __global__ void __launch_bounds__(NW * 64) k_gcn_bwd(
   }
 }
 
-// ==========================================================================================
-// readout (mean-pool) with the last layer's BatchNorm+ReLU+dropout fused in, and its backward
-// ==========================================================================================
-constexpr int PTHR = 256;   // 16 row-lanes x 16 chunks
-
-__global__ void __launch_bounds__(PTHR) k_pool_fwd(const float* __restrict__ Y,
-                                                   const float* __restrict__ bn, DropCfg drop_in,
-                                                   int use_drop, uint8_t* __restrict__ mask_out,
-                                                   const int32_t* __restrict__ gptr, int B,
-                                                   float* __restrict__ P, float* __restrict__ F1,
-                                                   float* __restrict__ F2) {
-  // F1/F2 (training): per graph and column, sum over the graph's rows of the factor f =
-  // relu'(z) * keep / (1-p) and of f * xhat.  The readout's gradient is constant per graph
-  // (dP[g] / (n_g + 1e-8)), so the BatchNorm-backward sums of the last layer are
-  // sum_g dP[g]/n_g * F1[g] and sum_g dP[g]/n_g * F2[g]: the backward never re-reads Y.
-  const DropCfg drop = drop_resolve(drop_in);
-  __shared__ float red[3 * 16 * HID];
-  const int j = threadIdx.x & 15, rr = threadIdx.x >> 4;
-  const float4 a = ld4(bn + 4 * j), b = ld4(bn + HID + 4 * j);
-  const float4 mean = ld4(bn + 2 * HID + 4 * j), is = ld4(bn + 3 * HID + 4 * j);
-  for (int g = blockIdx.x; g < B; g += gridDim.x) {
-    const int rbeg = gptr[g], rend = gptr[g + 1];
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), f1 = s, f2 = s;
-#define CGNN_POOL_U 4
-    constexpr int U = CGNN_POOL_U;             // rows in flight per thread (latency-bound otherwise)
-    for (int row0 = rbeg + rr; row0 < rend; row0 += 16 * U) {
-      float4 yb[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + 16 * u;
-        yb[u] = row < rend ? ldnt4(Y + (int64_t)row * HID + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + 16 * u;
-        if (row < rend) {
-          uint32_t keep = 0xFu;
-          if (use_drop) {
-            keep = drop_bits(drop, (uint32_t)row * 16u + (uint32_t)j);
-            if (mask_out) mask_out[(int64_t)row * 16 + j] = (uint8_t)keep;
-          }
-          float4 f;
-          const float4 y = yb[u];
-          const float4 x = act4(y, a, b, keep, drop.scale, f);
-          s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
-          if (F1) {
-            f1.x += f.x; f1.y += f.y; f1.z += f.z; f1.w += f.w;
-            f2.x = fmaf(f.x, (y.x - mean.x) * is.x, f2.x); f2.y = fmaf(f.y, (y.y - mean.y) * is.y, f2.y);
-            f2.z = fmaf(f.z, (y.z - mean.z) * is.z, f2.z); f2.w = fmaf(f.w, (y.w - mean.w) * is.w, f2.w);
-          }
-        }
-      }
-    }
-    st4(red + rr * HID + 4 * j, s);
-    if (F1) {
-      st4(red + (16 + rr) * HID + 4 * j, f1);
-      st4(red + (32 + rr) * HID + 4 * j, f2);
-    }
-    __syncthreads();
-    if (threadIdx.x < HID) {
-      float tot = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) tot += red[k * HID + threadIdx.x];
-      P[(int64_t)g * HID + threadIdx.x] = tot / ((float)(rend - rbeg) + 1e-8f);
-    } else if (F1 && threadIdx.x < 3 * HID) {
-      const int which = threadIdx.x / HID, col = threadIdx.x % HID;          // 1: F1, 2: F2
-      double tot = 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) tot += (double)red[(16 * which + k) * HID + col];
-      (which == 1 ? F1 : F2)[(int64_t)g * HID + col] = (float)tot;
-    }
-    __syncthreads();
-  }
-}
-
-// BatchNorm-backward sums of the last layer from the per-graph factor sums of k_pool_fwd:
-// slab[wg][0..63] = sum_g dP[g]/(n_g+1e-8) * F1[g], slab[wg][64..127] = ... * F2[g]  (fp64).
-__global__ void __launch_bounds__(128) k_pool_bwd_sums(const float* __restrict__ dP,
-                                                       const float* __restrict__ F1,
-                                                       const float* __restrict__ F2,
-                                                       const int32_t* __restrict__ gptr, int B,
-                                                       double* __restrict__ s_slab) {
-  const int col = threadIdx.x & 63;
-  const float* F = threadIdx.x < 64 ? F1 : F2;
-  double acc = 0.0;
-  for (int g = blockIdx.x; g < B; g += gridDim.x) {
-    const float inv = 1.0f / ((float)(gptr[g + 1] - gptr[g]) + 1e-8f);
-    acc += (double)(dP[(int64_t)g * HID + col] * inv) * (double)F[(int64_t)g * HID + col];
-  }
-  s_slab[(int64_t)blockIdx.x * 128 + threadIdx.x] = acc;
-}
-
-// The same sums folded over ALL graphs by one block per channel, finalised on the spot (per-rank
-// BatchNorm: no exchange between the sums and the coefficients) -- k_pool_bwd_sums +
-// k_bn_bwd_stats in one launch.
-__global__ void __launch_bounds__(256) k_pool_bwd_finalize(const float* __restrict__ dP,
-                                                           const float* __restrict__ F1,
-                                                           const float* __restrict__ F2,
-                                                           const int32_t* __restrict__ gptr, int B,
-                                                           double count, int zero_coef,
-                                                           float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta,
-                                                           float* __restrict__ bwc) {
-  __shared__ double sh[4];
-  const int c = blockIdx.x;
-  double a1 = 0.0, a2 = 0.0;
-  for (int g = threadIdx.x; g < B; g += 256) {
-    const float inv = 1.0f / ((float)(gptr[g + 1] - gptr[g]) + 1e-8f);
-    const double d = (double)(dP[(int64_t)g * HID + c] * inv);
-    a1 += d * (double)F1[(int64_t)g * HID + c];
-    a2 += d * (double)F2[(int64_t)g * HID + c];
-  }
-  const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
-  if (threadIdx.x == 0) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, HID, c);
-}
-
-constexpr int PBTHR = 1024;  // readout backward: 64 row-lanes x 16 chunks (16 waves per CU)
-
-__global__ void __launch_bounds__(PBTHR) k_pool_bwd(const float* __restrict__ dP,
-                                                   const float* __restrict__ Y,
-                                                   const float* __restrict__ bn, DropCfg drop,
-                                                   int use_drop, const uint8_t* __restrict__ mask,
-                                                   const int32_t* __restrict__ gptr, int B,
-                                                   float* __restrict__ dZ,
-                                                   double* __restrict__ s_slab) {
-  __shared__ double red[(PBTHR / 16) * 128];
-  const int j = threadIdx.x & 15, rr = threadIdx.x >> 4;
-  const float4 a = ld4(bn + 4 * j), b = ld4(bn + HID + 4 * j);
-  const float4 mean = ld4(bn + 2 * HID + 4 * j), is = ld4(bn + 3 * HID + 4 * j);
-  double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-  for (int g = blockIdx.x; g < B; g += gridDim.x) {
-    const int rbeg = gptr[g], rend = gptr[g + 1];
-    const float inv = 1.0f / ((float)(rend - rbeg) + 1e-8f);
-    float4 gp = ld4(dP + (int64_t)g * HID + 4 * j);
-    gp.x *= inv; gp.y *= inv; gp.z *= inv; gp.w *= inv;
-    constexpr int U = 3;                       // rows in flight per thread
-    constexpr int RS = PBTHR / 16;             // row stride
-    for (int row0 = rbeg + rr; row0 < rend; row0 += RS * U) {
-      float4 yb[U];
-      uint32_t kb[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + RS * u;
-        yb[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        kb[u] = 0u;
-        if (row < rend) {
-          yb[u] = ld4(Y + (int64_t)row * HID + 4 * j);
-          kb[u] = use_drop ? mask[(int64_t)row * 16 + j] : 0xFu;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + RS * u;
-        if (row < rend) {
-          const float4 y = yb[u];
-          float4 f;
-          act4(y, a, b, kb[u], drop.scale, f);
-          const float4 dz = make_float4(gp.x * f.x, gp.y * f.y, gp.z * f.z, gp.w * f.w);
-          if (dZ) st4(dZ + (int64_t)row * HID + 4 * j, dz);
-          s1[0] += dz.x; s1[1] += dz.y; s1[2] += dz.z; s1[3] += dz.w;
-          s2[0] += (double)dz.x * ((y.x - mean.x) * is.x); s2[1] += (double)dz.y * ((y.y - mean.y) * is.y);
-          s2[2] += (double)dz.z * ((y.z - mean.z) * is.z); s2[3] += (double)dz.w * ((y.w - mean.w) * is.w);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    red[rr * 128 + 4 * j + i] = s1[i];
-    red[rr * 128 + 64 + 4 * j + i] = s2[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    double tot = 0.0;
-    for (int k = 0; k < PBTHR / 16; ++k) tot += red[k * 128 + threadIdx.x];
-    s_slab[(int64_t)blockIdx.x * 128 + threadIdx.x] = tot;
-  }
-}
-
-// ==========================================================================================
-// small reductions / BatchNorm coefficient kernels
-// ==========================================================================================
-template <typename T>
-__global__ void __launch_bounds__(256) k_slab_reduce(const T* __restrict__ slab, int rows,
-                                                     int width, double* __restrict__ out_d,
-                                                     float* __restrict__ out_f, int out_cols,
-                                                     int take_cols, int ld_out,
-                                                     float* __restrict__ out_tail = nullptr, int split = 0) {
-  // one block per 4 output elements: 64 threads (one wave) per element, fixed-order tree
-  const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  double s = 0.0;
-  if (e < width)
-    for (int r = lane; r < rows; r += 64) s += (double)slab[(int64_t)r * width + e];
-  s = cgnn_wave_sum(s);
-  if (e < width && lane == 0) {
-    if (out_d) out_d[e] = s;
-    if (out_tail && e >= split) {
-      out_tail[e - split] = (float)s;
-    } else if (out_f) {
-      const int rr = e / out_cols, cc = e % out_cols;
-      if (cc < take_cols) out_f[(int64_t)rr * ld_out + cc] = (float)s;
-    }
-  }
-}
-
-// several f64 slab -> f32 vector reductions in one launch (blockIdx.y = job): the bias gradients of
-// all layers of a backward pass
-__global__ void __launch_bounds__(256) k_slab_reduce_multi(cgnn_reduce_jobs jobs) {
-  const int jb = blockIdx.y;
-  const int width = jobs.width[jb], rows = jobs.rows[jb];
-  const double* __restrict__ slab = jobs.slab[jb];
-  const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (e >= width) return;                                  // (wave-uniform)
-  double s = 0.0;
-  for (int r = lane; r < rows; r += 64) s += slab[(int64_t)r * width + e];
-  s = cgnn_wave_sum(s);
-  if (lane == 0) jobs.out[jb][e] = (float)s;
-}
-
-__global__ void k_bn_finalize(const double* __restrict__ sums, double count,
-                              const double* __restrict__ count_dev,
-                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                              float* __restrict__ rmean, float* __restrict__ rvar, float momentum,
-                              float eps, int training, float* __restrict__ bn_out,
-                              const float* __restrict__ mean_offset) {
-  const int c = threadIdx.x;
-  if (c >= HID) return;
-  if (count_dev) count = count_dev[0];
-  // mean_offset (nullable): the statistics are those of y - mean_offset[c] (the factored layer 0 is
-  // handed on without its constant term); the module's running mean is that of y.  sums: NULL in eval
-  const double S1 = training ? sums[c] : 0.0, S2 = training ? sums[HID + c] : 0.0;
-  bn_fwd_coef(training, S1, S2, count, gamma, beta, rmean, rvar, momentum, eps,
-              mean_offset ? mean_offset[c] : 0.f, bn_out, HID, c);
-}
-
-__global__ void k_bn_bwd_finalize(const double* __restrict__ sums, double count,
-                                  const double* __restrict__ count_dev, int zero_coef,
-                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                  float* __restrict__ bwc) {
-  const int c = threadIdx.x;
-  if (c >= HID) return;
-  if (count_dev) count = count_dev[0];
-  bn_bwd_coef(sums[c], sums[HID + c], count, zero_coef, dgamma, dbeta, bwc, HID, c);
-}
-
-// ---- merged "reduce the per-workgroup partials + finalise" kernels (single-GPU fast path) ----
-
-// one block per channel c: S1 = sum_r slab[r][c], S2 = sum_r slab[r][64+c], then finalise
-__global__ void __launch_bounds__(256) k_bn_fwd_stats(
-    const double* __restrict__ slab, int rows, double count, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
-    float momentum, float eps, long long* __restrict__ tracked, float* __restrict__ bn_out,
-    uint32_t* __restrict__ rng_state, int rng_n, const float* __restrict__ mean_offset) {
-  __shared__ double sh[4];
-  const int c = blockIdx.x;
-  // graph replay: refresh the device dropout words here -- this launch runs after every consumer of
-  // the previous step's words and before the first of this one
-  if (rng_state && c == 0 && (int)threadIdx.x < rng_n)
-    rng_state[threadIdx.x] = rng_refresh(rng_state[threadIdx.x], threadIdx.x);
-  double a1 = 0.0, a2 = 0.0;
-  for (int r = threadIdx.x; r < rows; r += 256) {
-    a1 += slab[(int64_t)r * 128 + c];
-    a2 += slab[(int64_t)r * 128 + HID + c];
-  }
-  const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
-  if (threadIdx.x == 0) {
-    bn_fwd_coef(true, S1, S2, count, gamma, beta, rmean, rvar, momentum, eps,
-                mean_offset ? mean_offset[c] : 0.f, bn_out, HID, c);
-    if (c == 0 && tracked) *tracked += 1;
-  }
-}
-
-__global__ void __launch_bounds__(256) k_bn_bwd_stats(const double* __restrict__ slab, int rows,
-                                                      double count, int zero_coef,
-                                                      float* __restrict__ dgamma,
-                                                      float* __restrict__ dbeta,
-                                                      float* __restrict__ bwc) {
-  __shared__ double sh[4];
-  const int c = blockIdx.x;
-  double a1 = 0.0, a2 = 0.0;
-  for (int r = threadIdx.x; r < rows; r += 256) {
-    a1 += slab[(int64_t)r * 128 + c];
-    a2 += slab[(int64_t)r * 128 + HID + c];
-  }
-  const double S1 = block_sum256(a1, sh), S2 = block_sum256(a2, sh);
-  if (threadIdx.x == 0) bn_bwd_coef(S1, S2, count, zero_coef, dgamma, dbeta, bwc, HID, c);
-}
-
-// dW (f32 slab [rows][64*out_cols]) and db (f64 slab [rows][64]) in one launch.  A block folds
-// RD_C consecutive output elements: thread (cc, rg) adds rows rg, rg + RD_G, ... of element cc
-// (every load instruction reads 64-byte row pieces, up to 16 in flight per thread; 64 row groups, since
-// the layer-0 slab has 2048 rows and the fold is a latency chain), then the RD_G partials are
-// combined in fixed order.  [one wave per element with lane = row touched 64 lines
-// per load: 32 us for the three layers of a step]
-constexpr int RD_C = 16, RD_G = 64;      // 1024 threads
-__host__ __device__ inline int dw_db_blocks(int out_cols) { return (HID * out_cols + HID) / RD_C; }
-__device__ __forceinline__ void dw_db_reduce_block(const float* __restrict__ dw_slab,
-                                                   const double* __restrict__ db_slab, int rows,
-                                                   int out_cols, int take_cols,
-                                                   float* __restrict__ dW, int ldw,
-                                                   float* __restrict__ db, int block) {
-  __shared__ double sh[RD_G][RD_C];
-  const int nw = HID * out_cols;                    // a multiple of RD_C: a block is all dW or all db
-  const int cc = threadIdx.x % RD_C, rg = threadIdx.x / RD_C;
-  const int e = block * RD_C + cc;
-  double s = 0.0;
-  if (e < nw) {
-    int r = rg;
-    for (; r + 15 * RD_G < rows; r += 16 * RD_G) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = dw_slab[(int64_t)(r + u * RD_G) * nw + e];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) s += (double)v[u];
-    }
-    for (; r + 3 * RD_G < rows; r += 4 * RD_G) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = dw_slab[(int64_t)(r + u * RD_G) * nw + e];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += (double)v[u];
-    }
-    for (; r < rows; r += RD_G) s += (double)dw_slab[(int64_t)r * nw + e];
-  } else {
-    int r = rg;
-    for (; r + 7 * RD_G < rows; r += 8 * RD_G) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = db_slab[(int64_t)(r + u * RD_G) * HID + (e - nw)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; r < rows; r += RD_G) s += db_slab[(int64_t)r * HID + (e - nw)];
-  }
-  sh[rg][cc] = s;
-  __syncthreads();
-  __shared__ double sh2[RD_G / 8][RD_C];
-  if (rg < RD_G / 8) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t += sh[8 * rg + k][cc];
-    sh2[rg][cc] = t;
-  }
-  __syncthreads();
-  if (rg == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < RD_G / 8; ++k) t += sh2[k][cc];
-    if (e < nw) {
-      const int o = e / out_cols, c2 = e % out_cols;
-      if (c2 < take_cols) dW[(int64_t)o * ldw + c2] = (float)t;
-    } else {
-      db[e - nw] = (float)t;
-    }
-  }
-}
-
-// several layers' slabs in ONE launch (the reductions do not feed the backward chain, so they can
-// all wait for its end: one launch instead of one per layer)
-__global__ void __launch_bounds__(RD_C * RD_G) k_dw_db_reduce_multi(cgnn_dw_jobs jobs) {
-  int block = blockIdx.x;
-#pragma unroll
-  for (int i = 0; i < CGNN_DW_MAX_JOBS; ++i) {
-    if (i >= jobs.n) return;
-    const int nb = dw_db_blocks(jobs.out_cols[i]);
-    if (block < nb) {
-      dw_db_reduce_block(jobs.dw_slab[i], jobs.db_slab[i], jobs.rows[i], jobs.out_cols[i], jobs.take_cols[i],
-                         jobs.dW[i], jobs.take_cols[i], jobs.db[i], block);
-      return;
-    }
-    block -= nb;
-  }
-}
-
-int g_grid_cache[CGNN_MAX_DEVICES] = {};
-int g_grid_override = 0;   // cgnn_set_fused_grid (test hook): > 0 replaces the CU count
-
-int fused_grid() {
-  if (g_grid_override > 0) return g_grid_override;
-  const int dev = cgnn_device_ordinal();
-  if (g_grid_cache[dev] == 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      return 256;
-    g_grid_cache[dev] = cus;
-  }
-  return g_grid_cache[dev];
-}
-
-__global__ void k_rng_advance(uint32_t* state, int n) {
-  const int i = threadIdx.x;
-  if (i < n) state[i] = rng_refresh(state[i], i);
-}
-
 bool l0src_ok(const cgnn_l0src* l0) {
   return l0 && l0->P0 && l0->W0 && l0->b0 && l0->F0 >= 1 && l0->F0 <= L0_FP;
 }
@@ -1420,10 +903,15 @@ bool tail_ok(const cgnn_bn_tail* tl, int mode) {
   return tl->dgamma && tl->dbeta && tl->bwc;
 }
 
-bool tiles_ok(const cgnn_tiles* t) {
-  return t && t->num_tiles >= 0 && t->num_nodes >= 0 && t->max_tile_rows <= CGNN_FUSED_MAX_ROWS &&
-         (t->num_tiles == 0 || (t->tile_ptr && t->tile_blk && t->blk_off_dst && t->ent_dst &&
-                                t->blk_off_src && t->ent_src && t->dis));
+// The tile metadata every tile kernel needs, and (first-layer forms) the input width.  CGNN_OK, or the
+// status to return: tiles taller than the LDS tile are a shape this build does not cover, whatever else
+// is wrong; anything else is a bad argument.
+int tiles_status(const cgnn_tiles* t, int F0 = 1) {
+  if (t && t->max_tile_rows > CGNN_FUSED_MAX_ROWS) return CGNN_EUNSUPPORTED;
+  const bool ok = t && t->num_tiles >= 0 && t->num_nodes >= 0 &&
+                  (t->num_tiles == 0 || (t->tile_ptr && t->tile_blk && t->blk_off_dst && t->ent_dst &&
+                                         t->blk_off_src && t->ent_src && t->dis));
+  return ok && F0 > 0 && F0 <= CGNN_FUSED_MAX_F0 ? CGNN_OK : CGNN_EINVAL;
 }
 
 }  // namespace
@@ -1441,29 +929,13 @@ int cgnn_debug_stamps(unsigned long long* out_host) {
 }
 #endif
 
-int cgnn_fused_grid(void) { return fused_grid(); }
-
-int cgnn_set_fused_grid(int32_t workgroups) {
-  if (workgroups < 0 || workgroups > 65535) return CGNN_EINVAL;
-  g_grid_override = workgroups;
-  return CGNN_OK;
-}
-
 int cgnn_gcn_fused_fwd_first(const cgnn_tiles* t, const float* X0, int32_t F0, const float* W0,
                              const float* bias, float* Y, double* stat_slab, int64_t stat_slab_bytes, void* stream) {
-  if (!tiles_ok(t) || F0 <= 0 || F0 > CGNN_FUSED_MAX_F0) return t && t->max_tile_rows > CGNN_FUSED_MAX_ROWS ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (const int rc = tiles_status(t, F0)) return rc;
   if (!X0 || !W0 || !bias || !Y) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(stat_slab, stat_slab_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
-  DropCfg d{};
-  k_gcn_fwd<CGNN_FUSED_MAX_ROWS, true><<<fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
-      *t, X0, F0, nullptr, d, 0, nullptr, W0, bias, Y, stat_slab);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_rng_advance(uint32_t* state, int32_t n, void* stream) {
-  if (!state || n <= 0 || n > 64) return CGNN_EINVAL;
-  k_rng_advance<<<1, 64, 0, cgnn_stream(stream)>>>(state, n);
+  CGNN_NEED_BYTES(stat_slab, stat_slab_bytes, fused_stat_slab_bytes());
+  k_gcn_fwd_first<CGNN_FUSED_MAX_ROWS><<<cgnn_fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
+      *t, X0, F0, W0, bias, Y, stat_slab);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
@@ -1472,90 +944,20 @@ int cgnn_gcn_fused_fwd(const cgnn_tiles* t, const float* Yprev, const cgnn_l0src
                        const float* bn_prev, float p_drop, uint64_t seed, const uint32_t* seed_dev,
                        uint8_t* mask_out, const float* W, const float* bias, float* Y,
                        double* stat_slab, int64_t stat_slab_bytes, const cgnn_bn_tail* tail, void* stream) {
-  if (!tiles_ok(t)) return t && t->max_tile_rows > CGNN_FUSED_MAX_ROWS ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (const int rc = tiles_status(t)) return rc;
   if ((!Yprev && !l0src_ok(l0)) || !bn_prev || !W || !bias || !Y || p_drop < 0.f || p_drop >= 1.f) return CGNN_EINVAL;
   if (!tail_ok(tail, 0)) return CGNN_EINVAL;
   const cgnn_bn_tail tl = tail ? *tail : cgnn_bn_tail{};
-  CGNN_NEED_BYTES(stat_slab, stat_slab_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
+  CGNN_NEED_BYTES(stat_slab, stat_slab_bytes, fused_stat_slab_bytes());
   int use_drop;
   DropCfg d = make_drop(p_drop, seed, &use_drop);
   d.dev_key = seed_dev;
   if (Yprev)
-    k_gcn_fwd_pf<CGNN_FUSED_MAX_ROWS, false><<<fused_grid(), PF_NTHR, 0, cgnn_stream(stream)>>>(
+    k_gcn_fwd_pf<CGNN_FUSED_MAX_ROWS, false><<<cgnn_fused_grid(), PF_NTHR, 0, cgnn_stream(stream)>>>(
         *t, Yprev, cgnn_l0src{}, bn_prev, d, use_drop, mask_out, W, bias, Y, stat_slab, tl);
   else
-    k_gcn_fwd_pf<CGNN_FUSED_MAX_ROWS, true><<<fused_grid(), PF_NTHR, 0, cgnn_stream(stream)>>>(
+    k_gcn_fwd_pf<CGNN_FUSED_MAX_ROWS, true><<<cgnn_fused_grid(), PF_NTHR, 0, cgnn_stream(stream)>>>(
         *t, nullptr, *l0, bn_prev, d, use_drop, mask_out, W, bias, Y, stat_slab, tl);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_bn_reduce(const double* slab, int32_t rows, int32_t width, double* sums, void* stream) {
-  if (!slab || !sums || rows <= 0 || width <= 0) return CGNN_EINVAL;
-  k_slab_reduce<double><<<(width + 3) / 4, 256, 0, cgnn_stream(stream)>>>(slab, rows, width, sums,
-                                                                        nullptr, 1, 1, 1);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_bn_finalize(const double* sums, double count, const double* count_dev, const float* gamma,
-                     const float* beta, float* running_mean, float* running_var, float momentum,
-                     float eps, int32_t training, float* bn_out, const float* mean_offset, void* stream) {
-  if (!gamma || !beta || !running_mean || !running_var || !bn_out) return CGNN_EINVAL;
-  if (training && (!sums || (!count_dev && count <= 0.0))) return CGNN_EINVAL;
-  k_bn_finalize<<<1, 64, 0, cgnn_stream(stream)>>>(sums, count, count_dev, gamma, beta, running_mean,
-                                                   running_var, momentum, eps, training, bn_out, mean_offset);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_gcn_fused_pool_fwd(const float* Y, const float* bn, float p_drop, uint64_t seed,
-                            const uint32_t* seed_dev, uint8_t* mask_out, const int32_t* gptr,
-                            int32_t num_graphs, float* P, float* F1, float* F2, void* stream) {
-  if (num_graphs < 0 || p_drop < 0.f || p_drop >= 1.f) return CGNN_EINVAL;
-  if (num_graphs == 0) return CGNN_OK;
-  if (!Y || !bn || !gptr || !P || (!F1) != (!F2)) return CGNN_EINVAL;
-  int use_drop;
-  DropCfg d = make_drop(p_drop, seed, &use_drop);
-  d.dev_key = seed_dev;
-  const int grid = num_graphs < 8 * fused_grid() ? num_graphs : 8 * fused_grid();
-  k_pool_fwd<<<grid, PTHR, 0, cgnn_stream(stream)>>>(Y, bn, d, use_drop, mask_out, gptr, num_graphs, P,
-                                                     F1, F2);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_gcn_fused_pool_bwd_sums(const float* dP, const float* F1, const float* F2,
-                                 const int32_t* gptr, int32_t num_graphs, double* s_slab, int64_t s_slab_bytes,
-                                 void* stream) {
-  if (num_graphs < 0 || !dP || !F1 || !F2 || !gptr || !s_slab) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(s_slab, s_slab_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
-  // exactly cgnn_fused_grid() workgroups so that the slab has the documented row count
-  k_pool_bwd_sums<<<fused_grid(), 128, 0, cgnn_stream(stream)>>>(dP, F1, F2, gptr, num_graphs, s_slab);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_gcn_fused_pool_bwd(const float* dP, const float* Y, const float* bn, float p_drop,
-                            const uint8_t* mask, const int32_t* gptr, int32_t num_graphs,
-                            float* dZ, double* s_slab, int64_t s_slab_bytes, void* stream) {
-  if (num_graphs < 0 || p_drop < 0.f || p_drop >= 1.f) return CGNN_EINVAL;
-  if (!dP || !Y || !bn || !gptr || !s_slab) return CGNN_EINVAL;   /* dZ may be NULL: sums only */
-  if (p_drop > 0.f && !mask) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(s_slab, s_slab_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
-  int use_drop;
-  DropCfg d = make_drop(p_drop, 0, &use_drop);
-  // exactly cgnn_fused_grid() workgroups so that the slab has the documented row count
-  k_pool_bwd<<<fused_grid(), PBTHR, 0, cgnn_stream(stream)>>>(dP, Y, bn, d, use_drop, mask, gptr,
-                                                             num_graphs, dZ, s_slab);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_bn_bwd_finalize(const double* sums, double count, const double* count_dev,
-                         int32_t zero_coef, float* dgamma, float* dbeta, float* bwc, void* stream) {
-  if (!sums || !dgamma || !dbeta || !bwc || (!count_dev && count <= 0.0)) return CGNN_EINVAL;
-  k_bn_bwd_finalize<<<1, 64, 0, cgnn_stream(stream)>>>(sums, count, count_dev, zero_coef, dgamma, dbeta, bwc);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
@@ -1566,7 +968,7 @@ int cgnn_gcn_fused_bwd(const cgnn_tiles* t, const float* dZ, const float* Y, con
                        float* dZprev, double* s_slab_prev, int64_t s_slab_prev_bytes, float* dW_slab, int64_t dW_slab_bytes, double* db_slab, int64_t db_slab_bytes,
                        const float* dP, const int32_t* node_graph, const int32_t* gptr,
                        const uint8_t* mask_cur, const cgnn_bn_tail* tail, void* stream) {
-  if (!tiles_ok(t)) return t && t->max_tile_rows > CGNN_FUSED_MAX_ROWS ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (const int rc = tiles_status(t)) return rc;
   if (!Y || !bn || !bwc || (!Yprev && !l0src_ok(l0)) || !bn_prev || !W || !dZprev || (!s_slab_prev && !tail) ||
       !dW_slab || !db_slab || p_drop < 0.f || p_drop >= 1.f)
     return CGNN_EINVAL;
@@ -1574,16 +976,16 @@ int cgnn_gcn_fused_bwd(const cgnn_tiles* t, const float* dZ, const float* Y, con
   const cgnn_bn_tail tl = tail ? *tail : cgnn_bn_tail{};
   if (p_drop > 0.f && (!mask_prev || (reinterpret_cast<uintptr_t>(mask_prev) & 3u))) return CGNN_EINVAL;
   if (dP ? (!node_graph || !gptr || (p_drop > 0.f && !mask_cur)) : !dZ) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(s_slab_prev, s_slab_prev_bytes, (int64_t)fused_grid() * 128 * (int64_t)sizeof(double));
-  CGNN_NEED_BYTES(dW_slab, dW_slab_bytes, (int64_t)fused_grid() * HID * HID * (int64_t)sizeof(float));
-  CGNN_NEED_BYTES(db_slab, db_slab_bytes, (int64_t)fused_grid() * HID * (int64_t)sizeof(double));
+  CGNN_NEED_BYTES(s_slab_prev, s_slab_prev_bytes, fused_stat_slab_bytes());
+  CGNN_NEED_BYTES(dW_slab, dW_slab_bytes, (int64_t)cgnn_fused_grid() * HID * HID * (int64_t)sizeof(float));
+  CGNN_NEED_BYTES(db_slab, db_slab_bytes, (int64_t)cgnn_fused_grid() * HID * (int64_t)sizeof(double));
   int use_drop;
   DropCfg d = make_drop(p_drop, 0, &use_drop);
   PoolIn pin{dP, node_graph, gptr, mask_cur};
   const cgnn_l0src src = Yprev ? cgnn_l0src{} : *l0;
 #define CGNN_BWD_NW 8
 #define CGNN_BWD_LAUNCH(POOL, XP)                                                                      \
-  k_gcn_bwd<CGNN_FUSED_MAX_ROWS, false, POOL, XP, CGNN_BWD_NW><<<fused_grid(), CGNN_BWD_NW * 64, 0, cgnn_stream(stream)>>>( \
+  k_gcn_bwd<CGNN_FUSED_MAX_ROWS, false, POOL, XP, CGNN_BWD_NW><<<cgnn_fused_grid(), CGNN_BWD_NW * 64, 0, cgnn_stream(stream)>>>( \
       *t, pin, src, dZ, Y, bn, bwc, Yprev, 0, bn_prev, d, use_drop, mask_prev, W, dZprev, s_slab_prev, \
       dW_slab, db_slab, tl)
   if (dP) { if (Yprev) CGNN_BWD_LAUNCH(true, false); else CGNN_BWD_LAUNCH(true, true); }
@@ -1598,104 +1000,22 @@ int cgnn_gcn_fused_bwd_first(const cgnn_tiles* t, const float* dZ, const float* 
                              double* db_slab, int64_t db_slab_bytes, float p_drop, const float* dP,
                              const int32_t* node_graph, const int32_t* gptr,
                              const uint8_t* mask_cur, void* stream) {
-  if (!tiles_ok(t) || F0 <= 0 || F0 > CGNN_FUSED_MAX_F0) return t && t->max_tile_rows > CGNN_FUSED_MAX_ROWS ? CGNN_EUNSUPPORTED : CGNN_EINVAL;
+  if (const int rc = tiles_status(t, F0)) return rc;
   if (!Y || !bn || !bwc || !X0 || !dW_slab || !db_slab || p_drop < 0.f || p_drop >= 1.f) return CGNN_EINVAL;
   if (dP ? (!node_graph || !gptr || (p_drop > 0.f && !mask_cur)) : !dZ) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(dW_slab, dW_slab_bytes, (int64_t)fused_grid() * HID * 16 * (int64_t)sizeof(float));
-  CGNN_NEED_BYTES(db_slab, db_slab_bytes, (int64_t)fused_grid() * HID * (int64_t)sizeof(double));
+  CGNN_NEED_BYTES(dW_slab, dW_slab_bytes, (int64_t)cgnn_fused_grid() * HID * 16 * (int64_t)sizeof(float));
+  CGNN_NEED_BYTES(db_slab, db_slab_bytes, (int64_t)cgnn_fused_grid() * HID * (int64_t)sizeof(double));
   int use_drop;
   DropCfg d = make_drop(dP ? p_drop : 0.f, 0, &use_drop);
   PoolIn pin{dP, node_graph, gptr, mask_cur};
   if (dP)
-    k_gcn_bwd<CGNN_FUSED_MAX_ROWS, true, true><<<fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
+    k_gcn_bwd<CGNN_FUSED_MAX_ROWS, true, true><<<cgnn_fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
         *t, pin, cgnn_l0src{}, dZ, Y, bn, bwc, X0, F0, nullptr, d, use_drop, nullptr, nullptr, nullptr, nullptr,
         dW_slab, db_slab, cgnn_bn_tail{});
   else
-    k_gcn_bwd<CGNN_FUSED_MAX_ROWS, true, false><<<fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
+    k_gcn_bwd<CGNN_FUSED_MAX_ROWS, true, false><<<cgnn_fused_grid(), NTHR, 0, cgnn_stream(stream)>>>(
         *t, pin, cgnn_l0src{}, dZ, Y, bn, bwc, X0, F0, nullptr, d, use_drop, nullptr, nullptr, nullptr, nullptr,
         dW_slab, db_slab, cgnn_bn_tail{});
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_bn_stats_finalize_rng(const double* slab, int32_t rows, double count, const float* gamma,
-                               const float* beta, float* running_mean, float* running_var,
-                               float momentum, float eps, int64_t* num_batches_tracked, float* bn_out,
-                               uint32_t* rng_state, int32_t rng_n, const float* mean_offset, void* stream) {
-  if (!slab || rows <= 0 || count <= 0.0 || !gamma || !beta || !running_mean || !running_var || !bn_out)
-    return CGNN_EINVAL;
-  if (rng_n < 0 || rng_n > 64 || (rng_n > 0 && !rng_state)) return CGNN_EINVAL;
-  k_bn_fwd_stats<<<HID, 256, 0, cgnn_stream(stream)>>>(
-      slab, rows, count, gamma, beta, running_mean, running_var, momentum, eps,
-      reinterpret_cast<long long*>(num_batches_tracked), bn_out, rng_state, rng_n, mean_offset);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_gcn_fused_pool_bwd_finalize(const float* dP, const float* F1, const float* F2,
-                                     const int32_t* gptr, int32_t num_graphs, double count,
-                                     int32_t zero_coef, float* dgamma, float* dbeta, float* bwc,
-                                     void* stream) {
-  if (num_graphs < 0 || count <= 0.0 || !dP || !F1 || !F2 || !gptr || !dgamma || !dbeta || !bwc)
-    return CGNN_EINVAL;
-  k_pool_bwd_finalize<<<HID, 256, 0, cgnn_stream(stream)>>>(dP, F1, F2, gptr, num_graphs, count, zero_coef,
-                                                           dgamma, dbeta, bwc);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_bn_bwd_stats_finalize(const double* slab, int32_t rows, double count, int32_t zero_coef,
-                               float* dgamma, float* dbeta, float* bwc, void* stream) {
-  if (!slab || rows <= 0 || count <= 0.0 || !dgamma || !dbeta || !bwc) return CGNN_EINVAL;
-  k_bn_bwd_stats<<<HID, 256, 0, cgnn_stream(stream)>>>(slab, rows, count, zero_coef, dgamma, dbeta, bwc);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_dw_db_reduce_multi(const cgnn_dw_jobs* jobs, void* stream) {
-  if (!jobs || jobs->n < 1 || jobs->n > CGNN_DW_MAX_JOBS) return CGNN_EINVAL;
-  int total = 0;
-  for (int i = 0; i < jobs->n; ++i) {
-    if (!jobs->dw_slab[i] || !jobs->db_slab[i] || !jobs->dW[i] || !jobs->db[i] || jobs->rows[i] <= 0 ||
-        jobs->out_cols[i] <= 0 || jobs->take_cols[i] <= 0 || jobs->take_cols[i] > jobs->out_cols[i])
-      return CGNN_EINVAL;
-    total += (HID * jobs->out_cols[i] + HID) / RD_C;
-  }
-  k_dw_db_reduce_multi<<<total, RD_C * RD_G, 0, cgnn_stream(stream)>>>(*jobs);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_slab_reduce_f32(const float* slab, int32_t rows, int32_t out_rows, int32_t out_cols,
-                         int32_t take_cols, float* out, int32_t ld_out, void* stream) {
-  if (!slab || !out || rows <= 0 || out_rows <= 0 || out_cols <= 0 || take_cols <= 0 ||
-      take_cols > out_cols || ld_out < take_cols)
-    return CGNN_EINVAL;
-  const int width = out_rows * out_cols;
-  k_slab_reduce<float><<<(width + 3) / 4, 256, 0, cgnn_stream(stream)>>>(
-      slab, rows, width, nullptr, out, out_cols, take_cols, ld_out);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_slab_reduce_f32_split(const float* slab, int32_t rows, int32_t width, int32_t split, float* out,
-                               float* out_tail, void* stream) {
-  if (!slab || !out || !out_tail || rows <= 0 || width <= 0 || split <= 0 || split >= width) return CGNN_EINVAL;
-  k_slab_reduce<float><<<(width + 3) / 4, 256, 0, cgnn_stream(stream)>>>(slab, rows, width, nullptr, out, width,
-                                                                        width, width, out_tail, split);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
-}
-
-int cgnn_slab_reduce_f64_multi(const cgnn_reduce_jobs* jobs, void* stream) {
-  if (!jobs || jobs->n < 0 || jobs->n > CGNN_REDUCE_MAX_JOBS) return CGNN_EINVAL;
-  if (jobs->n == 0) return CGNN_OK;
-  int wmax = 0;
-  for (int j = 0; j < jobs->n; ++j) {
-    if (!jobs->slab[j] || !jobs->out[j] || jobs->rows[j] <= 0 || jobs->width[j] <= 0) return CGNN_EINVAL;
-    wmax = jobs->width[j] > wmax ? jobs->width[j] : wmax;
-  }
-  k_slab_reduce_multi<<<dim3((wmax + 3) / 4, jobs->n), 256, 0, cgnn_stream(stream)>>>(*jobs);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }

@@ -391,3 +391,242 @@ def test_trainer_host_side_decisions_for_the_packed_path():
     p._cgnn_direct = True
     p.grad = torch.zeros(3)
     assert ops.grad_destination(p) is None and p._cgnn_direct is False         # host tensors are never written to; disarmed
+
+
+# ---- refusal codes of the tile entry points (csrc/fused_gcn.hip, fused_readout.hip, aggregate_tiled*.hip) ----
+# One row = one call with one bad argument (a few with two, where the ORDER of the checks decides the code) and
+# the status the library returns for it.  Every row returns before any launch and before any HIP runtime call:
+# the pointers are made-up values that are only ever compared and masked, and the workgroup count behind the
+# slab sizes is pinned with cgnn_set_fused_grid.
+_A, _M = 0x1000, 0x1004          # 16-byte aligned / misaligned device-pointer values
+_GRID = 4                        # pinned workgroup count: [grid][128] f64 slab = 4096 bytes
+_INV, _UNS, _OK = _lib.CGNN_EINVAL, _lib.CGNN_EUNSUPPORTED, _lib.CGNN_OK
+_TILE_FIELDS = ("tile_ptr", "tile_blk", "blk_off_dst", "ent_dst", "blk_off_src", "ent_src", "dis")
+
+
+def _tiles(**kw):
+    if kw.pop("null", False):
+        return None
+    t = _lib.CgnnTiles()
+    t.num_nodes, t.num_tiles, t.max_tile_rows = 10, 1, 16
+    for f in _TILE_FIELDS:
+        setattr(t, f, _A)
+    for k, v in kw.items():
+        setattr(t, k, v)
+    return t
+
+
+def _l0(**kw):
+    s = _lib.CgnnL0Src()
+    s.P0, s.W0, s.b0, s.F0 = _A, _A, _A, 5
+    for k, v in kw.items():
+        setattr(s, k, v)
+    return s
+
+
+def _tail(mode):
+    t = _lib.CgnnBnTail()
+    t.acc, t.count, t.mode = _A, 10.0, mode
+    for f in ("gamma", "beta", "running_mean", "running_var", "bn_out", "dgamma", "dbeta", "bwc"):
+        setattr(t, f, _A)
+    return t
+
+
+# defaults that pass every check (such a call would launch; every row below breaks at least one of them)
+_REFUSAL_DEFAULTS = {
+    "cgnn_gcn_fused_fwd_first": dict(t={}, X0=_A, F0=5, W0=_A, bias=_A, Y=_A, stat_slab=_A, stat_slab_bytes=4096,
+                                     stream=None),
+    "cgnn_gcn_fused_fwd": dict(t={}, Yprev=_A, l0=None, bn_prev=_A, p_drop=0.0, seed=0, seed_dev=None, mask_out=None,
+                               W=_A, bias=_A, Y=_A, stat_slab=_A, stat_slab_bytes=4096, tail=None, stream=None),
+    "cgnn_gcn_fused_bwd": dict(t={}, dZ=_A, Y=_A, bn=_A, bwc=_A, Yprev=_A, l0=None, bn_prev=_A, p_drop=0.0,
+                               mask_prev=None, W=_A, dZprev=_A, s_slab_prev=_A, s_slab_prev_bytes=4096, dW_slab=_A,
+                               dW_slab_bytes=65536, db_slab=_A, db_slab_bytes=2048, dP=None, node_graph=None,
+                               gptr=None, mask_cur=None, tail=None, stream=None),
+    "cgnn_gcn_fused_bwd_first": dict(t={}, dZ=_A, Y=_A, bn=_A, bwc=_A, X0=_A, F0=5, dW_slab=_A, dW_slab_bytes=16384,
+                                     db_slab=_A, db_slab_bytes=2048, p_drop=0.0, dP=None, node_graph=None, gptr=None,
+                                     mask_cur=None, stream=None),
+    "cgnn_gcn_fused_pool_bwd_sums": dict(dP=_A, F1=_A, F2=_A, gptr=_A, num_graphs=3, s_slab=_A, s_slab_bytes=4096,
+                                         stream=None),
+    "cgnn_gcn_fused_pool_bwd": dict(dP=_A, Y=_A, bn=_A, p_drop=0.0, mask=None, gptr=_A, num_graphs=3, dZ=_A,
+                                    s_slab=_A, s_slab_bytes=4096, stream=None),
+    "cgnn_aggregate_tiled_f32": dict(t={}, flags=0, X=_A, ldx=64, F=64, pre=None, post=None, bias=None, Yadd=None,
+                                     ldadd=0, Y=_A, ldy=64, stream=None),
+    "cgnn_aggregate_tiled_bn_f32": dict(t={}, flags=0, Z=_A, ldz=64, F=64, pre=None, post=None, bias=None, Y=_A,
+                                        ldy=64, coef=_A, relu=1, p_drop=0.0, seed=0, seed_dev=None, mask_out=None,
+                                        Xout=_A, ldxo=64, stream=None),
+    "cgnn_aggregate_tiled_f16": dict(t={}, flags=0, X=_A, ldx=64, F=64, pre=None, post=None, bias=None, Y=_A, ldy=64,
+                                     stream=None),
+}
+
+_FWD1, _FWD, _BWD, _BWD1 = ("cgnn_gcn_fused_fwd_first", "cgnn_gcn_fused_fwd", "cgnn_gcn_fused_bwd",
+                            "cgnn_gcn_fused_bwd_first")
+_PSUM, _PBWD = "cgnn_gcn_fused_pool_bwd_sums", "cgnn_gcn_fused_pool_bwd"
+_AGG, _AGGBN, _AGGH = "cgnn_aggregate_tiled_f32", "cgnn_aggregate_tiled_bn_f32", "cgnn_aggregate_tiled_f16"
+_POOLIN = dict(dP=_A, node_graph=_A, gptr=_A, dZ=None)
+
+_REFUSALS = [
+    # ---- first-layer forward
+    (_FWD1, dict(t=dict(null=True)), _INV),
+    (_FWD1, dict(t=dict(num_tiles=-1)), _INV),
+    (_FWD1, dict(t=dict(num_nodes=-1)), _INV),
+    (_FWD1, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_FWD1, dict(t=dict(max_tile_rows=385), F0=0), _UNS),            # the row limit decides, whatever else is wrong
+    (_FWD1, dict(t=dict(max_tile_rows=385, dis=None)), _UNS),
+    (_FWD1, dict(t=dict(dis=None)), _INV),
+    (_FWD1, dict(t=dict(ent_src=None)), _INV),
+    (_FWD1, dict(F0=0), _INV),
+    (_FWD1, dict(F0=17), _INV),
+    (_FWD1, dict(X0=None), _INV),
+    (_FWD1, dict(Y=None), _INV),
+    (_FWD1, dict(stat_slab_bytes=4095), _INV),
+    # ---- projection-first forward
+    (_FWD, dict(t=dict(null=True)), _INV),
+    (_FWD, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_FWD, dict(t=dict(max_tile_rows=385), W=None), _UNS),
+    (_FWD, dict(t=dict(tile_blk=None)), _INV),
+    (_FWD, dict(Yprev=None), _INV),                                  # neither Yprev nor a factored layer 0
+    (_FWD, dict(Yprev=None, l0=dict(F0=9)), _INV),
+    (_FWD, dict(Yprev=None, l0=dict(W0=None)), _INV),
+    (_FWD, dict(bn_prev=None), _INV),
+    (_FWD, dict(p_drop=1.0), _INV),
+    (_FWD, dict(p_drop=-0.5), _INV),
+    (_FWD, dict(tail=1), _INV),                                      # a backward tail on the forward
+    (_FWD, dict(stat_slab_bytes=4095), _INV),
+    # ---- backward
+    (_BWD, dict(t=dict(null=True)), _INV),
+    (_BWD, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_BWD, dict(t=dict(max_tile_rows=385), p_drop=1.0), _UNS),
+    (_BWD, dict(t=dict(blk_off_src=None)), _INV),
+    (_BWD, dict(W=None), _INV),
+    (_BWD, dict(Yprev=None), _INV),
+    (_BWD, dict(s_slab_prev=None), _INV),                            # no slab and no tail to take the sums
+    (_BWD, dict(p_drop=1.0), _INV),
+    (_BWD, dict(p_drop=0.5), _INV),                                  # dropout without mask_prev
+    (_BWD, dict(p_drop=0.5, mask_prev=0x1001), _INV),                # mask_prev is read as 4-byte words
+    (_BWD, dict(dZ=None), _INV),
+    (_BWD, dict(_POOLIN, gptr=None), _INV),
+    (_BWD, dict(_POOLIN, p_drop=0.5, mask_prev=_A), _INV),           # readout form with dropout needs mask_cur
+    (_BWD, dict(tail=0), _INV),                                      # a forward tail on the backward
+    (_BWD, dict(s_slab_prev_bytes=4095), _INV),
+    (_BWD, dict(dW_slab_bytes=65535), _INV),
+    (_BWD, dict(db_slab_bytes=2047), _INV),
+    # ---- first-layer backward
+    (_BWD1, dict(t=dict(null=True)), _INV),
+    (_BWD1, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_BWD1, dict(t=dict(max_tile_rows=385), F0=17), _UNS),
+    (_BWD1, dict(t=dict(tile_ptr=None)), _INV),
+    (_BWD1, dict(F0=0), _INV),
+    (_BWD1, dict(F0=17), _INV),
+    (_BWD1, dict(X0=None), _INV),
+    (_BWD1, dict(p_drop=1.0), _INV),
+    (_BWD1, dict(dZ=None), _INV),
+    (_BWD1, dict(_POOLIN, node_graph=None), _INV),
+    (_BWD1, dict(_POOLIN, p_drop=0.5), _INV),
+    (_BWD1, dict(dW_slab_bytes=16383), _INV),
+    (_BWD1, dict(db_slab_bytes=2047), _INV),
+    # ---- readout backward
+    (_PSUM, dict(num_graphs=-1), _INV),
+    (_PSUM, dict(F2=None), _INV),
+    (_PSUM, dict(s_slab=None), _INV),
+    (_PSUM, dict(s_slab_bytes=4095), _INV),
+    (_PBWD, dict(num_graphs=-1), _INV),
+    (_PBWD, dict(p_drop=1.0), _INV),
+    (_PBWD, dict(p_drop=0.5), _INV),                                 # dropout without its mask
+    (_PBWD, dict(Y=None), _INV),
+    (_PBWD, dict(s_slab=None), _INV),
+    (_PBWD, dict(s_slab_bytes=4095), _INV),
+    # ---- tiled aggregation, fp32: bad values first, then unsupported shapes, then an empty batch, then pointers
+    (_AGG, dict(t=dict(null=True)), _INV),
+    (_AGG, dict(t=dict(num_nodes=-1)), _INV),
+    (_AGG, dict(t=dict(num_tiles=-1)), _INV),
+    (_AGG, dict(F=0), _INV),
+    (_AGG, dict(F=0, t=dict(max_tile_rows=385)), _INV),
+    (_AGG, dict(ldx=63), _INV),
+    (_AGG, dict(ldy=63), _INV),
+    (_AGG, dict(Yadd=_A, ldadd=63), _INV),
+    (_AGG, dict(Yadd=_A, ldadd=60, F=96, ldx=96, ldy=96), _INV),
+    (_AGG, dict(F=96, ldx=96, ldy=96), _UNS),
+    (_AGG, dict(F=96, ldx=96, ldy=96, X=None), _UNS),
+    (_AGG, dict(ldx=66), _UNS),
+    (_AGG, dict(ldy=66), _UNS),
+    (_AGG, dict(Yadd=_A, ldadd=66), _UNS),
+    (_AGG, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_AGG, dict(X=_M), _UNS),
+    (_AGG, dict(Y=_M), _UNS),
+    (_AGG, dict(bias=_M), _UNS),
+    (_AGG, dict(Yadd=_M, ldadd=64), _UNS),
+    (_AGG, dict(X=_M, t=dict(num_tiles=0)), _UNS),
+    (_AGG, dict(X=None, t=dict(num_tiles=0)), _OK),                  # nothing to do comes before the NULL checks
+    (_AGG, dict(X=None, t=dict(num_nodes=0)), _OK),
+    (_AGG, dict(X=None), _INV),
+    (_AGG, dict(Y=None), _INV),
+    (_AGG, dict(t=dict(tile_ptr=None)), _INV),
+    (_AGG, dict(t=dict(tile_blk=None)), _INV),
+    (_AGG, dict(t=dict(ent_dst=None)), _INV),
+    (_AGG, dict(t=dict(blk_off_dst=None)), _INV),
+    (_AGG, dict(flags=1, t=dict(ent_src=None)), _INV),
+    (_AGG, dict(flags=1, t=dict(blk_off_src=None)), _INV),
+    # ---- tiled aggregation with the BatchNorm prologue
+    (_AGGBN, dict(t=dict(null=True)), _INV),
+    (_AGGBN, dict(F=0), _INV),
+    (_AGGBN, dict(ldz=63), _INV),
+    (_AGGBN, dict(ldxo=63), _INV),
+    (_AGGBN, dict(p_drop=1.0), _INV),
+    (_AGGBN, dict(p_drop=1.0, F=96, ldz=96, ldy=96, ldxo=96), _INV),
+    (_AGGBN, dict(coef=None), _INV),
+    (_AGGBN, dict(coef=None, t=dict(max_tile_rows=385)), _INV),
+    (_AGGBN, dict(Xout=None), _INV),
+    (_AGGBN, dict(F=96, ldz=96, ldy=96, ldxo=96), _UNS),
+    (_AGGBN, dict(ldz=66), _UNS),
+    (_AGGBN, dict(ldxo=66), _UNS),
+    (_AGGBN, dict(t=dict(max_tile_rows=385)), _UNS),
+    (_AGGBN, dict(Z=_M), _UNS),
+    (_AGGBN, dict(coef=_M), _UNS),
+    (_AGGBN, dict(Xout=_M), _UNS),
+    (_AGGBN, dict(Z=None, t=dict(num_tiles=0)), _OK),
+    (_AGGBN, dict(Z=None), _INV),
+    (_AGGBN, dict(Y=None), _INV),
+    (_AGGBN, dict(flags=1, t=dict(ent_src=None)), _INV),
+    # ---- tiled aggregation, fp16 storage: 8-element row strides, 1024-row tiles
+    (_AGGH, dict(t=dict(null=True)), _INV),
+    (_AGGH, dict(t=dict(num_tiles=-1)), _INV),
+    (_AGGH, dict(F=-64), _INV),
+    (_AGGH, dict(ldy=63), _INV),
+    (_AGGH, dict(F=96, ldx=96, ldy=96), _UNS),
+    (_AGGH, dict(ldx=68), _UNS),
+    (_AGGH, dict(ldy=68), _UNS),
+    (_AGGH, dict(t=dict(max_tile_rows=1025)), _UNS),
+    (_AGGH, dict(t=dict(max_tile_rows=1024), X=None), _INV),         # 1024 rows pass the limit; the NULL is what is wrong
+    (_AGGH, dict(X=_M), _UNS),
+    (_AGGH, dict(bias=_M), _UNS),
+    (_AGGH, dict(Y=None, t=dict(num_nodes=0)), _OK),
+    (_AGGH, dict(Y=None), _INV),
+    (_AGGH, dict(t=dict(tile_ptr=None)), _INV),
+    (_AGGH, dict(flags=1, t=dict(blk_off_src=None)), _INV),
+]
+
+
+def test_tile_entry_points_refuse_bad_arguments_with_the_documented_code():
+    lib = _lib.load()
+    assert lib.cgnn_set_fused_grid(_GRID) == _OK
+    keep = []                                    # structures passed by pointer stay alive over the call
+    got = []
+    try:
+        for name, bad, want in _REFUSALS:
+            args = dict(_REFUSAL_DEFAULTS[name])
+            unknown = set(bad) - set(args)
+            assert not unknown, (name, unknown)
+            args.update(bad)
+            t = _tiles(**args["t"]) if "t" in args else None
+            if "t" in args:
+                args["t"] = ctypes.byref(t) if t is not None else None
+            if isinstance(args.get("l0"), dict):
+                args["l0"] = ctypes.byref(_l0(**args["l0"]))
+            if isinstance(args.get("tail"), int):
+                args["tail"] = ctypes.byref(_tail(args["tail"]))
+            keep.append((t, args))
+            got.append((name, bad, want, getattr(lib, name)(*args.values())))
+    finally:
+        assert lib.cgnn_set_fused_grid(0) == _OK
+    wrong = [(n, b, w, g) for n, b, w, g in got if g != w]
+    assert not wrong, wrong

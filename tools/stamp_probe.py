@@ -20,8 +20,9 @@ from connectome_gnn_amd import _lib  # noqa: E402
 from connectome_gnn_amd.resident import assemble_batch  # noqa: E402
 from connectome_gnn_amd.synthetic import generate_packed  # noqa: E402
 
-NAMES = ["A:load+fill", "A:barrier", "B:meta commit", "B:aggregate", "B:stage+Afrag (bwd: mfma+epi)",
-         "B:mfma (fwd)", "end barrier", "B:epilogue (fwd)"]
+# k_gcn_fwd_first stamps slots 1-4 and 6, k_gcn_bwd slots 0-6; k_gcn_fwd_pf carries no stamps
+NAMES = ["A:load+fill", "A:barrier", "B:meta commit", "B:aggregate", "B:epilogue (bwd: mfma+epilogue)",
+         "B:readout staging (bwd)", "end barrier", "(unused)"]
 
 
 def read(lib):
@@ -54,10 +55,10 @@ def main():
     for _ in range(2):
         m(b).sum().backward()
     read(lib)
-    # forward only: layer 0 kernel + two generic kernels
+    # forward only: the layer 0 kernel is the one that is stamped
     out = m(b)
     st_f = read(lib)
-    show("forward (fwd_first + 2x fwd)", st_f)
+    show("forward (fwd_first)", st_f)
     if os.environ.get("PROBE_NODROP"):
         return
     out.sum().backward()
