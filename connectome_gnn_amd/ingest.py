@@ -74,6 +74,57 @@ launch (csrc/paths.hip): a workgroup keeps a subject's adjacency as a bitset in 
 bits, and so do two grids.  The fused GCN path takes ``in_channels <= 8``: a request of more than 8 columns trains on
 the wide path.
 
+Weighted shortest-path node measures: the names of ``WEIGHTED_PATH_MEASURES`` are accepted wherever
+``measures=`` is -- in ``node_measures``, ``from_matrices`` and ``from_timeseries`` -- in any order and mix with the
+other nine names.  Columns follow the order given.  Thresholds are selected once.  ``measures=True`` still stands for
+the five of ``MEASURES``.  A request without a weighted name launches exactly what it launches today and gives the
+same bits.  Everything is per subject, with matrix ``A``, threshold ``t`` and the existing edge test: ``e_ij`` iff
+``i != j``, ``A_ij > t`` and ``A_ij > 0``.  Nothing is symmetrised.
+
+Connection lengths:
+
+* ``wmax = max_{e_ij} A_ij``.
+* ``l_ij = wmax / A_ij`` where ``e_ij``, formed as one correctly rounded fp32 division.  Otherwise ``l_ij = +inf``.
+* So every length is ``>= 1``, and the strongest edge has length exactly ``1.0``.
+* Scaling a subject's matrix by a constant changes nothing.  This is the same normalisation that
+  ``weighted_clustering`` uses.
+* If all kept weights are equal, every length is exactly 1 and the weighted measures reduce to the binary ones.
+
+Distances:
+
+* ``dw_ij`` is the smallest sum of lengths along a directed path ``i -> ... -> j`` of kept edges.
+* ``dw_ii = 0``.
+* ``dw_ij = +inf`` when there is no path.
+* ``R_i = { j != i : dw_ij finite }`` and ``r_i = |R_i|``.  This is the same set as the binary ``R_i``.
+
+Measures:
+
+* ``weighted_nodal_efficiency``: ``(1 / (n - 1)) sum_{j in R_i} 1 / dw_ij``.  It is 0 for ``n == 1``.
+* ``weighted_closeness``: ``(r_i / (n - 1)) (r_i / sum_{j in R_i} dw_ij)`` if ``r_i > 0``, else 0 (Wasserman-Faust).
+* ``weighted_eccentricity``: ``max_{j in R_i} dw_ij / (n - 1)``.  It is 0 if ``r_i == 0`` or ``n == 1``.  It may
+  exceed 1.
+
+Special cases:
+
+* A subject without edges gives zeros.
+* NaN entries are never edges.
+* A subject with a kept non-finite weight gets unspecified values in these columns.  The call must still return,
+  which a fixed round count guarantees.
+
+Arithmetic:
+
+* Distances are fp32 sums of fp32 lengths.
+* The three row reductions (``sum 1/dw``, ``sum dw``, the max) are taken in fp64 in a fixed order and rounded to fp32
+  once.
+* No atomics.
+* No work assignment depends on the grid, so every run and every grid gives the same bits.
+
+One launch (csrc/wpaths.hip): a batched blocked Floyd-Warshall (min-plus), a workgroup per subject on a distance slab
+of its own in the workspace -- one slab per workgroup of the launch, not per subject, so nothing cohort-sized exists
+besides the output -- and ``n <= WEIGHTED_PATH_MAX_NODES = 1024`` (a ``ValueError`` beyond).  The cost is ``npad^3``
+relaxations per subject (``npad``: ``n`` rounded up to the block, 32 nodes to ``n = 512`` and 16 beyond) whatever the
+density.  ``path_lengths`` returns ``dw`` itself.
+
 Functional cohorts start one step earlier, as one ROI time series per subject:
 ``correlation_matrices`` / ``from_timeseries`` take ``timeseries`` -- float32, contiguous, ``[S, T, n]``, one row
 per frame, on a ROCm device -- and build the Pearson correlation matrices there (csrc/timeseries.hip).
@@ -108,6 +159,10 @@ _LIMIT = 2 ** 31
 MEASURES = ("strength", "degree", "mean_weight", "clustering", "weighted_clustering")   # ids: include/cgnn.h
 PATH_MEASURES = ("nodal_efficiency", "closeness", "eccentricity", "local_efficiency")      # ids: include/cgnn.h
 PATH_MAX_NODES = 1024                                 # CGNN_PATH_MAX_NODES: the adjacency bitset must fit LDS
+WEIGHTED_PATH_MEASURES = ("weighted_nodal_efficiency", "weighted_closeness", "weighted_eccentricity")   # ids: cgnn.h
+WEIGHTED_PATH_MAX_NODES = 1024                        # CGNN_WPATH_MAX_NODES: both panels of a round must fit LDS
+_ALL_MEASURES = MEASURES + PATH_MEASURES + WEIGHTED_PATH_MEASURES
+_CLASSIC, _PATH, _WEIGHTED = 0, 1, 2                  # the kind of a column: which call writes it
 
 
 def _check_matrices(matrices) -> tuple:
@@ -242,20 +297,22 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
 
 
 def _measure_ids(measures) -> list:
-    """A valid request, a non-empty tuple of distinct names, as one ``(is_path, id)`` per column: the id is the
-    position in PATH_MEASURES or in MEASURES."""
+    """A valid request, a non-empty tuple of distinct names, as one ``(kind, id)`` per column: the kind is _CLASSIC,
+    _PATH or _WEIGHTED, the id the position in MEASURES, PATH_MEASURES or WEIGHTED_PATH_MEASURES."""
     if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
-        raise TypeError(f"measures must be a tuple of names from {MEASURES + PATH_MEASURES}, got {measures!r}")
+        raise TypeError(f"measures must be a tuple of names from {_ALL_MEASURES}, got {measures!r}")
     if len(measures) == 0:
-        raise ValueError(f"measures is empty: name at least one of {MEASURES + PATH_MEASURES}")
+        raise ValueError(f"measures is empty: name at least one of {_ALL_MEASURES}")
     ids = []
     for name in measures:
         if name in MEASURES:
-            entry = (False, MEASURES.index(name))
+            entry = (_CLASSIC, MEASURES.index(name))
         elif name in PATH_MEASURES:
-            entry = (True, PATH_MEASURES.index(name))
+            entry = (_PATH, PATH_MEASURES.index(name))
+        elif name in WEIGHTED_PATH_MEASURES:
+            entry = (_WEIGHTED, WEIGHTED_PATH_MEASURES.index(name))
         else:
-            raise ValueError(f"unknown measure {name!r}: the measures are {MEASURES + PATH_MEASURES}")
+            raise ValueError(f"unknown measure {name!r}: the measures are {_ALL_MEASURES}")
         if entry in ids:
             raise ValueError(f"measure {name!r} is named twice")
         ids.append(entry)
@@ -263,9 +320,14 @@ def _measure_ids(measures) -> list:
 
 
 def _check_path_size(ids, n: int) -> None:
-    if ids is not None and n > PATH_MAX_NODES and any(is_path for is_path, _ in ids):
+    if ids is None:
+        return
+    if n > PATH_MAX_NODES and any(kind == _PATH for kind, _ in ids):
         raise ValueError(f"the path measures {PATH_MEASURES} take n <= {PATH_MAX_NODES} nodes (the adjacency bitset "
                          f"of a subject must fit LDS), got n = {n}")
+    if n > WEIGHTED_PATH_MAX_NODES and any(kind == _WEIGHTED for kind, _ in ids):
+        raise ValueError(f"the weighted path measures {WEIGHTED_PATH_MEASURES} take n <= {WEIGHTED_PATH_MAX_NODES} "
+                         f"nodes (both panels of a Floyd-Warshall round must fit LDS), got n = {n}")
 
 
 def _check_measures_argument(measures, node_features):
@@ -315,17 +377,42 @@ def _path_measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, id
                                          _lib.stream_ptr(dev)), "cgnn_ingest_paths")
 
 
+def _weighted_paths(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, cols: list, x,
+                    dist=None) -> None:
+    """Weighted path measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as they
+    are), and the distances into ``dist`` ``[S, n, n]`` if given.  The workspace is one slab per workgroup."""
+    if S == 0:
+        return
+    dev = matrices.device
+    lib = _lib.load()
+    num = len(ids)
+    arr, carr = (ctypes.c_int32 * num)(*ids), (ctypes.c_int32 * num)(*cols)
+    with _lib.device_guard(dev):
+        need = lib.cgnn_ingest_wpaths_workspace_bytes(S, n, arr, num)
+        if need < 0:
+            raise _lib.CgnnError(f"cgnn_ingest_wpaths_workspace_bytes({S}, {n}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cgnn_ingest_wpaths(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num, carr,
+                                          x.shape[2] if x is not None else 1, _lib.ptr(work), _lib.nbytes(work),
+                                          _lib.ptr(x), _lib.nbytes(x), _lib.ptr(dist), _lib.nbytes(dist),
+                                          _lib.stream_ptr(dev)), "cgnn_ingest_wpaths")
+
+
 def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
-    """``[S, n, len(ids)]``.  A request without path names is one cgnn_ingest_measures call, as before; otherwise the
-    path columns are written in place (cols / ldx) and the classic ones, if any, are that call's columns copied in."""
-    classic = [(c, i) for c, (is_path, i) in enumerate(ids) if not is_path]
-    paths = [(c, i) for c, (is_path, i) in enumerate(ids) if is_path]
-    if not paths:
+    """``[S, n, len(ids)]``.  A request of classic names only is one cgnn_ingest_measures call, as before; otherwise the
+    path columns and the weighted path columns are written in place (cols / ldx), one call each, and the classic ones,
+    if any, are that call's columns copied in."""
+    classic, paths, weighted = ([(c, i) for c, (kind, i) in enumerate(ids) if kind == k]
+                                for k in (_CLASSIC, _PATH, _WEIGHTED))
+    if not paths and not weighted:
         return _classic_measures(matrices, S, n, thr, [i for _, i in classic])
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
     if classic:
         x[:, :, [c for c, _ in classic]] = _classic_measures(matrices, S, n, thr, [i for _, i in classic])
-    _path_measures(matrices, S, n, thr, [i for _, i in paths], [c for c, _ in paths], x)
+    if paths:
+        _path_measures(matrices, S, n, thr, [i for _, i in paths], [c for c, _ in paths], x)
+    if weighted:
+        _weighted_paths(matrices, S, n, thr, [i for _, i in weighted], [c for c, _ in weighted], x)
     return x
 
 
@@ -338,8 +425,8 @@ def _threshold_tensor(min_weight, S: int, dev) -> torch.Tensor:
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   measures=MEASURES) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
-    ``matrices.device``, one column per name in ``measures``: names from ``MEASURES`` and ``PATH_MEASURES`` in any
-    order and mix (module docstring).  The thresholds are those ``from_matrices`` applies for the same ``keep`` /
+    ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES`` and
+    ``WEIGHTED_PATH_MEASURES`` in any order and mix (module docstring).  The thresholds are those ``from_matrices`` applies for the same ``keep`` /
     ``num_edges`` / ``min_weight``, selected once.  No read-back."""
     S, n = _check_matrices(matrices)
     if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
@@ -362,6 +449,36 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     return _measures(matrices, S, n, thr, ids)
 
 
+def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None) -> torch.Tensor:
+    """The weighted distances ``dw`` of the module docstring: float32 ``[S, n, n]`` on ``matrices.device``, ``+inf``
+    where ``j`` is not reached from ``i`` and a zero diagonal, at the thresholds ``from_matrices`` applies for the same
+    ``keep`` / ``num_edges`` / ``min_weight``.  This is the one call of this module whose output is cohort-sized: as
+    large as ``matrices`` itself.  The measures of ``WEIGHTED_PATH_MEASURES`` are formed from the same distances without
+    it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back."""
+    S, n = _check_matrices(matrices)
+    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
+        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
+    if min_weight is None:
+        _rank(n, keep, num_edges)
+    elif isinstance(min_weight, torch.Tensor):
+        if min_weight.shape != (S,) or not min_weight.is_floating_point():
+            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
+                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    else:
+        min_weight = float(min_weight)
+    if n > WEIGHTED_PATH_MAX_NODES:
+        raise ValueError(f"path_lengths takes n <= {WEIGHTED_PATH_MAX_NODES} nodes (both panels of a Floyd-Warshall "
+                         f"round must fit LDS), got n = {n}")
+    _require_resident(matrices)
+    if min_weight is None:
+        thr = select_thresholds(matrices, keep=keep, num_edges=num_edges)
+    else:
+        thr = _threshold_tensor(min_weight, S, matrices.device)
+    dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
+    _weighted_paths(matrices, S, n, thr, [], [], None, dist)
+    return dist
+
+
 def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> torch.Tensor:
     """Per subject, the off-diagonal entry of descending rank ``k`` (``[S]`` float32 on the matrices'
     device): the threshold that ``from_matrices`` applies for the same ``keep`` / ``num_edges``."""
@@ -379,8 +496,8 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   node_features=None, measures=None) -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
-    ``measures`` (a tuple of names from ``MEASURES`` and ``PATH_MEASURES``, or ``True`` for all of ``MEASURES``) ``x``
-    is ``node_measures`` at the thresholds of this call, which are selected once.
+    ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES`` and ``WEIGHTED_PATH_MEASURES``, or ``True``
+    for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call, which are selected once.
 
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""

@@ -508,6 +508,68 @@ int cgnn_ingest_paths(const float* matrices, int64_t S, int32_t n, const float* 
                       int32_t num_measures, const int32_t* cols, int32_t ldx, void* workspace,
                       int64_t workspace_bytes, float* x, int64_t x_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Weighted shortest-path node measures of the thresholded cohort.  matrices and thr as for
+ * cgnn_ingest_measures.  Everything is per subject, with matrix A, threshold t and the existing edge test: e_ij iff
+ * i != j, A_ij > t and A_ij > 0.  Nothing is symmetrised.
+ * Connection lengths
+ *   wmax = max_{e_ij} A_ij.
+ *   l_ij = wmax / A_ij where e_ij, formed as one correctly rounded fp32 division.  Otherwise l_ij = +inf.
+ *   So every length is >= 1, and the strongest edge has length exactly 1.0.
+ *   Scaling a subject's matrix by a constant changes nothing.  This is the same normalisation that
+ *   CGNN_MEASURE_WEIGHTED_CLUSTERING uses.
+ *   If all kept weights are equal, every length is exactly 1 and the weighted measures reduce to the binary ones.
+ * Distances
+ *   dw_ij is the smallest sum of lengths along a directed path i -> ... -> j of kept edges.
+ *   dw_ii = 0.
+ *   dw_ij = +inf when there is no path.
+ *   R_i = { j != i : dw_ij finite } and r_i = |R_i|.  This is the same set as the binary R_i.
+ * Measures
+ *   CGNN_WPATH_NODAL_EFFICIENCY  (1 / (n - 1)) sum_{j in R_i} 1 / dw_ij.  It is 0 for n == 1.
+ *   CGNN_WPATH_CLOSENESS         (r_i / (n - 1)) (r_i / sum_{j in R_i} dw_ij) if r_i > 0, else 0 (Wasserman-Faust).
+ *   CGNN_WPATH_ECCENTRICITY      max_{j in R_i} dw_ij / (n - 1).  It is 0 if r_i == 0 or n == 1.  It may exceed 1.
+ * Special cases
+ *   A subject without edges gives zeros.
+ *   NaN entries are never edges.
+ *   A subject with a kept non-finite weight gets unspecified values in these columns.  The call must still return,
+ *   which a fixed round count guarantees.
+ * Arithmetic
+ *   Distances are fp32 sums of fp32 lengths.
+ *   The three row reductions (sum 1/dw, sum dw, the max) are taken in fp64 in a fixed order and rounded to fp32 once.
+ *   No atomics.
+ *   No work assignment depends on the grid, so every run and every grid gives the same bits.
+ *
+ *   measures   HOST array of num_measures distinct ids, 0 <= num_measures <= CGNN_NUM_WPATH_MEASURES; 0 (measures,
+ *              cols and x may then be NULL) when only `dist` is asked for
+ *   cols, ldx  as for cgnn_ingest_paths: measure m of node i of subject s is written to
+ *              x[(s * n + i) * ldx + cols[m]]; the other columns of x are not touched
+ *   x          float [S, n, ldx]
+ *   dist       float [S, n, n] or NULL: dw itself, +inf where unreachable, a zero diagonal.  At least one of x and
+ *              dist is required.
+ *   workspace  cgnn_ingest_wpaths_workspace_bytes(S, n, measures, num_measures) bytes, 16-byte aligned: one distance
+ *              slab float [npad][npad] per WORKGROUP of the launch (not per subject), npad = n rounded up to the
+ *              block size; the count depends on cgnn_fused_grid() as it is when the call is made
+ * One launch on `stream`: min(S, w * cgnn_fused_grid()) workgroups of 8 waves (w = what the LDS of a CU admits, at
+ * most 4), a workgroup per subject with a grid stride, a batched blocked Floyd-Warshall (min-plus) on the subject's
+ * slab.  Blocks of 32 nodes while n rounded up to 32 is at most 512, of 16 beyond: the two panels of a round,
+ * 2 * block * npad floats, stay in LDS (136 KB at the largest n of either rule).  npad^3 relaxations per subject
+ * whatever the density.
+ * n > CGNN_WPATH_MAX_NODES, a NULL, misaligned or short buffer (the workspace included), S < 0, n <= 0,
+ * S * n >= 2^31, num_measures outside [0, CGNN_NUM_WPATH_MEASURES], an unknown or repeated id, ldx < 1, a column
+ * outside [0, ldx) or a repeated column, or neither x nor dist return CGNN_EINVAL before any launch (the byte count: a
+ * negative value); S == 0 returns CGNN_OK with nothing launched.  Element offsets are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_WPATH_NODAL_EFFICIENCY 0
+#define CGNN_WPATH_CLOSENESS 1
+#define CGNN_WPATH_ECCENTRICITY 2
+#define CGNN_NUM_WPATH_MEASURES 3
+#define CGNN_WPATH_MAX_NODES 1024
+int64_t cgnn_ingest_wpaths_workspace_bytes(int64_t S, int32_t n, const int32_t* measures, int32_t num_measures);
+int cgnn_ingest_wpaths(const float* matrices, int64_t S, int32_t n, const float* thr, const int32_t* measures,
+                       int32_t num_measures, const int32_t* cols, int32_t ldx, void* workspace,
+                       int64_t workspace_bytes, float* x, int64_t x_bytes, float* dist, int64_t dist_bytes,
+                       void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
