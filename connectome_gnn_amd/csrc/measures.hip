@@ -23,11 +23,13 @@
 //   k_measure_finish      a thread per (subject, node): the nt partials in ascending b, the measures, x[s, i, column].
 //
 // No atomics: the same bits on every run and for every grid.  Element offsets into `matrices` are 64-bit.
+// The request (1 to 5 distinct ids, packed columns), the cohort's size and its buffers are checked by
+// measure_request.h.
 #include <math.h>
 
-#include "common.h"
 #include "gram_tile.h"
 #include "ingest_rows.h"
+#include "measure_request.h"
 
 namespace {
 
@@ -200,10 +202,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_measure_tri(const float* __rest
   }
 }
 
-struct Columns {
-  int32_t col[CGNN_NUM_MEASURES];                           // column of x for each measure, -1 when it is not asked for
-  int32_t F;
-};
+typedef cgnn_columns<CGNN_NUM_MEASURES> Columns;
 
 __global__ __launch_bounds__(kFinishThreads) void k_measure_finish(int64_t S, int n, const int32_t* __restrict__ deg,
                                                                    const float* __restrict__ strength,
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(kFinishThreads) void k_measure_finish(int64_t S, in
     const int k = deg[r];
     const float si = strength[r], kf = (float)k;
     const float pairs = kf * (kf - 1.0f);
-    float* __restrict__ o = x + r * cols.F;
+    float* __restrict__ o = x + r * cols.ldx;
     if (cols.col[kStrength] >= 0) o[cols.col[kStrength]] = cgnn_strength_feature(si, sub[2 * s]);
     if (cols.col[kDegree] >= 0) o[cols.col[kDegree]] = n > 1 ? kf / (float)(n - 1) : 0.0f;
     if (cols.col[kMeanWeight] >= 0) o[cols.col[kMeanWeight]] = si / (kf + 1e-8f);
@@ -244,16 +243,10 @@ __global__ __launch_bounds__(kFinishThreads) void k_measure_finish(int64_t S, in
 #define CGNN_MEASURE_ROWS_PER_CU 4
 #endif
 
-// (CGNN_OK, the bitmask of the measures) of a valid list: 1 to 5 distinct ids
-int check_measures(const int32_t* measures, int32_t num, int* mask) {
-  if (!measures || num < 1 || num > CGNN_NUM_MEASURES) return CGNN_EINVAL;
-  int m = 0;
-  for (int i = 0; i < num; ++i) {
-    if (measures[i] < 0 || measures[i] >= CGNN_NUM_MEASURES || ((m >> measures[i]) & 1)) return CGNN_EINVAL;
-    m |= 1 << measures[i];
-  }
-  *mask = m;
-  return CGNN_OK;
+// (CGNN_OK, the packed columns) of a valid call: the cohort's size, then 1 to 5 distinct ids
+int check(int64_t S, int32_t n, const int32_t* measures, int32_t num, Columns* c) {
+  if (cgnn_check_cohort(S, n) != CGNN_OK) return CGNN_EINVAL;
+  return cgnn_check_request(measures, num, 1, nullptr, 0, false, c);
 }
 
 template <bool kWeights>
@@ -270,27 +263,22 @@ void launch_tri(const float* matrices, int64_t S, int32_t n, const float* thr, c
 
 extern "C" int64_t cgnn_ingest_measures_workspace_bytes(int64_t S, int32_t n, const int32_t* measures,
                                                         int32_t num_measures) {
-  int mask = 0;
-  if (cgnn_check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK)
-    return CGNN_EINVAL;
-  return layout_of(S, n, (mask >> kClustering) & 1, (mask >> kWeighted) & 1).total;
+  Columns c;
+  if (check(S, n, measures, num_measures, &c) != CGNN_OK) return CGNN_EINVAL;
+  return layout_of(S, n, c.col[kClustering] >= 0, c.col[kWeighted] >= 0).total;
 }
 
 extern "C" int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n, const float* thr,
                                     const int32_t* measures, int32_t num_measures, void* workspace,
                                     int64_t workspace_bytes, float* x, int64_t x_bytes, void* stream) {
-  int mask = 0;
-  if (cgnn_check_cohort(S, n) != CGNN_OK || check_measures(measures, num_measures, &mask) != CGNN_OK)
-    return CGNN_EINVAL;
+  Columns cols;
+  if (check(S, n, measures, num_measures, &cols) != CGNN_OK) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  if (!matrices || !thr || !workspace || !x) return CGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(matrices) & 3) || (reinterpret_cast<uintptr_t>(thr) & 3) ||
-      (reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+  if (!workspace || cgnn_check_cohort_buffers(matrices, thr, workspace, x, x_bytes, true, S * n, cols.ldx) != CGNN_OK)
     return CGNN_EINVAL;
-  const bool need_b = (mask >> kClustering) & 1, need_u = (mask >> kWeighted) & 1;
+  const bool need_b = cols.col[kClustering] >= 0, need_u = cols.col[kWeighted] >= 0;
   const Layout l = layout_of(S, n, need_b, need_u);
   CGNN_NEED_BYTES(workspace, workspace_bytes, l.total);
-  CGNN_NEED_BYTES(x, x_bytes, S * n * (int64_t)num_measures * (int64_t)sizeof(float));
   char* ws = static_cast<char*>(workspace);
   int32_t* deg = reinterpret_cast<int32_t*>(ws + l.k);
   float* strength = reinterpret_cast<float*>(ws + l.s);
@@ -309,10 +297,6 @@ extern "C" int cgnn_ingest_measures(const float* matrices, int64_t S, int32_t n,
     launch_tri<true>(matrices, S, n, thr, sub, part_u, hs);
     CGNN_CHECK_LAUNCH();
   }
-  Columns cols;
-  for (int m = 0; m < CGNN_NUM_MEASURES; ++m) cols.col[m] = -1;
-  for (int c = 0; c < num_measures; ++c) cols.col[measures[c]] = c;
-  cols.F = num_measures;
   const int64_t blocks = (S * n + kFinishThreads - 1) / kFinishThreads;
   k_measure_finish<<<cgnn_grid_for(blocks, 8), kFinishThreads, 0, hs>>>(S, n, deg, strength, sub, part_b, part_u, cols,
                                                                         x);

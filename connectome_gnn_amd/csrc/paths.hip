@@ -36,10 +36,12 @@
 // integers (sum_l count_l / l in ascending l; local: per source, sources in list order per group, groups folded in
 // lane order) and rounded to fp32 once.  No atomics, and no work assignment depends on the grid: the same bits on
 // every run and for every grid.  Element offsets into `matrices` and `x` are 64-bit.
+// The request (1 to 4 distinct ids, distinct columns below ldx), the cohort's size (n <= CGNN_PATH_MAX_NODES) and its
+// buffers are checked by measure_request.h, which also holds the LDS rules of the launch.
 #include <math.h>
 
-#include "common.h"
 #include "ingest_rows.h"
+#include "measure_request.h"
 
 namespace {
 
@@ -58,10 +60,7 @@ enum {
   kLocal = CGNN_PATH_LOCAL_EFFICIENCY
 };
 
-struct Columns {
-  int32_t col[CGNN_NUM_PATH_MEASURES];        // column of x for each measure, -1 when it is not asked for
-  int32_t ldx;
-};
+typedef cgnn_columns<CGNN_NUM_PATH_MEASURES> Columns;
 
 // words of a bitset row, and the entries of a wave's neighbour list (a multiple of 4: the lists stay 8-byte aligned)
 inline __host__ __device__ int words_of(int n) { return (n + 63) >> 6; }
@@ -242,41 +241,11 @@ __global__ __launch_bounds__(kThreads) void k_paths(const float* __restrict__ ma
   }
 }
 
-// (CGNN_OK, the columns) of a valid request: 1 to 4 distinct ids, distinct columns below ldx
-int check_request(const int32_t* measures, int32_t num, const int32_t* cols, int32_t ldx, Columns* out) {
-  if (!measures || num < 1 || num > CGNN_NUM_PATH_MEASURES) return CGNN_EINVAL;
-  for (int m = 0; m < CGNN_NUM_PATH_MEASURES; ++m) out->col[m] = -1;
-  for (int i = 0; i < num; ++i) {
-    if (measures[i] < 0 || measures[i] >= CGNN_NUM_PATH_MEASURES || out->col[measures[i]] >= 0) return CGNN_EINVAL;
-    out->col[measures[i]] = i;
-  }
-  if (!cols) return CGNN_OK;                  // the byte count does not depend on the columns
-  if (ldx < 1) return CGNN_EINVAL;
-  for (int i = 0; i < num; ++i) {
-    if (cols[i] < 0 || cols[i] >= ldx) return CGNN_EINVAL;
-    for (int j = 0; j < i; ++j)
-      if (cols[j] == cols[i]) return CGNN_EINVAL;
-    out->col[measures[i]] = cols[i];
-  }
-  out->ldx = ldx;
-  return CGNN_OK;
-}
-
-// (n <= CGNN_PATH_MAX_NODES is the stricter bound on n * n)
-int check_cohort(int64_t S, int32_t n) {
-  return n > CGNN_PATH_MAX_NODES ? CGNN_EINVAL : cgnn_check_cohort(S, n);
-}
-
-bool paths_attr() {
-  static bool done[CGNN_MAX_DEVICES] = {};
-  bool& d = done[cgnn_device_ordinal()];
-  if (!d) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_paths), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kLdsBytes) != hipSuccess)
-      return false;
-    d = true;
-  }
-  return true;
+// (CGNN_OK, the columns) of a valid call: the cohort's size, then 1 to 4 distinct ids and, with_cols, their columns
+int check(int64_t S, int32_t n, const int32_t* measures, int32_t num, const int32_t* cols, int32_t ldx, bool with_cols,
+          Columns* c) {
+  if (cgnn_check_cohort_upto(S, n, CGNN_PATH_MAX_NODES) != CGNN_OK) return CGNN_EINVAL;
+  return cgnn_check_request(measures, num, 1, cols, ldx, with_cols, c);
 }
 
 }  // namespace
@@ -284,8 +253,7 @@ bool paths_attr() {
 extern "C" int64_t cgnn_ingest_paths_workspace_bytes(int64_t S, int32_t n, const int32_t* measures,
                                                      int32_t num_measures) {
   Columns c;
-  if (check_cohort(S, n) != CGNN_OK || check_request(measures, num_measures, nullptr, 0, &c) != CGNN_OK)
-    return CGNN_EINVAL;
+  if (check(S, n, measures, num_measures, nullptr, 0, false, &c) != CGNN_OK) return CGNN_EINVAL;
   return 0;                                   // the one kernel keeps its state in LDS and registers
 }
 
@@ -293,22 +261,14 @@ extern "C" int cgnn_ingest_paths(const float* matrices, int64_t S, int32_t n, co
                                  const int32_t* measures, int32_t num_measures, const int32_t* cols, int32_t ldx,
                                  void* workspace, int64_t workspace_bytes, float* x, int64_t x_bytes, void* stream) {
   Columns c;
-  if (check_cohort(S, n) != CGNN_OK || !cols || check_request(measures, num_measures, cols, ldx, &c) != CGNN_OK)
-    return CGNN_EINVAL;
+  if (check(S, n, measures, num_measures, cols, ldx, true, &c) != CGNN_OK) return CGNN_EINVAL;
   if (workspace_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  if (!matrices || !thr || !x) return CGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(matrices) & 3) || (reinterpret_cast<uintptr_t>(thr) & 3) ||
-      (reinterpret_cast<uintptr_t>(x) & 3))
-    return CGNN_EINVAL;
-  // S * n < 2^31 and ldx < 2^31: the row count times ldx stays below 2^62, the byte count is compared by division
-  if (x_bytes < 0 || x_bytes / (int64_t)sizeof(float) / ldx < S * n) return CGNN_EINVAL;
+  if (cgnn_check_cohort_buffers(matrices, thr, workspace, x, x_bytes, true, S * n, ldx) != CGNN_OK) return CGNN_EINVAL;
   const size_t lds = lds_of(n);
   if (lds > (size_t)kLdsBytes) return CGNN_EINVAL;            // (n <= CGNN_PATH_MAX_NODES fits: 160 KB at 1024)
-  if (!paths_attr()) return CGNN_ELAUNCH;
-  // workgroups a CU holds: by LDS, and 8 waves each against 32 wave slots
-  int per_cu = (int)((size_t)kLdsBytes / lds);
-  per_cu = per_cu > 4 ? 4 : per_cu;
+  if (!cgnn_raise_lds_limit<k_paths>(kLdsBytes)) return CGNN_ELAUNCH;
+  const int per_cu = cgnn_wg_per_cu_by_lds(lds, kLdsBytes);
   k_paths<<<cgnn_grid_for(S, per_cu), kThreads, lds, cgnn_stream(stream)>>>(matrices, S, n, thr, c, x);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;

@@ -36,10 +36,12 @@
 // folded by a butterfly -- and rounded to fp32 once.  No atomics, and no work assignment depends on the grid: the
 // same bits on every run and for every grid.  The round count is fixed, so a kept non-finite weight cannot hang the
 // call.  Element offsets into `matrices`, `x`, `dist` and the workspace are 64-bit.
+// The request (0 to 3 distinct ids, distinct columns below ldx), the cohort's size (n <= CGNN_WPATH_MAX_NODES) and
+// its buffers are checked by measure_request.h, which also holds the LDS rules of the launch.
 #include <math.h>
 
-#include "common.h"
 #include "ingest_rows.h"
+#include "measure_request.h"
 
 namespace {
 
@@ -54,10 +56,7 @@ enum {
   kEccentricity = CGNN_WPATH_ECCENTRICITY
 };
 
-struct Columns {
-  int32_t col[CGNN_NUM_WPATH_MEASURES];       // column of x for each measure, -1 when it is not asked for
-  int32_t ldx;
-};
+typedef cgnn_columns<CGNN_NUM_WPATH_MEASURES> Columns;
 
 // the block rule, and what follows from it
 inline int block_of(int n) { return ((n + 31) & ~31) <= kWideNodes ? 32 : 16; }
@@ -298,61 +297,24 @@ __global__ __launch_bounds__(kThreads) void k_wpaths(const float* __restrict__ m
   }
 }
 
-// (CGNN_OK, the columns) of a valid request: 0 to 3 distinct ids, distinct columns below ldx
-int check_request(const int32_t* measures, int32_t num, const int32_t* cols, int32_t ldx, bool with_cols,
-                  Columns* out) {
-  if (num < 0 || num > CGNN_NUM_WPATH_MEASURES || (num > 0 && !measures)) return CGNN_EINVAL;
-  for (int m = 0; m < CGNN_NUM_WPATH_MEASURES; ++m) out->col[m] = -1;
-  out->ldx = 1;
-  for (int i = 0; i < num; ++i) {
-    if (measures[i] < 0 || measures[i] >= CGNN_NUM_WPATH_MEASURES || out->col[measures[i]] >= 0) return CGNN_EINVAL;
-    out->col[measures[i]] = i;
-  }
-  if (!with_cols || num == 0) return CGNN_OK;             // the byte count does not depend on the columns
-  if (!cols || ldx < 1) return CGNN_EINVAL;
-  for (int i = 0; i < num; ++i) {
-    if (cols[i] < 0 || cols[i] >= ldx) return CGNN_EINVAL;
-    for (int j = 0; j < i; ++j)
-      if (cols[j] == cols[i]) return CGNN_EINVAL;
-    out->col[measures[i]] = cols[i];
-  }
-  out->ldx = ldx;
-  return CGNN_OK;
+// (CGNN_OK, the columns) of a valid call: the cohort's size, then 0 to 3 distinct ids and, with_cols, their columns
+int check(int64_t S, int32_t n, const int32_t* measures, int32_t num, const int32_t* cols, int32_t ldx, bool with_cols,
+          Columns* c) {
+  if (cgnn_check_cohort_upto(S, n, CGNN_WPATH_MAX_NODES) != CGNN_OK) return CGNN_EINVAL;
+  return cgnn_check_request(measures, num, 0, cols, ldx, with_cols, c);
 }
 
-// (n <= CGNN_WPATH_MAX_NODES is the stricter bound on n * n)
-int check_cohort(int64_t S, int32_t n) {
-  return n > CGNN_WPATH_MAX_NODES ? CGNN_EINVAL : cgnn_check_cohort(S, n);
-}
-
-// workgroups a CU holds: by LDS, and 8 waves each against 32 wave slots
-int per_cu_of(size_t lds) {
-  const int by_lds = (int)((size_t)kLdsBytes / lds);
-  return by_lds > 4 ? 4 : by_lds;
-}
-
-template <int B>
-bool wpaths_attr() {
-  static bool done[CGNN_MAX_DEVICES] = {};
-  bool& d = done[cgnn_device_ordinal()];
-  if (!d) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_wpaths<B>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kLdsBytes) != hipSuccess)
-      return false;
-    d = true;
-  }
-  return true;
-}
+// the launch's workgroups: one per subject, as many as the CUs hold
+int grid_of(int64_t S, size_t lds) { return cgnn_grid_for(S, cgnn_wg_per_cu_by_lds(lds, kLdsBytes)); }
 
 }  // namespace
 
 extern "C" int64_t cgnn_ingest_wpaths_workspace_bytes(int64_t S, int32_t n, const int32_t* measures,
                                                       int32_t num_measures) {
   Columns c;
-  if (check_cohort(S, n) != CGNN_OK || check_request(measures, num_measures, nullptr, 0, false, &c) != CGNN_OK)
-    return CGNN_EINVAL;
+  if (check(S, n, measures, num_measures, nullptr, 0, false, &c) != CGNN_OK) return CGNN_EINVAL;
   const int B = block_of(n), npad = padded(n, B);
-  return cgnn_grid_for(S, per_cu_of(lds_of(npad, B))) * slab_bytes(npad);       // a slab per workgroup of the launch
+  return grid_of(S, lds_of(npad, B)) * slab_bytes(npad);       // a slab per workgroup of the launch
 }
 
 extern "C" int cgnn_ingest_wpaths(const float* matrices, int64_t S, int32_t n, const float* thr,
@@ -360,24 +322,22 @@ extern "C" int cgnn_ingest_wpaths(const float* matrices, int64_t S, int32_t n, c
                                   void* workspace, int64_t workspace_bytes, float* x, int64_t x_bytes, float* dist,
                                   int64_t dist_bytes, void* stream) {
   Columns c;
-  if (check_cohort(S, n) != CGNN_OK || check_request(measures, num_measures, cols, ldx, true, &c) != CGNN_OK)
-    return CGNN_EINVAL;
+  if (check(S, n, measures, num_measures, cols, ldx, true, &c) != CGNN_OK) return CGNN_EINVAL;
   if (workspace_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
   if (x_bytes < 0 || dist_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  if (!matrices || !thr || (num_measures > 0 && !x) || (num_measures == 0 && !dist)) return CGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(matrices) & 3) || (reinterpret_cast<uintptr_t>(thr) & 3) ||
-      (reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(dist) & 3))
+  // x [S n][ldx] if measures are asked for, dist [S n][n] if given (n <= 1024: by division too); one of the two
+  if (cgnn_check_cohort_buffers(matrices, thr, workspace, x, x_bytes, num_measures > 0, S * n, c.ldx) != CGNN_OK ||
+      cgnn_check_cohort_buffers(matrices, thr, workspace, dist, dist_bytes, dist != nullptr, S * n, n) != CGNN_OK ||
+      (num_measures == 0 && !dist))
     return CGNN_EINVAL;
-  // S * n < 2^31, ldx < 2^31 and n <= 1024: the byte counts are compared by division
-  if (num_measures > 0 && x_bytes / (int64_t)sizeof(float) / c.ldx < S * n) return CGNN_EINVAL;
-  if (dist && dist_bytes / (int64_t)sizeof(float) / n < S * n) return CGNN_EINVAL;
   const int B = block_of(n), npad = padded(n, B);
   const size_t lds = lds_of(npad, B);
   if (lds > (size_t)kLdsBytes) return CGNN_EINVAL;          // (n <= CGNN_WPATH_MAX_NODES fits: 136 KB at 512 and 1024)
-  const int grid = cgnn_grid_for(S, per_cu_of(lds));
+  const int grid = grid_of(S, lds);
   if (!workspace || workspace_bytes < grid * slab_bytes(npad)) return CGNN_EINVAL;
-  if (!(B == 32 ? wpaths_attr<32>() : wpaths_attr<16>())) return CGNN_ELAUNCH;
+  if (!(B == 32 ? cgnn_raise_lds_limit<k_wpaths<32>>(kLdsBytes) : cgnn_raise_lds_limit<k_wpaths<16>>(kLdsBytes)))
+    return CGNN_ELAUNCH;
   float* slabs = static_cast<float*>(workspace);
   float* xs = num_measures > 0 ? x : nullptr;
   if (B == 32)

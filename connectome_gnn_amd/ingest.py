@@ -149,6 +149,7 @@ A window sweep is ``from_timeseries`` called again on the same resident time ser
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -161,8 +162,27 @@ PATH_MEASURES = ("nodal_efficiency", "closeness", "eccentricity", "local_efficie
 PATH_MAX_NODES = 1024                                 # CGNN_PATH_MAX_NODES: the adjacency bitset must fit LDS
 WEIGHTED_PATH_MEASURES = ("weighted_nodal_efficiency", "weighted_closeness", "weighted_eccentricity")   # ids: cgnn.h
 WEIGHTED_PATH_MAX_NODES = 1024                        # CGNN_WPATH_MAX_NODES: both panels of a round must fit LDS
-_ALL_MEASURES = MEASURES + PATH_MEASURES + WEIGHTED_PATH_MEASURES
-_CLASSIC, _PATH, _WEIGHTED = 0, 1, 2                  # the kind of a column: which call writes it
+
+
+class _Family(NamedTuple):
+    """One C entry point and the measures it writes; a measure's id is its position in ``names``."""
+    names: tuple
+    call: str                                         # the byte-count query is call + "_workspace_bytes"
+    cols: bool                                        # takes cols / ldx: writes its columns inside a wider x
+    dist: bool                                        # takes dist / dist_bytes
+    max_nodes: Optional[int] = None                   # the largest n, and for the message who is limited and why
+    what: str = ""
+    why: str = ""
+
+
+_FAMILIES = (                                         # in the order of their calls
+    _Family(MEASURES, "cgnn_ingest_measures", False, False),
+    _Family(PATH_MEASURES, "cgnn_ingest_paths", True, False, PATH_MAX_NODES, "path measures",
+            "the adjacency bitset of a subject must fit LDS"),
+    _Family(WEIGHTED_PATH_MEASURES, "cgnn_ingest_wpaths", True, True, WEIGHTED_PATH_MAX_NODES,
+            "weighted path measures", "both panels of a Floyd-Warshall round must fit LDS"))
+_WEIGHTED = _FAMILIES[2]                              # path_lengths's
+_ALL_MEASURES = tuple(name for fam in _FAMILIES for name in fam.names)
 
 
 def _check_matrices(matrices) -> tuple:
@@ -195,6 +215,21 @@ def _rank(n: int, keep, num_edges) -> int:
     return min(num_edges, _LIMIT)                     # anything >= n (n - 1) keeps every positive entry
 
 
+def _threshold_choice(n: int, units: int, unit_name: str, keep, num_edges, min_weight) -> tuple:
+    """``(k, min_weight)`` of a valid choice, exactly one of the three: the rank ``k`` of ``keep=`` / ``num_edges=``
+    (``min_weight`` None), or ``k = 0`` and ``min_weight`` as a float or as the ``[units]`` tensor it is."""
+    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
+        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
+    if min_weight is None:
+        return _rank(n, keep, num_edges), None
+    if not isinstance(min_weight, torch.Tensor):
+        return 0, float(min_weight)
+    if min_weight.shape != (units,) or not min_weight.is_floating_point():
+        raise ValueError(f"a min_weight tensor must be floating point [{unit_name}] = [{units}], got "
+                         f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    return 0, min_weight
+
+
 def _require_resident(matrices: torch.Tensor) -> None:
     if not matrices.is_contiguous():
         raise ValueError("matrices must be contiguous")
@@ -202,6 +237,15 @@ def _require_resident(matrices: torch.Tensor) -> None:
         raise RuntimeError(
             f"matrices are on {matrices.device}: connectome_gnn_amd thresholds connectivity matrices on a "
             "ROCm device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+def _thresholds(matrices: torch.Tensor, S: int, keep, num_edges, min_weight) -> torch.Tensor:
+    """The ``[S]`` float32 thresholds of a valid choice on the matrices' device: selected there, or ``min_weight``."""
+    if min_weight is None:
+        return select_thresholds(matrices, keep=keep, num_edges=num_edges)
+    if isinstance(min_weight, torch.Tensor):
+        return min_weight.to(device=matrices.device, dtype=torch.float32).contiguous()
+    return torch.full((S,), min_weight, dtype=torch.float32, device=matrices.device)
 
 
 def _check_timeseries(timeseries, window, stride) -> tuple:
@@ -277,13 +321,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
     _check_path_size(_check_measures_argument(measures, node_features), n)
-    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
-        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
-    if min_weight is None:
-        _rank(n, keep, num_edges)
-    elif isinstance(min_weight, torch.Tensor) and (min_weight.shape != (U,) or not min_weight.is_floating_point()):
-        raise ValueError(f"a min_weight tensor must be floating point [U] = [{U}], got "
-                         f"{min_weight.dtype} {tuple(min_weight.shape)}")
+    _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
         raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
     if node_features is not None:
@@ -297,21 +335,15 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
 
 
 def _measure_ids(measures) -> list:
-    """A valid request, a non-empty tuple of distinct names, as one ``(kind, id)`` per column: the kind is _CLASSIC,
-    _PATH or _WEIGHTED, the id the position in MEASURES, PATH_MEASURES or WEIGHTED_PATH_MEASURES."""
+    """A valid request, a non-empty tuple of distinct names, as one ``(family, id)`` per column."""
     if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
         raise TypeError(f"measures must be a tuple of names from {_ALL_MEASURES}, got {measures!r}")
     if len(measures) == 0:
         raise ValueError(f"measures is empty: name at least one of {_ALL_MEASURES}")
     ids = []
     for name in measures:
-        if name in MEASURES:
-            entry = (_CLASSIC, MEASURES.index(name))
-        elif name in PATH_MEASURES:
-            entry = (_PATH, PATH_MEASURES.index(name))
-        elif name in WEIGHTED_PATH_MEASURES:
-            entry = (_WEIGHTED, WEIGHTED_PATH_MEASURES.index(name))
-        else:
+        entry = next(((fam, fam.names.index(name)) for fam in _FAMILIES if name in fam.names), None)
+        if entry is None:
             raise ValueError(f"unknown measure {name!r}: the measures are {_ALL_MEASURES}")
         if entry in ids:
             raise ValueError(f"measure {name!r} is named twice")
@@ -319,15 +351,16 @@ def _measure_ids(measures) -> list:
     return ids
 
 
+def _check_size(fam: _Family, n: int, subject=None) -> None:
+    if fam.max_nodes is not None and n > fam.max_nodes:
+        subject = subject or f"the {fam.what} {fam.names} take"
+        raise ValueError(f"{subject} n <= {fam.max_nodes} nodes ({fam.why}), got n = {n}")
+
+
 def _check_path_size(ids, n: int) -> None:
-    if ids is None:
-        return
-    if n > PATH_MAX_NODES and any(kind == _PATH for kind, _ in ids):
-        raise ValueError(f"the path measures {PATH_MEASURES} take n <= {PATH_MAX_NODES} nodes (the adjacency bitset "
-                         f"of a subject must fit LDS), got n = {n}")
-    if n > WEIGHTED_PATH_MAX_NODES and any(kind == _WEIGHTED for kind, _ in ids):
-        raise ValueError(f"the weighted path measures {WEIGHTED_PATH_MEASURES} take n <= {WEIGHTED_PATH_MAX_NODES} "
-                         f"nodes (both panels of a Floyd-Warshall round must fit LDS), got n = {n}")
+    for fam in _FAMILIES if ids is not None else ():
+        if any(f is fam for f, _ in ids):
+            _check_size(fam, n)
 
 
 def _check_measures_argument(measures, node_features):
@@ -339,114 +372,63 @@ def _check_measures_argument(measures, node_features):
     return _measure_ids(MEASURES if measures is True else measures)
 
 
-def _classic_measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
-    dev = matrices.device
-    lib = _lib.load()
-    F = len(ids)
-    arr = (ctypes.c_int32 * F)(*ids)
-    x = torch.empty(S, n, F, dtype=torch.float32, device=dev)
+def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x, dist=None):
+    """One call of ``fam``: measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as
+    they are; a family without ``cols`` fills ``x`` ``[S, n, len(ids)]`` in the order of ``ids``), and the distances into
+    ``dist`` ``[S, n, n]`` if given.  The workspace is what the family's query asks for: nothing for the paths, one slab
+    per workgroup for the weighted paths.  Returns ``x``."""
     if S == 0:
         return x
-    need = lib.cgnn_ingest_measures_workspace_bytes(S, n, arr, F)
-    if need < 0:
-        raise _lib.CgnnError(f"cgnn_ingest_measures_workspace_bytes({S}, {n}) refused its arguments")
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    with _lib.device_guard(dev):
-        _lib.check(lib.cgnn_ingest_measures(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, F, _lib.ptr(work),
-                                            _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x), _lib.stream_ptr(dev)),
-                   "cgnn_ingest_measures")
-    return x
-
-
-def _path_measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, cols: list,
-                   x: torch.Tensor) -> None:
-    """Path measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]``; the other columns stay as they are."""
-    if S == 0:
-        return
     dev = matrices.device
     lib = _lib.load()
     num = len(ids)
-    arr, carr = (ctypes.c_int32 * num)(*ids), (ctypes.c_int32 * num)(*cols)
-    need = lib.cgnn_ingest_paths_workspace_bytes(S, n, arr, num)
-    if need < 0:
-        raise _lib.CgnnError(f"cgnn_ingest_paths_workspace_bytes({S}, {n}) refused its arguments")
-    work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    with _lib.device_guard(dev):
-        _lib.check(lib.cgnn_ingest_paths(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num, carr, x.shape[2],
-                                         _lib.ptr(work), _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x),
-                                         _lib.stream_ptr(dev)), "cgnn_ingest_paths")
-
-
-def _weighted_paths(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, cols: list, x,
-                    dist=None) -> None:
-    """Weighted path measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as they
-    are), and the distances into ``dist`` ``[S, n, n]`` if given.  The workspace is one slab per workgroup."""
-    if S == 0:
-        return
-    dev = matrices.device
-    lib = _lib.load()
-    num = len(ids)
-    arr, carr = (ctypes.c_int32 * num)(*ids), (ctypes.c_int32 * num)(*cols)
-    with _lib.device_guard(dev):
-        need = lib.cgnn_ingest_wpaths_workspace_bytes(S, n, arr, num)
+    arr = (ctypes.c_int32 * num)(*ids)
+    args = [_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num]
+    if fam.cols:
+        args += [(ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1]
+    with _lib.device_guard(dev):                      # (the weighted paths' byte count depends on the device's grid)
+        need = getattr(lib, fam.call + "_workspace_bytes")(S, n, arr, num)
         if need < 0:
-            raise _lib.CgnnError(f"cgnn_ingest_wpaths_workspace_bytes({S}, {n}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cgnn_ingest_wpaths(_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num, carr,
-                                          x.shape[2] if x is not None else 1, _lib.ptr(work), _lib.nbytes(work),
-                                          _lib.ptr(x), _lib.nbytes(x), _lib.ptr(dist), _lib.nbytes(dist),
-                                          _lib.stream_ptr(dev)), "cgnn_ingest_wpaths")
+            raise _lib.CgnnError(f"{fam.call}_workspace_bytes({S}, {n}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        args += [_lib.ptr(work), _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x)]
+        if fam.dist:
+            args += [_lib.ptr(dist), _lib.nbytes(dist)]
+        _lib.check(getattr(lib, fam.call)(*args, _lib.stream_ptr(dev)), fam.call)
+    return x
 
 
 def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
-    """``[S, n, len(ids)]``.  A request of classic names only is one cgnn_ingest_measures call, as before; otherwise the
-    path columns and the weighted path columns are written in place (cols / ldx), one call each, and the classic ones,
-    if any, are that call's columns copied in."""
-    classic, paths, weighted = ([(c, i) for c, (kind, i) in enumerate(ids) if kind == k]
-                                for k in (_CLASSIC, _PATH, _WEIGHTED))
-    if not paths and not weighted:
-        return _classic_measures(matrices, S, n, thr, [i for _, i in classic])
+    """``[S, n, len(ids)]``, one call per family that is named.  A request of classic names only is one packed
+    cgnn_ingest_measures call, as before; the path families write their columns in place (cols / ldx)."""
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
-    if classic:
-        x[:, :, [c for c, _ in classic]] = _classic_measures(matrices, S, n, thr, [i for _, i in classic])
-    if paths:
-        _path_measures(matrices, S, n, thr, [i for _, i in paths], [c for c, _ in paths], x)
-    if weighted:
-        _weighted_paths(matrices, S, n, thr, [i for _, i in weighted], [c for c, _ in weighted], x)
+    for fam in _FAMILIES:
+        cols = [c for c, (f, _) in enumerate(ids) if f is fam]
+        fam_ids = [ids[c][1] for c in cols]
+        if not cols:
+            continue
+        if fam.cols or len(cols) == len(ids):
+            _run_family(fam, matrices, S, n, thr, fam_ids, cols, x)
+        else:
+            # cgnn_ingest_measures writes a packed block only, so in a mixed request its columns are copied in.  Removing
+            # this temporary takes a cols / ldx entry point for the classic family: another change (DESIGN.md 7).
+            x[:, :, cols] = _run_family(fam, matrices, S, n, thr, fam_ids, cols,
+                                        torch.empty(S, n, len(cols), dtype=torch.float32, device=matrices.device))
     return x
-
-
-def _threshold_tensor(min_weight, S: int, dev) -> torch.Tensor:
-    if isinstance(min_weight, torch.Tensor):
-        return min_weight.to(device=dev, dtype=torch.float32).contiguous()
-    return torch.full((S,), min_weight, dtype=torch.float32, device=dev)
 
 
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   measures=MEASURES) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
     ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES`` and
-    ``WEIGHTED_PATH_MEASURES`` in any order and mix (module docstring).  The thresholds are those ``from_matrices`` applies for the same ``keep`` /
-    ``num_edges`` / ``min_weight``, selected once.  No read-back."""
+    ``WEIGHTED_PATH_MEASURES`` in any order and mix (module docstring).  The thresholds are those ``from_matrices``
+    applies for the same ``keep`` / ``num_edges`` / ``min_weight``, selected once.  No read-back."""
     S, n = _check_matrices(matrices)
-    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
-        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
-    if min_weight is None:
-        _rank(n, keep, num_edges)
-    elif isinstance(min_weight, torch.Tensor):
-        if min_weight.shape != (S,) or not min_weight.is_floating_point():
-            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
-                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
-    else:
-        min_weight = float(min_weight)
+    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
     _require_resident(matrices)
-    if min_weight is None:
-        thr = select_thresholds(matrices, keep=keep, num_edges=num_edges)
-    else:
-        thr = _threshold_tensor(min_weight, S, matrices.device)
-    return _measures(matrices, S, n, thr, ids)
+    return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids)
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None) -> torch.Tensor:
@@ -456,26 +438,12 @@ def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weigh
     large as ``matrices`` itself.  The measures of ``WEIGHTED_PATH_MEASURES`` are formed from the same distances without
     it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back."""
     S, n = _check_matrices(matrices)
-    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
-        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
-    if min_weight is None:
-        _rank(n, keep, num_edges)
-    elif isinstance(min_weight, torch.Tensor):
-        if min_weight.shape != (S,) or not min_weight.is_floating_point():
-            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
-                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
-    else:
-        min_weight = float(min_weight)
-    if n > WEIGHTED_PATH_MAX_NODES:
-        raise ValueError(f"path_lengths takes n <= {WEIGHTED_PATH_MAX_NODES} nodes (both panels of a Floyd-Warshall "
-                         f"round must fit LDS), got n = {n}")
+    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    _check_size(_WEIGHTED, n, "path_lengths takes")
     _require_resident(matrices)
-    if min_weight is None:
-        thr = select_thresholds(matrices, keep=keep, num_edges=num_edges)
-    else:
-        thr = _threshold_tensor(min_weight, S, matrices.device)
+    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
-    _weighted_paths(matrices, S, n, thr, [], [], None, dist)
+    _run_family(_WEIGHTED, matrices, S, n, thr, [], [], None, dist)
     return dist
 
 
@@ -502,15 +470,7 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
     S, n = _check_matrices(matrices)
-    if sum(a is not None for a in (keep, num_edges, min_weight)) != 1:
-        raise ValueError("give exactly one of keep=, num_edges= and min_weight=")
-    k = 0 if min_weight is not None else _rank(n, keep, num_edges)
-    if isinstance(min_weight, torch.Tensor):
-        if min_weight.shape != (S,) or not min_weight.is_floating_point():
-            raise ValueError(f"a min_weight tensor must be floating point [S] = [{S}], got "
-                             f"{min_weight.dtype} {tuple(min_weight.shape)}")
-    elif min_weight is not None:
-        min_weight = float(min_weight)
+    k, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
         raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
     if node_features is not None:
@@ -525,9 +485,9 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     dev = matrices.device
     lib = _lib.load()
     if min_weight is None:
-        thr = torch.empty(S, dtype=torch.float32, device=dev)
+        thr = torch.empty(S, dtype=torch.float32, device=dev)     # cgnn_ingest_count selects them: no launch of its own
     else:
-        thr = _threshold_tensor(min_weight, S, dev)
+        thr = _thresholds(matrices, S, None, None, min_weight)
     row_count = torch.empty(S * n, dtype=torch.int32, device=dev)
     strength = None                                   # the default feature, unless x comes from elsewhere
     if node_features is None and ids is None:

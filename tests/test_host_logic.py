@@ -630,3 +630,219 @@ def test_tile_entry_points_refuse_bad_arguments_with_the_documented_code():
         assert lib.cgnn_set_fused_grid(0) == _OK
     wrong = [(n, b, w, g) for n, b, w, g in got if g != w]
     assert not wrong, wrong
+
+
+# ---- argument checks of the node-measure families (csrc/measure_request.h; measures.hip, paths.hip, wpaths.hip) ----
+# The same kind of table for cgnn_ingest_{measures,paths,wpaths} and their _workspace_bytes: one row = one call and
+# what it returns.  No row launches or reaches the HIP runtime: it is a refusal, a call with S == 0 (CGNN_OK before any
+# pointer is looked at) or a byte-count query.  S = 6 (wpaths: 3) subjects of n = 20 nodes, every measure of the family.
+_i32 = ctypes.c_int32
+_MEAS, _PATHS, _WPATHS = "cgnn_ingest_measures", "cgnn_ingest_paths", "cgnn_ingest_wpaths"
+_MEAS_WS, _PATHS_WS, _WPATHS_WS = (f + "_workspace_bytes" for f in (_MEAS, _PATHS, _WPATHS))
+_ID5, _ID4, _ID3 = (_i32 * 5)(0, 1, 2, 3, 4), (_i32 * 4)(0, 1, 2, 3), (_i32 * 3)(0, 1, 2)
+_COL4, _COL3 = (_i32 * 4)(5, 1, 2, 4), (_i32 * 3)(5, 1, 3)
+_A2 = 0x1002                     # a pointer that is not 4-byte aligned
+_EMPTY = dict(matrices=None, S=0, thr=None, workspace=None, workspace_bytes=0, x=None, x_bytes=0)
+_BIG_S = 2 ** 31 // 20 + 1       # S * n >= 2^31 at n = 20
+
+# defaults that pass every check (the three calls would launch; every row below breaks a check or has S == 0)
+_MEASURE_DEFAULTS = {
+    _MEAS_WS: dict(S=6, n=20, measures=_ID5, num=5),
+    _PATHS_WS: dict(S=6, n=20, measures=_ID4, num=4),
+    _WPATHS_WS: dict(S=3, n=20, measures=_ID3, num=3),
+    _MEAS: dict(matrices=_A, S=6, n=20, thr=_A, measures=_ID5, num=5, workspace=_A, workspace_bytes=5888, x=_A,
+                x_bytes=2400, stream=None),
+    _PATHS: dict(matrices=_A, S=6, n=20, thr=_A, measures=_ID4, num=4, cols=_COL4, ldx=7, workspace=_A,
+                 workspace_bytes=16, x=_A, x_bytes=3360, stream=None),
+    _WPATHS: dict(matrices=_A, S=3, n=20, thr=_A, measures=_ID3, num=3, cols=_COL3, ldx=6, workspace=_A,
+                  workspace_bytes=12288, x=_A, x_bytes=1440, dist=_A, dist_bytes=4800, stream=None),
+}
+
+_MEASURE_CALLS = [
+    # ---- byte counts: [k | s | (smax, wmax) | T(b) partials | T(u) partials]; none; a slab per workgroup at grid 4
+    (_MEAS_WS, dict(), 5888),
+    (_MEAS_WS, dict(measures=(_i32 * 2)(1, 0), num=2), 1280),        # no partial sums without clustering
+    (_MEAS_WS, dict(measures=(_i32 * 1)(3), num=1), 3584),
+    (_MEAS_WS, dict(S=0), 0),
+    (_MEAS_WS, dict(S=1, n=46340), 179537664),                       # the largest n with n * n < 2^31
+    (_MEAS_WS, dict(S=1, n=46341), _INV),
+    (_MEAS_WS, dict(S=-1), _INV),
+    (_MEAS_WS, dict(n=0), _INV),
+    (_MEAS_WS, dict(measures=None), _INV),
+    (_MEAS_WS, dict(measures=None, num=0), _INV),
+    (_MEAS_WS, dict(num=0), _INV),
+    (_MEAS_WS, dict(num=6), _INV),
+    (_MEAS_WS, dict(measures=(_i32 * 2)(3, 3), num=2), _INV),
+    (_MEAS_WS, dict(S=_BIG_S), _INV),
+    (_MEAS_WS, dict(n=46341), _INV),
+    (_PATHS_WS, dict(), 0),
+    (_PATHS_WS, dict(n=1024), 0),
+    (_PATHS_WS, dict(n=1025), _INV),
+    (_PATHS_WS, dict(S=-1), _INV),
+    (_PATHS_WS, dict(n=0), _INV),
+    (_PATHS_WS, dict(measures=None), _INV),
+    (_PATHS_WS, dict(measures=None, num=0), _INV),
+    (_PATHS_WS, dict(num=0), _INV),
+    (_PATHS_WS, dict(num=5), _INV),
+    (_PATHS_WS, dict(measures=(_i32 * 2)(3, 3), num=2), _INV),
+    (_PATHS_WS, dict(measures=(_i32 * 1)(4), num=1), _INV),
+    (_PATHS_WS, dict(S=_BIG_S), _INV),
+    (_WPATHS_WS, dict(), 12288),
+    (_WPATHS_WS, dict(measures=None, num=0), 12288),                 # distances alone: no measure is a request
+    (_WPATHS_WS, dict(S=100, n=84), 16 * 96 * 96 * 4),               # 4 workgroups a CU at 32 KB of LDS
+    (_WPATHS_WS, dict(S=100, n=360), 4 * 384 * 384 * 4),             # 1 at 104 KB
+    (_WPATHS_WS, dict(S=100, n=512), 4 * 512 * 512 * 4),             # blocks of 32 up to here: 136 KB
+    (_WPATHS_WS, dict(S=100, n=513), 8 * 528 * 528 * 4),             # of 16 beyond: 2 at 68 KB
+    (_WPATHS_WS, dict(n=1024), 3 * 1024 * 1024 * 4),
+    (_WPATHS_WS, dict(n=1025), _INV),
+    (_WPATHS_WS, dict(S=-1), _INV),
+    (_WPATHS_WS, dict(n=0), _INV),
+    (_WPATHS_WS, dict(measures=None), _INV),
+    (_WPATHS_WS, dict(num=4), _INV),
+    (_WPATHS_WS, dict(num=-1), _INV),
+    (_WPATHS_WS, dict(measures=(_i32 * 2)(2, 2), num=2), _INV),
+    (_WPATHS_WS, dict(measures=(_i32 * 1)(3), num=1), _INV),
+    (_WPATHS_WS, dict(S=_BIG_S), _INV),
+    # ---- cgnn_ingest_measures
+    (_MEAS, dict(workspace_bytes=5887), _INV),
+    (_MEAS, dict(x_bytes=2399), _INV),
+    (_MEAS, dict(x_bytes=-1), _INV),
+    (_MEAS, dict(workspace_bytes=-1), _INV),
+    (_MEAS, dict(matrices=None), _INV),
+    (_MEAS, dict(thr=None), _INV),
+    (_MEAS, dict(measures=None), _INV),
+    (_MEAS, dict(workspace=None), _INV),
+    (_MEAS, dict(x=None), _INV),
+    (_MEAS, dict(S=-1), _INV),
+    (_MEAS, dict(n=0), _INV),
+    (_MEAS, dict(n=-3), _INV),
+    (_MEAS, dict(S=_BIG_S), _INV),
+    (_MEAS, dict(n=46341), _INV),
+    (_MEAS, dict(num=0), _INV),
+    (_MEAS, dict(num=-1), _INV),
+    (_MEAS, dict(num=6), _INV),
+    (_MEAS, dict(measures=(_i32 * 5)(0, 1, 2, 3, 5)), _INV),
+    (_MEAS, dict(measures=(_i32 * 5)(0, -1, 2, 3, 4)), _INV),
+    (_MEAS, dict(measures=(_i32 * 5)(0, 1, 2, 3, 3)), _INV),
+    (_MEAS, dict(workspace=_M), _INV),
+    (_MEAS, dict(matrices=_A2), _INV),
+    (_MEAS, dict(thr=_A2), _INV),
+    (_MEAS, dict(x=_A2), _INV),
+    (_MEAS, dict(measures=None, num=0, x=None, x_bytes=0), _INV),    # no measure: only wpaths takes that
+    (_MEAS, dict(S=0), _OK),
+    (_MEAS, dict(_EMPTY), _OK),
+    (_MEAS, dict(_EMPTY, n=46340), _OK),
+    (_MEAS, dict(_EMPTY, n=46341), _INV),
+    (_MEAS, dict(_EMPTY, workspace=_M, workspace_bytes=-1, x_bytes=-1), _OK),   # buffers come after S == 0 here
+    (_MEAS, dict(_EMPTY, num=0), _INV),                              # the request comes before it
+    (_MEAS, dict(_EMPTY, measures=None, num=0), _INV),
+    (_MEAS, dict(_EMPTY, measures=None), _INV),
+    # ---- cgnn_ingest_paths
+    (_PATHS, dict(x_bytes=3359), _INV),
+    (_PATHS, dict(x_bytes=-1), _INV),
+    (_PATHS, dict(matrices=None), _INV),
+    (_PATHS, dict(thr=None), _INV),
+    (_PATHS, dict(measures=None), _INV),
+    (_PATHS, dict(cols=None), _INV),
+    (_PATHS, dict(x=None), _INV),
+    (_PATHS, dict(S=-1), _INV),
+    (_PATHS, dict(n=0), _INV),
+    (_PATHS, dict(n=-3), _INV),
+    (_PATHS, dict(n=1025), _INV),
+    (_PATHS, dict(S=_BIG_S), _INV),
+    (_PATHS, dict(num=0), _INV),
+    (_PATHS, dict(num=-1), _INV),
+    (_PATHS, dict(num=5), _INV),
+    (_PATHS, dict(measures=(_i32 * 4)(0, 1, 2, 4)), _INV),
+    (_PATHS, dict(measures=(_i32 * 4)(0, -1, 2, 3)), _INV),
+    (_PATHS, dict(measures=(_i32 * 4)(0, 1, 3, 3)), _INV),
+    (_PATHS, dict(cols=(_i32 * 4)(5, 1, 2, 7)), _INV),               # a column == ldx
+    (_PATHS, dict(cols=(_i32 * 4)(5, -1, 2, 4)), _INV),
+    (_PATHS, dict(cols=(_i32 * 4)(5, 1, 2, 5)), _INV),
+    (_PATHS, dict(ldx=5), _INV),
+    (_PATHS, dict(ldx=0), _INV),
+    (_PATHS, dict(workspace_bytes=-1), _INV),
+    (_PATHS, dict(workspace=_M), _INV),
+    (_PATHS, dict(matrices=_A2), _INV),
+    (_PATHS, dict(x=_A2), _INV),
+    (_PATHS, dict(thr=_A2), _INV),
+    (_PATHS, dict(ldx=2 ** 31 - 1), _INV),                           # S * n * ldx * 4 would wrap 64 bits
+    (_PATHS, dict(ldx=2 ** 30), _INV),
+    (_PATHS, dict(measures=None, num=0, cols=None, x=None, x_bytes=0), _INV),   # no measure: only wpaths takes that
+    (_PATHS, dict(S=0), _OK),
+    (_PATHS, dict(_EMPTY), _OK),
+    (_PATHS, dict(_EMPTY, n=1024), _OK),
+    (_PATHS, dict(_EMPTY, n=1025), _INV),
+    (_PATHS, dict(_EMPTY, ldx=2 ** 31 - 1), _OK),
+    (_PATHS, dict(_EMPTY, workspace_bytes=-1), _INV),                # these two come before S == 0
+    (_PATHS, dict(_EMPTY, workspace=_M), _INV),
+    (_PATHS, dict(_EMPTY, x_bytes=-1), _OK),                         # x's byte count after it
+    (_PATHS, dict(_EMPTY, num=0), _INV),
+    (_PATHS, dict(_EMPTY, measures=None, num=0, cols=None), _INV),
+    (_PATHS, dict(_EMPTY, cols=None), _INV),
+    # ---- cgnn_ingest_wpaths
+    (_WPATHS, dict(x_bytes=1439), _INV),
+    (_WPATHS, dict(dist_bytes=4799), _INV),
+    (_WPATHS, dict(workspace_bytes=12287), _INV),
+    (_WPATHS, dict(workspace=None), _INV),
+    (_WPATHS, dict(matrices=None), _INV),
+    (_WPATHS, dict(thr=None), _INV),
+    (_WPATHS, dict(measures=None), _INV),
+    (_WPATHS, dict(cols=None), _INV),
+    (_WPATHS, dict(x=None), _INV),
+    (_WPATHS, dict(S=-1), _INV),
+    (_WPATHS, dict(n=0), _INV),
+    (_WPATHS, dict(n=-3), _INV),
+    (_WPATHS, dict(n=1025), _INV),
+    (_WPATHS, dict(S=_BIG_S), _INV),
+    (_WPATHS, dict(num=-1), _INV),
+    (_WPATHS, dict(num=4), _INV),
+    (_WPATHS, dict(measures=(_i32 * 3)(0, 1, 3)), _INV),
+    (_WPATHS, dict(measures=(_i32 * 3)(0, -1, 2)), _INV),
+    (_WPATHS, dict(measures=(_i32 * 3)(0, 2, 2)), _INV),
+    (_WPATHS, dict(cols=(_i32 * 3)(5, 1, 6)), _INV),                 # a column == ldx
+    (_WPATHS, dict(cols=(_i32 * 3)(5, -1, 3)), _INV),
+    (_WPATHS, dict(cols=(_i32 * 3)(5, 1, 5)), _INV),
+    (_WPATHS, dict(ldx=5), _INV),
+    (_WPATHS, dict(ldx=0), _INV),
+    (_WPATHS, dict(workspace_bytes=-1), _INV),
+    (_WPATHS, dict(x_bytes=-1), _INV),
+    (_WPATHS, dict(dist_bytes=-1), _INV),
+    (_WPATHS, dict(workspace=_M), _INV),
+    (_WPATHS, dict(matrices=_A2), _INV),
+    (_WPATHS, dict(x=_A2), _INV),
+    (_WPATHS, dict(dist=_A2), _INV),
+    (_WPATHS, dict(thr=_A2), _INV),
+    (_WPATHS, dict(ldx=2 ** 31 - 1), _INV),
+    (_WPATHS, dict(ldx=2 ** 30), _INV),
+    (_WPATHS, dict(measures=None, num=0, cols=None, ldx=0, x=None, x_bytes=0, dist=None, dist_bytes=0), _INV),  # neither
+    (_WPATHS, dict(measures=None, num=0, cols=None, ldx=0, x=None, x_bytes=0, workspace_bytes=12287), _INV),
+    (_WPATHS, dict(S=0), _OK),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0), _OK),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, n=1024), _OK),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, n=1025), _INV),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, ldx=2 ** 31 - 1), _OK),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, workspace_bytes=-1), _INV),     # these four come before S == 0
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, workspace=_M), _INV),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=0, x_bytes=-1), _INV),
+    (_WPATHS, dict(_EMPTY, dist=None, dist_bytes=-1), _INV),
+    (_WPATHS, dict(_EMPTY, measures=None, num=0, cols=None, ldx=0, dist_bytes=0), _OK),   # distances alone, x NULL
+    (_WPATHS, dict(_EMPTY, cols=None, dist=None, dist_bytes=0), _INV),
+]
+
+
+def test_measure_entry_points_check_their_arguments_before_any_launch():
+    lib = _lib.load()
+    assert lib.cgnn_set_fused_grid(_GRID) == _OK
+    got = []
+    try:
+        for name, change, want in _MEASURE_CALLS:
+            args = dict(_MEASURE_DEFAULTS[name])
+            unknown = set(change) - set(args)
+            assert not unknown, (name, unknown)
+            args.update(change)
+            got.append((name, change, want, getattr(lib, name)(*args.values())))
+    finally:
+        assert lib.cgnn_set_fused_grid(0) == _OK
+    wrong = [(n, c, w, g) for n, c, w, g in got if g != w]
+    assert not wrong, wrong
