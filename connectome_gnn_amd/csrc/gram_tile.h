@@ -1,6 +1,7 @@
 // gram_tile.h -- THE tile walk of a symmetric product G = Z^T Z on the matrix pipe, defined once for k_corr
-// (timeseries.hip: Z = the centred, scaled frames of a window) and k_measure_tri (measures.hip: Z = the value map of
-// a thresholded connectivity matrix).  DESIGN.md 4.3c, 4.3d.
+// (timeseries.hip: Z = the centred, scaled frames of a window), k_measure_tri (measures.hip: Z = the value map of
+// a thresholded connectivity matrix) and k_partial (partial.hip: Z = the scaled inverse of a triangular factor, walked
+// from the first row that is not known to be zero).  DESIGN.md 4.3c, 4.3d, 4.3h.
 //
 // Z is never materialised.  A caller names a row-major source (float rows of n columns, `rows` of them) and a stage
 // functor that turns 4 loaded entries of row k into 4 entries of Z; it gets the 96 x 96 tile of G in registers.
@@ -149,14 +150,16 @@ __device__ __forceinline__ void load_panels(f32x4 (&pre)[2][kSlots], const float
   }
 }
 
-// The K loop of one item.  `pre` holds the loads of step 0 (load_panels at k0 = 0), and a barrier separates the
+// The K loop of one item over the rows k_begin .. rows - 1 (k_begin a multiple of kKS: a caller whose operand is
+// known to be zero above it, such as the inverse of a triangular factor, skips those rows; 0 walks them all).
+// `pre` holds the loads of the first step (load_panels at k0 = k_begin), and a barrier separates the
 // previous item's last LDS reads from this call.  stage(side, k, c, v) maps the 4 loaded entries v of row k, columns
 // c .. c + 3 of tile side `side` (c counted inside the tile), to what LDS holds for them.  On return acc is this
 // wave's 3 x 3 blocks and every wave is past its last read of the panels.
 template <bool kVec, class Stage>
 __device__ __forceinline__ void run(Panels& panel, f32x4 (&pre)[2][kSlots], f32x4 (&acc)[3][3],
                                     const float* __restrict__ base, int rows, int n, const Item& it, const Thread& th,
-                                    const Stage& stage) {
+                                    const Stage& stage, int k_begin = 0) {
   // registers -> LDS buffer `buf` for the step that starts at row k0
   auto store = [&](int buf, int k0) {
 #pragma unroll
@@ -168,7 +171,7 @@ __device__ __forceinline__ void run(Panels& panel, f32x4 (&pre)[2][kSlots], f32x
             stage(side, k0 + th.srow[q], th.scol[q], pre[side][q]);
     }
   };
-  store(0, 0);
+  store(0, k_begin);
   __syncthreads();
 
 #pragma unroll
@@ -176,18 +179,18 @@ __device__ __forceinline__ void run(Panels& panel, f32x4 (&pre)[2][kSlots], f32x
 #pragma unroll
     for (int b = 0; b < 3; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nks = (rows + kKS - 1) / kKS;
+  const int nks = (rows - k_begin + kKS - 1) / kKS;
   int cur = 0;
   for (int ks = 0; ks < nks; ++ks) {
     const bool more = ks + 1 < nks;
-    if (more) load_panels<kVec>(pre, base, rows, n, (ks + 1) * kKS, it, th);
+    if (more) load_panels<kVec>(pre, base, rows, n, k_begin + (ks + 1) * kKS, it, th);
     const float* __restrict__ pa = &panel[cur][0][th.frow * kLd + it.wr * 48 + th.fcol];
     const float* __restrict__ pb = &panel[cur][it.diag ? 0 : 1][th.frow * kLd + it.wc * 48 + th.fcol];
     if (it.mask == kAll) mma_step<kAll>(pa, pb, acc);
     else if (it.mask == kUpper) mma_step<kUpper>(pa, pb, acc);
     else if (it.mask == kFirst5) mma_step<kFirst5>(pa, pb, acc);
     else mma_step<kLast4>(pa, pb, acc);
-    if (more) store(cur ^ 1, (ks + 1) * kKS);
+    if (more) store(cur ^ 1, k_begin + (ks + 1) * kKS);
     __syncthreads();
     cur ^= 1;
   }

@@ -145,6 +145,33 @@ per frame, on a ROCm device -- and build the Pearson correlation matrices there 
 * Non-finite inputs are not checked; they propagate as IEEE says.
 
 A window sweep is ``from_timeseries`` called again on the same resident time series.
+
+Partial correlation: ``partial_correlation(matrices, shrinkage=a)`` turns correlation matrices
+``[U, n, n]`` into partial-correlation matrices there (csrc/partial.hip), and ``kind="partial"`` of
+``correlation_matrices`` / ``from_timeseries`` does so to the signed correlations of the time series, in place.
+Everything is per unit, with matrix ``R`` read from its UPPER triangle (``i <= j``) only.
+
+* ROI ``i`` with ``R_ii == 0`` -- the zero row and column ``correlation_matrices`` writes for a constant or masked
+  column -- is *excluded*: its pivot is taken as 1, so the factorisation of the others is untouched, and its row and
+  column of the output, diagonal included, are exactly ``0.0``.
+* ``C = (1 - a) R + a I`` over the other ROIs, ``a = shrinkage`` in ``[0, 1]``.
+* ``P = C^-1``.  For ``i != j``, ``out_ij = -P_ij / sqrt(P_ii P_jj)``, clamped to ``[-1, 1]``; ``out_ii`` is exactly
+  ``1.0``; ``out_ij`` and ``out_ji`` are the same bits.  ``absolute=True`` stores ``|out|`` (with ``kind="partial"``
+  it applies to the partial values; the correlation underneath stays signed).
+* A unit whose factorisation meets a pivot ``<= 0`` or a NaN gets an all-NaN matrix.  NaN entries are never edges, so
+  ``from_matrices`` gives that unit no edges.  The round counts are fixed: the call always returns.
+* ``shrinkage == 0`` needs at least ``n + 2`` frames per unit: with fewer the correlation matrix is singular by
+  construction (a ``ValueError`` from ``correlation_matrices`` / ``from_timeseries``; give ``shrinkage > 0``).
+  Estimating ``a`` from the frames (Ledoit-Wolf) is not done here.
+
+Arithmetic: ``C = U^T U`` (blocked Cholesky, upper), ``W = U^-T``, ``P = W^T W``.  Storage and products are fp32,
+every sum in ascending order, the trailing updates and ``W^T W`` on the fp32 matrix pipe.  The reciprocal pivots, the
+shrunk diagonal and the scales ``1 / sqrt(P_ii)`` (``P_ii`` summed in fp64) are formed in fp64 and rounded to fp32
+once.  No atomics, and no work assignment depends on the grid: every run and every grid gives the same bits.
+
+One launch: a workgroup per unit on a slab of its own in the workspace -- one slab per workgroup of the launch, not
+per unit, so nothing cohort-sized exists besides the output -- and ``n <= PARTIAL_MAX_NODES = 1024`` (a ``ValueError``
+beyond: the row panel of a round must fit LDS).  About ``n^3`` multiply-adds per unit.  No solver library is called.
 """
 from __future__ import annotations
 
@@ -162,6 +189,8 @@ PATH_MEASURES = ("nodal_efficiency", "closeness", "eccentricity", "local_efficie
 PATH_MAX_NODES = 1024                                 # CGNN_PATH_MAX_NODES: the adjacency bitset must fit LDS
 WEIGHTED_PATH_MEASURES = ("weighted_nodal_efficiency", "weighted_closeness", "weighted_eccentricity")   # ids: cgnn.h
 WEIGHTED_PATH_MAX_NODES = 1024                        # CGNN_WPATH_MAX_NODES: both panels of a round must fit LDS
+PARTIAL_MAX_NODES = 1024                              # CGNN_PARTIAL_MAX_NODES: the row panel of a round must fit LDS
+KINDS = ("correlation", "partial")                    # correlation_matrices's kind=
 
 
 class _Family(NamedTuple):
@@ -303,23 +332,99 @@ def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, abso
     return out
 
 
-def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False) -> torch.Tensor:
+def _check_shrinkage(shrinkage) -> float:
+    if isinstance(shrinkage, bool) or not isinstance(shrinkage, (int, float)):
+        raise TypeError(f"shrinkage must be a float, got {type(shrinkage).__name__}")
+    shrinkage = float(shrinkage)
+    if not 0.0 <= shrinkage <= 1.0:                   # (a NaN is refused here too)
+        raise ValueError(f"shrinkage must lie in [0, 1], got {shrinkage}")
+    return shrinkage
+
+
+def _check_partial_size(n: int) -> None:
+    if n > PARTIAL_MAX_NODES:
+        raise ValueError(f"partial correlation takes n <= {PARTIAL_MAX_NODES} nodes (the row panel of a round must "
+                         f"fit LDS), got n = {n}")
+
+
+def _check_kind(kind, shrinkage, n: int, L: int) -> float:
+    """The shrinkage of a valid (kind, shrinkage) for units of L frames and n ROIs."""
+    if kind not in KINDS:
+        raise ValueError(f"unknown kind {kind!r}: the kinds are {KINDS}")
+    shrinkage = _check_shrinkage(shrinkage)
+    if kind == "correlation":
+        if shrinkage != 0.0:
+            raise ValueError('shrinkage applies to kind="partial"; kind="correlation" takes shrinkage=0')
+        return shrinkage
+    _check_partial_size(n)
+    if shrinkage == 0.0 and L < n + 2:
+        raise ValueError(f"the correlation matrix of {L} frames and n = {n} ROIs is singular by construction (a "
+                         f"partial correlation without shrinkage needs at least n + 2 = {n + 2} frames per unit): "
+                         "give shrinkage > 0")
+    return shrinkage
+
+
+def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage: float, absolute: bool, out: torch.Tensor):
+    """cgnn_ingest_partial of resident matrices into ``out``, which may be ``matrices``.  The workspace is what the
+    query asks for: one slab per workgroup of the launch."""
+    if U == 0:
+        return out
+    dev = matrices.device
+    lib = _lib.load()
+    with _lib.device_guard(dev):                      # (the byte count depends on the device's grid)
+        need = lib.cgnn_ingest_partial_workspace_bytes(U, n)
+        if need < 0:
+            raise _lib.CgnnError(f"cgnn_ingest_partial_workspace_bytes({U}, {n}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cgnn_ingest_partial(_lib.ptr(matrices), U, n, shrinkage, int(bool(absolute)), _lib.ptr(work),
+                                           _lib.nbytes(work), _lib.ptr(out), _lib.nbytes(out),
+                                           _lib.stream_ptr(dev)), "cgnn_ingest_partial")
+    return out
+
+
+def partial_correlation(matrices: torch.Tensor, *, shrinkage=0.0, absolute=False) -> torch.Tensor:
+    """Partial correlation of every unit's correlation matrix: ``[U, n, n]`` float32 on ``matrices.device`` (module
+    docstring).  ``matrices`` are read from their upper triangles and left as they are.  One launch on resident data;
+    the only temporary is the workspace, one slab per workgroup.  No read-back."""
+    U, n = _check_matrices(matrices)
+    shrinkage = _check_shrinkage(shrinkage)
+    _check_partial_size(n)
+    _require_resident(matrices)
+    return _partial(matrices, U, n, shrinkage, absolute, torch.empty_like(matrices))
+
+
+def _connectivity(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, kind: str,
+                  shrinkage: float) -> torch.Tensor:
+    """The matrices of a valid request: the correlations, or the partial correlations of the signed correlations
+    written over them (no second cohort-sized tensor)."""
+    if kind == "correlation":
+        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute)
+    matrices = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
+    return _partial(matrices, S * W, n, shrinkage, absolute, matrices)
+
+
+def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
+                         shrinkage=0.0) -> torch.Tensor:
     """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
-    (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics."""
+    (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics.
+    ``kind="partial"`` gives ``partial_correlation`` of the signed correlations at ``shrinkage``, written in place
+    over them by a third launch; ``absolute`` then applies to the partial values."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    shrinkage = _check_kind(kind, shrinkage, n, L)
     _require_resident_timeseries(timeseries)
-    return _correlate(timeseries, S, T, n, L, W, st, window is not None, absolute)
+    return _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage)
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                    window=None, stride=None, absolute=False, node_features=None,
-                    measures=None) -> RaggedPackedDataset:
+                    window=None, stride=None, absolute=False, node_features=None, measures=None,
+                    kind="correlation", shrinkage=0.0) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
-    if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s.  The one
-    read-back is ``from_matrices``'s."""
+    if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
+    ``shrinkage`` are ``correlation_matrices``'s.  The one read-back is ``from_matrices``'s."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
+    shrinkage = _check_kind(kind, shrinkage, n, L)
     _check_path_size(_check_measures_argument(measures, node_features), n)
     _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
@@ -329,7 +434,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
                 or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (U, n):
             raise ValueError(f"node_features must be a float32 tensor [U, n, F] = [{U}, {n}, F]")
     _require_resident_timeseries(timeseries)
-    matrices = _correlate(timeseries, S, T, n, L, W, st, window is not None, absolute)
+    matrices = _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
                          num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
 

@@ -570,6 +570,37 @@ int cgnn_ingest_wpaths(const float* matrices, int64_t S, int32_t n, const float*
                        int64_t workspace_bytes, float* x, int64_t x_bytes, float* dist, int64_t dist_bytes,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Partial-correlation matrices from correlation matrices.  matrices: float [U, n, n], as
+ * cgnn_ingest_corr writes them (signed).  Per unit with matrix R, read from its UPPER triangle (i <= j) only:
+ *   excluded   ROI i iff R_ii == 0 (a constant column: the zero row and column of cgnn_ingest_corr).  Its pivot is
+ *              taken as 1, so the others are untouched; its row and column of the output, diagonal included, are 0.
+ *   C          (1 - shrinkage) R + shrinkage I over the ROIs that are not excluded, shrinkage in [0, 1]
+ *   output     P = C^-1;  out_ij = -P_ij / sqrt(P_ii P_jj) clamped to [-1, 1] for i != j, out_ii = 1 exactly; out_ij
+ *              and out_ji are the same bits (one is the mirror store of the other); absolute != 0 stores |out|.
+ *   failure    a unit whose factorisation meets a pivot that is not > 0 (a NaN is not), or a P_ii that is not finite
+ *              and positive, gets an all-NaN matrix.  The round counts are fixed: the call always returns.
+ *   arithmetic C = U^T U, W = U^-T, P = W^T W.  Storage and products are fp32, every sum k ascending, the trailing
+ *              updates and W^T W on the fp32 matrix pipe.  The reciprocal pivots 1 / u_kk, the shrunk diagonal and the
+ *              scales 1 / sqrt(P_ii) (P_ii summed in fp64) are formed in fp64 and rounded to fp32 once.
+ *   out        float [U, n, n]; may be `matrices` itself: a unit is read whole before its first entry is written
+ *   workspace  cgnn_ingest_partial_workspace_bytes(U, n) bytes, 16-byte aligned: one slab float [npad][npad] per
+ *              WORKGROUP of the launch (not per unit), npad = n rounded up to 32; the count depends on
+ *              cgnn_fused_grid() as it is when the call is made
+ * One launch on `stream`: min(U, w * cgnn_fused_grid()) workgroups of 4 waves (w = what the LDS of a CU admits), a
+ * workgroup per unit with a grid stride: a right-looking blocked factorisation of [C | I] in blocks of 32 (the row
+ * panel of a round, 32 * (npad + 16) floats, stays in LDS: 151 KB of it at n = 1024), then the 96 x 96 tile walk of
+ * cgnn_ingest_corr over W^T W.  ~ n^3 multiply-adds per unit.  No atomics, nothing depends on the grid: the same bits
+ * on every run and for every grid.
+ * n > CGNN_PARTIAL_MAX_NODES, a NULL, misaligned or short buffer (the workspace included), U < 0, n <= 0,
+ * U * n >= 2^31, shrinkage outside [0, 1] or NaN return CGNN_EINVAL before any launch (the byte count: a negative
+ * value); U == 0 returns CGNN_OK with nothing launched.  Element offsets are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_PARTIAL_MAX_NODES 1024
+int64_t cgnn_ingest_partial_workspace_bytes(int64_t U, int32_t n);
+int cgnn_ingest_partial(const float* matrices, int64_t U, int32_t n, double shrinkage, int32_t absolute,
+                        void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
