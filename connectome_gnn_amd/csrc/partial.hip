@@ -1,11 +1,13 @@
 // partial.hip -- partial-correlation matrices of a device-resident cohort of correlation matrices (float [U, n, n] ->
-// float [U, n, n], in place if asked): cgnn_ingest_partial, cgnn_ingest_partial_workspace_bytes.
+// float [U, n, n], in place if asked): cgnn_ingest_partial, cgnn_ingest_partial_each (a shrinkage per
+// unit, read on the device: DESIGN.md 4.3i), cgnn_ingest_partial_workspace_bytes.
 //
 // Per unit with matrix R, read from its UPPER triangle (i <= j) only: ROI i is excluded iff R_ii == 0 (the zero row
 // and column k_corr writes for a constant column); C = (1 - a) R + a I over the others, a = shrinkage, and the
 // identity on the excluded ones; P = C^-1; out_ij = -P_ij / sqrt(P_ii P_jj) clamped to [-1, 1], out_ii = 1, zero rows
 // and columns (diagonal included) for the excluded ROIs, |.| if asked.  A unit whose factorisation meets a pivot
-// that is not > 0 (a NaN is not), or a P_ii that is not finite and > 0, is all NaN.
+// that is not > 0 (a NaN is not), or a P_ii that is not finite and > 0, is all NaN; so is, with a shrinkage per unit,
+// a unit whose own is not in [0, 1] (the kernel is its first reader).
 //
 //   k_partial   one launch.  A workgroup of 4 waves owns a unit, grid stride; its slab [npad][npad] fp32, npad = n
 //               rounded up to the block of 32, is workgroup blockIdx.x's slice of the workspace (one slab per workgroup
@@ -60,9 +62,10 @@ inline size_t lds_of(int n) {
              sizeof(float);
 }
 
-template <bool kVecOut>
-__global__ __launch_bounds__(kThreads, 2) void k_partial(const float* matrices, int64_t U, int n, double alpha,
-                                                      int absolute, float* slabs, float* out) {
+template <bool kVecOut, bool kEach>
+__global__ __launch_bounds__(kThreads, 2) void k_partial(const float* matrices, int64_t U, int n, double shrinkage,
+                                                      const double* __restrict__ alphas, int absolute, float* slabs,
+                                                      float* out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int frow = lane >> 4, fcol = lane & 15;           // a lane's row and column in a fragment (gram_tile.h)
@@ -77,11 +80,18 @@ __global__ __launch_bounds__(kThreads, 2) void k_partial(const float* matrices, 
   float* panel = lkk + kB * kB;                           // [kB][ldp]  block row K of [U | W]
   Panels& prod = *reinterpret_cast<Panels*>(panel);
   float* D = slabs + (int64_t)blockIdx.x * npad * npad;
-  const float om = (float)(1.0 - alpha);
 
   for (int64_t u = blockIdx.x; u < U; u += gridDim.x) {
     const float* R = matrices + u * (int64_t)n * n;       // (may be `o`: not restrict)
     float* o = out + u * (int64_t)n * n;
+    // the unit's own shrinkage, if there is one per unit: nobody has read it before now, so a value that is not in
+    // [0, 1] (a NaN is not) is refused here, by the failure path's all-NaN matrix
+    const double alpha = kEach ? alphas[u] : shrinkage;
+    const float om = (float)(1.0 - alpha);
+    if (kEach && !(alpha >= 0.0 && alpha <= 1.0)) {
+      for (int64_t e = t; e < (int64_t)n * n; e += kThreads) o[e] = NAN;
+      continue;                               // (uniform: the whole workgroup leaves, no LDS is touched)
+    }
 
     // ---- build ----
     for (int i = t; i < nd; i += kThreads) scale[i] = i < n && R[(int64_t)i * n + i] != 0.0f ? 1.0f : 0.0f;
@@ -295,6 +305,38 @@ int check(int64_t U, int32_t n) { return cgnn_check_cohort_upto(U, n, CGNN_PARTI
 // the launch's workgroups: one per unit, as many as the CUs hold
 int grid_of(int64_t U, size_t lds) { return cgnn_grid_for(U, cgnn_wg_per_cu_by_lds(lds, kLdsBytes)); }
 
+template <bool kVecOut, bool kEach>
+int launch_as(int grid, size_t lds, const float* matrices, int64_t U, int32_t n, double shrinkage, const double* alphas,
+              int32_t absolute, float* slabs, float* out, void* stream) {
+  if (!cgnn_raise_lds_limit<k_partial<kVecOut, kEach>>(kLdsBytes)) return CGNN_ELAUNCH;
+  k_partial<kVecOut, kEach><<<grid, kThreads, lds, cgnn_stream(stream)>>>(matrices, U, n, shrinkage, alphas, absolute,
+                                                                         slabs, out);
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
+}
+
+// Both entry points: the checks, then the one launch.  each: alphas[u] is unit u's shrinkage; else `shrinkage` is all's.
+int launch(const float* matrices, int64_t U, int32_t n, double shrinkage, const double* alphas, bool each,
+           int32_t absolute, void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream) {
+  if (check(U, n) != CGNN_OK || !(shrinkage >= 0.0 && shrinkage <= 1.0)) return CGNN_EINVAL;
+  if (workspace_bytes < 0 || out_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
+  if (U == 0) return CGNN_OK;
+  if (!matrices || !out || !workspace) return CGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(matrices) | reinterpret_cast<uintptr_t>(out)) & 3) return CGNN_EINVAL;
+  if (each && (!alphas || (reinterpret_cast<uintptr_t>(alphas) & 7))) return CGNN_EINVAL;
+  // out [U n][n] (U * n < 2^31 and n <= 1024: the byte count fits, and is compared by division as its neighbours do)
+  if (out_bytes / (int64_t)sizeof(float) / n < U * n) return CGNN_EINVAL;
+  const size_t lds = lds_of(n);
+  if (lds > (size_t)kLdsBytes) return CGNN_EINVAL;            // (n <= CGNN_PARTIAL_MAX_NODES fits: 151 KB at 1024)
+  const int grid = grid_of(U, lds);
+  if (workspace_bytes < grid * slab_bytes(padded(n))) return CGNN_EINVAL;
+  const bool vec = n % 4 == 0 && !(reinterpret_cast<uintptr_t>(out) & 15);
+  float* slabs = static_cast<float*>(workspace);
+  const auto go = each ? (vec ? launch_as<true, true> : launch_as<false, true>)
+                       : (vec ? launch_as<true, false> : launch_as<false, false>);
+  return go(grid, lds, matrices, U, n, shrinkage, alphas, absolute, slabs, out, stream);
+}
+
 }  // namespace
 
 extern "C" int64_t cgnn_ingest_partial_workspace_bytes(int64_t U, int32_t n) {
@@ -305,25 +347,12 @@ extern "C" int64_t cgnn_ingest_partial_workspace_bytes(int64_t U, int32_t n) {
 extern "C" int cgnn_ingest_partial(const float* matrices, int64_t U, int32_t n, double shrinkage, int32_t absolute,
                                    void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
                                    void* stream) {
-  if (check(U, n) != CGNN_OK || !(shrinkage >= 0.0 && shrinkage <= 1.0)) return CGNN_EINVAL;
-  if (workspace_bytes < 0 || out_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
-  if (U == 0) return CGNN_OK;
-  if (!matrices || !out || !workspace) return CGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(matrices) | reinterpret_cast<uintptr_t>(out)) & 3) return CGNN_EINVAL;
-  // out [U n][n] (U * n < 2^31 and n <= 1024: the byte count fits, and is compared by division as its neighbours do)
-  if (out_bytes / (int64_t)sizeof(float) / n < U * n) return CGNN_EINVAL;
-  const size_t lds = lds_of(n);
-  if (lds > (size_t)kLdsBytes) return CGNN_EINVAL;            // (n <= CGNN_PARTIAL_MAX_NODES fits: 151 KB at 1024)
-  const int grid = grid_of(U, lds);
-  if (workspace_bytes < grid * slab_bytes(padded(n))) return CGNN_EINVAL;
-  const bool vec = n % 4 == 0 && !(reinterpret_cast<uintptr_t>(out) & 15);
-  if (!(vec ? cgnn_raise_lds_limit<k_partial<true>>(kLdsBytes) : cgnn_raise_lds_limit<k_partial<false>>(kLdsBytes)))
-    return CGNN_ELAUNCH;
-  float* slabs = static_cast<float*>(workspace);
-  if (vec)
-    k_partial<true><<<grid, kThreads, lds, cgnn_stream(stream)>>>(matrices, U, n, shrinkage, absolute, slabs, out);
-  else
-    k_partial<false><<<grid, kThreads, lds, cgnn_stream(stream)>>>(matrices, U, n, shrinkage, absolute, slabs, out);
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
+  return launch(matrices, U, n, shrinkage, nullptr, false, absolute, workspace, workspace_bytes, out, out_bytes,
+                stream);
+}
+
+extern "C" int cgnn_ingest_partial_each(const float* matrices, int64_t U, int32_t n, const double* shrinkage,
+                                        int32_t absolute, void* workspace, int64_t workspace_bytes, float* out,
+                                        int64_t out_bytes, void* stream) {
+  return launch(matrices, U, n, 0.0, shrinkage, true, absolute, workspace, workspace_bytes, out, out_bytes, stream);
 }

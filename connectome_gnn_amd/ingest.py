@@ -162,7 +162,8 @@ Everything is per unit, with matrix ``R`` read from its UPPER triangle (``i <= j
   ``from_matrices`` gives that unit no edges.  The round counts are fixed: the call always returns.
 * ``shrinkage == 0`` needs at least ``n + 2`` frames per unit: with fewer the correlation matrix is singular by
   construction (a ``ValueError`` from ``correlation_matrices`` / ``from_timeseries``; give ``shrinkage > 0``).
-  Estimating ``a`` from the frames (Ledoit-Wolf) is not done here.
+* ``shrinkage`` is one float for the whole cohort, a ``[U]`` tensor with one value per unit, or, where the time series
+  are at hand (``correlation_matrices`` / ``from_timeseries``), the name of an estimator from ``SHRINKAGES``.
 
 Arithmetic: ``C = U^T U`` (blocked Cholesky, upper), ``W = U^-T``, ``P = W^T W``.  Storage and products are fp32,
 every sum in ascending order, the trailing updates and ``W^T W`` on the fp32 matrix pipe.  The reciprocal pivots, the
@@ -172,6 +173,25 @@ once.  No atomics, and no work assignment depends on the grid: every run and eve
 One launch: a workgroup per unit on a slab of its own in the workspace -- one slab per workgroup of the launch, not
 per unit, so nothing cohort-sized exists besides the output -- and ``n <= PARTIAL_MAX_NODES = 1024`` (a ``ValueError``
 beyond: the row panel of a round must fit LDS).  About ``n^3`` multiply-adds per unit.  No solver library is called.
+
+Shrinkage per unit, estimated from the frames: ``ledoit_wolf_shrinkage(timeseries, window=, stride=)``
+gives the Ledoit-Wolf shrinkage of every unit, float64 ``[U]`` on the device, and ``shrinkage="ledoit_wolf"`` of
+``correlation_matrices`` / ``from_timeseries`` with ``kind="partial"`` applies it unit by unit (what nilearn's
+``ConnectivityMeasure`` does by default).  The series are standardised, so Ledoit-Wolf's target is the identity that
+``partial_correlation`` shrinks towards and the estimator is two scalars per unit of ``L`` frames, with
+``z[t, i] = (x[t, i] - m_i) / sqrt(q_i)`` in fp32 as the correlation kernel forms it and ``R`` the unit's matrix:
+
+* ``p`` is the number of ROIs with ``q_i > 0`` (constant ROIs are excluded, as everywhere);
+* ``s_t = sum_i z[t, i]^2`` and ``B = L sum_t s_t^2``;
+* ``O = 2 sum_{i<j} R_ij^2`` and ``F = p + O``;
+* ``a = 0`` if ``O == 0``, else ``(B - F) / (L O)`` clipped to ``[0, 1]``.
+
+This is ``sklearn.covariance.ledoit_wolf_shrinkage`` of the standardised frames.  Squares, sums and the quotient are
+fp64; no atomics, every merge in a fixed order: every run and every grid gives the same bits.  ``L == 2`` makes
+``B - F`` zero identically and gives exactly 0; so do ``n == 1`` and a unit with one ROI that is not constant.  A
+non-finite frame gives its unit a NaN.  One launch (csrc/shrinkage.hip): one read of the frames and one of the upper
+triangles; ``n <= PARTIAL_MAX_NODES``.  A ``[U]`` shrinkage tensor is float64 (float32 is converted) on the matrices'
+device; its values are read by the kernel only: a unit whose value is NaN or outside ``[0, 1]`` is all NaN.
 """
 from __future__ import annotations
 
@@ -191,6 +211,7 @@ WEIGHTED_PATH_MEASURES = ("weighted_nodal_efficiency", "weighted_closeness", "we
 WEIGHTED_PATH_MAX_NODES = 1024                        # CGNN_WPATH_MAX_NODES: both panels of a round must fit LDS
 PARTIAL_MAX_NODES = 1024                              # CGNN_PARTIAL_MAX_NODES: the row panel of a round must fit LDS
 KINDS = ("correlation", "partial")                    # correlation_matrices's kind=
+SHRINKAGES = ("ledoit_wolf",)                         # correlation_matrices's shrinkage=, besides a float or a tensor
 
 
 class _Family(NamedTuple):
@@ -319,7 +340,8 @@ def _require_resident_timeseries(timeseries: torch.Tensor) -> None:
             "device only (there is no CPU fallback; move them with .to('cuda')).")
 
 
-def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool) -> torch.Tensor:
+def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool) -> tuple:
+    """(the correlations [U, n, n], the statistics [U, n, 2] they were built with)"""
     dev = timeseries.device
     U = S * W
     out = torch.empty(U, n, n, dtype=torch.float32, device=dev)
@@ -329,12 +351,43 @@ def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, abso
                                                 st if windowed else 0, int(bool(absolute)), _lib.ptr(stats),
                                                 _lib.nbytes(stats), _lib.ptr(out), _lib.nbytes(out),
                                                 _lib.stream_ptr(dev)), "cgnn_ingest_corr")
-    return out
+    return out, stats
 
 
-def _check_shrinkage(shrinkage) -> float:
+def _estimate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, stats: torch.Tensor,
+              matrices: torch.Tensor) -> torch.Tensor:
+    """cgnn_ingest_shrinkage: float64 [U], for the signed correlations and the statistics ``_correlate`` returned."""
+    dev = timeseries.device
+    alpha = torch.empty(S * W, dtype=torch.float64, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(_lib.load().cgnn_ingest_shrinkage(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
+                                                     st if windowed else 0, _lib.ptr(stats), _lib.ptr(matrices),
+                                                     _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)),
+                   "cgnn_ingest_shrinkage")
+    return alpha
+
+
+def _check_shrinkage(shrinkage, units: int, like: torch.Tensor, frames: bool):
+    """A valid shrinkage=: a float in [0, 1]; a ``[units]`` tensor on ``like``'s device, as float64 (its values are the
+    kernel's to read); or, where the ``frames`` are at hand, a name from SHRINKAGES."""
+    if isinstance(shrinkage, torch.Tensor):
+        if shrinkage.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"a shrinkage tensor must be float64 (or float32), got {shrinkage.dtype}")
+        if tuple(shrinkage.shape) != (units,):
+            raise ValueError(f"a shrinkage tensor must be [U] = [{units}], one value per unit, got "
+                             f"{tuple(shrinkage.shape)}")
+        if shrinkage.device != like.device:
+            raise ValueError(f"the shrinkage tensor is on {shrinkage.device}, the data on {like.device}")
+        return shrinkage.to(torch.float64).contiguous()
+    if isinstance(shrinkage, str) and shrinkage in SHRINKAGES:
+        if not frames:
+            raise ValueError(f"shrinkage={shrinkage!r} is estimated from the frames, which correlation matrices no "
+                             "longer hold: pass shrinkage=ledoit_wolf_shrinkage(timeseries), or ask "
+                             "correlation_matrices / from_timeseries for it")
+        return shrinkage
     if isinstance(shrinkage, bool) or not isinstance(shrinkage, (int, float)):
-        raise TypeError(f"shrinkage must be a float, got {type(shrinkage).__name__}")
+        got = repr(shrinkage) if isinstance(shrinkage, str) else type(shrinkage).__name__
+        raise TypeError(f"shrinkage must be a float, a [U] tensor or one of {SHRINKAGES}, got {got}")
     shrinkage = float(shrinkage)
     if not 0.0 <= shrinkage <= 1.0:                   # (a NaN is refused here too)
         raise ValueError(f"shrinkage must lie in [0, 1], got {shrinkage}")
@@ -347,26 +400,27 @@ def _check_partial_size(n: int) -> None:
                          f"fit LDS), got n = {n}")
 
 
-def _check_kind(kind, shrinkage, n: int, L: int) -> float:
-    """The shrinkage of a valid (kind, shrinkage) for units of L frames and n ROIs."""
+def _check_kind(kind, shrinkage, n: int, L: int, units: int, timeseries: torch.Tensor):
+    """The shrinkage (``_check_shrinkage``'s) of a valid (kind, shrinkage) for ``units`` units of L frames and n ROIs."""
     if kind not in KINDS:
         raise ValueError(f"unknown kind {kind!r}: the kinds are {KINDS}")
-    shrinkage = _check_shrinkage(shrinkage)
+    shrinkage = _check_shrinkage(shrinkage, units, timeseries, True)
     if kind == "correlation":
-        if shrinkage != 0.0:
+        if not isinstance(shrinkage, float) or shrinkage != 0.0:
             raise ValueError('shrinkage applies to kind="partial"; kind="correlation" takes shrinkage=0')
         return shrinkage
     _check_partial_size(n)
-    if shrinkage == 0.0 and L < n + 2:
+    if isinstance(shrinkage, float) and shrinkage == 0.0 and L < n + 2:
         raise ValueError(f"the correlation matrix of {L} frames and n = {n} ROIs is singular by construction (a "
                          f"partial correlation without shrinkage needs at least n + 2 = {n + 2} frames per unit): "
                          "give shrinkage > 0")
     return shrinkage
 
 
-def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage: float, absolute: bool, out: torch.Tensor):
-    """cgnn_ingest_partial of resident matrices into ``out``, which may be ``matrices``.  The workspace is what the
-    query asks for: one slab per workgroup of the launch."""
+def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage, absolute: bool, out: torch.Tensor):
+    """cgnn_ingest_partial of resident matrices into ``out``, which may be ``matrices``; cgnn_ingest_partial_each if
+    ``shrinkage`` is a float64 ``[U]`` tensor.  The workspace is what the query asks for: one slab per workgroup of the
+    launch."""
     if U == 0:
         return out
     dev = matrices.device
@@ -376,31 +430,51 @@ def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage: float, absolute:
         if need < 0:
             raise _lib.CgnnError(f"cgnn_ingest_partial_workspace_bytes({U}, {n}) refused its arguments")
         work = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cgnn_ingest_partial(_lib.ptr(matrices), U, n, shrinkage, int(bool(absolute)), _lib.ptr(work),
-                                           _lib.nbytes(work), _lib.ptr(out), _lib.nbytes(out),
-                                           _lib.stream_ptr(dev)), "cgnn_ingest_partial")
+        each = isinstance(shrinkage, torch.Tensor)
+        call = "cgnn_ingest_partial_each" if each else "cgnn_ingest_partial"
+        _lib.check(getattr(lib, call)(_lib.ptr(matrices), U, n, _lib.ptr(shrinkage) if each else shrinkage,
+                                      int(bool(absolute)), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
+                                      _lib.nbytes(out), _lib.stream_ptr(dev)), call)
     return out
 
 
 def partial_correlation(matrices: torch.Tensor, *, shrinkage=0.0, absolute=False) -> torch.Tensor:
     """Partial correlation of every unit's correlation matrix: ``[U, n, n]`` float32 on ``matrices.device`` (module
     docstring).  ``matrices`` are read from their upper triangles and left as they are.  One launch on resident data;
-    the only temporary is the workspace, one slab per workgroup.  No read-back."""
+    the only temporary is the workspace, one slab per workgroup.  ``shrinkage`` is a float or a ``[U]`` tensor, such as
+    ``ledoit_wolf_shrinkage`` gives; the tensor's values are read on the device only.  No read-back."""
     U, n = _check_matrices(matrices)
-    shrinkage = _check_shrinkage(shrinkage)
+    shrinkage = _check_shrinkage(shrinkage, U, matrices, False)
     _check_partial_size(n)
     _require_resident(matrices)
     return _partial(matrices, U, n, shrinkage, absolute, torch.empty_like(matrices))
 
 
 def _connectivity(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, kind: str,
-                  shrinkage: float) -> torch.Tensor:
+                  shrinkage) -> torch.Tensor:
     """The matrices of a valid request: the correlations, or the partial correlations of the signed correlations
-    written over them (no second cohort-sized tensor)."""
+    written over them (no second cohort-sized tensor).  A shrinkage named in SHRINKAGES is estimated in between, from
+    the frames, the statistics and the signed correlations."""
     if kind == "correlation":
-        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute)
-    matrices = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
+        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute)[0]
+    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
+    if isinstance(shrinkage, str):
+        shrinkage = _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices)
+    del stats
     return _partial(matrices, S * W, n, shrinkage, absolute, matrices)
+
+
+def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None) -> torch.Tensor:
+    """The Ledoit-Wolf shrinkage of every unit's correlation matrix, estimated from the unit's own frames: float64
+    ``[U]`` on the time series' device (module docstring); what ``partial_correlation(..., shrinkage=)`` takes.  Three
+    launches on resident data (the two of ``correlation_matrices``, then the estimate); the matrices and the statistics
+    are temporaries.  ``n <= PARTIAL_MAX_NODES``.  No read-back."""
+    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    _check_partial_size(n)
+    _require_resident_timeseries(timeseries)
+    windowed = window is not None
+    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
+    return _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices)
 
 
 def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
@@ -408,9 +482,10 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
     """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
     (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics.
     ``kind="partial"`` gives ``partial_correlation`` of the signed correlations at ``shrinkage``, written in place
-    over them by a third launch; ``absolute`` then applies to the partial values."""
+    over them by a third launch; ``absolute`` then applies to the partial values.  ``shrinkage`` is a float, a ``[U]``
+    tensor or ``"ledoit_wolf"``: each unit's own estimate (``ledoit_wolf_shrinkage``), a launch between the two."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
-    shrinkage = _check_kind(kind, shrinkage, n, L)
+    shrinkage = _check_kind(kind, shrinkage, n, L, S * W, timeseries)
     _require_resident_timeseries(timeseries)
     return _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage)
 
@@ -424,7 +499,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     ``shrinkage`` are ``correlation_matrices``'s.  The one read-back is ``from_matrices``'s."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
-    shrinkage = _check_kind(kind, shrinkage, n, L)
+    shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
     _check_path_size(_check_measures_argument(measures, node_features), n)
     _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):

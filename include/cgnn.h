@@ -601,6 +601,44 @@ int64_t cgnn_ingest_partial_workspace_bytes(int64_t U, int32_t n);
 int cgnn_ingest_partial(const float* matrices, int64_t U, int32_t n, double shrinkage, int32_t absolute,
                         void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A shrinkage per unit: cgnn_ingest_partial with shrinkage[u], double [U] on the device and 8-byte
+ * aligned, in place of the one scalar.  The kernel reads shrinkage[u] when it starts unit u; the host never does.  A
+ * unit whose value is not in [0, 1] (a NaN is not) takes the failure path: an all-NaN matrix, its neighbours untouched.
+ * A unit whose value equals the scalar of cgnn_ingest_partial gets the bits of that call.  The workspace, its query, the
+ * launch and every other refusal are cgnn_ingest_partial's; a NULL or misaligned shrinkage returns CGNN_EINVAL.
+ * ------------------------------------------------------------------------------------- */
+int cgnn_ingest_partial_each(const float* matrices, int64_t U, int32_t n, const double* shrinkage, int32_t absolute,
+                             void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The Ledoit-Wolf shrinkage of every unit, estimated from its frames: what cgnn_ingest_partial_each
+ * takes.  ts, S, T, n, window, stride: as given to cgnn_ingest_corr, which defines the units; stats: float [U, n, 2],
+ * the statistics that call left; matrices: float [U, n, n], the SIGNED correlations it wrote (absolute == 0).
+ *   per unit   of L frames, with z[t,i] = (x[t,i] - m_i) rs_i formed in fp32 as cgnn_ingest_corr stages it (rs_i = 0 for
+ *              a constant column) and R the unit's matrix, so that the estimate is for the R that was built:
+ *                p   = the number of columns with rs_i != 0
+ *                s_t = sum_i z[t,i]^2,   B = L sum_t s_t^2
+ *                O   = 2 sum_{i<j} R_ij^2 (from the entries above the diagonal, never as F - p),   F = p + O
+ *                a   = 0 if O == 0, else (B - F) / (L O) clipped to [0, 1]
+ *              This is sklearn.covariance.ledoit_wolf_shrinkage of the standardised frames (the constant columns
+ *              left out), whose target mu I is the identity cgnn_ingest_partial shrinks towards.  Squares, sums and the
+ *              quotient are fp64.  L == 2 makes B - F zero identically: a = 0 there, not what rounding leaves.  n == 1
+ *              or a single column that is not constant gives O == 0 and a = 0.  Non-finite inputs are not checked: a
+ *              NaN in a unit's sums gives that unit a NaN (which cgnn_ingest_partial_each turns into an all-NaN unit).
+ *   output     alpha: double [U], 8-byte aligned, alpha_bytes >= 8 U.
+ * One launch on `stream`: min(U, 4 * cgnn_fused_grid()) workgroups of 4 waves, a workgroup per unit with a grid stride;
+ * one read of the unit's frames (a wave per frame, a lane per column) and one of the upper triangle of its matrix.
+ * Overlapping windows read their frames again.  No atomics, every merge in a fixed order, nothing depends on the grid:
+ * the same bits on every run and for every grid.
+ * n > CGNN_PARTIAL_MAX_NODES (the unit's statistics wait in LDS; the estimate feeds a call with that bound), a NULL,
+ * misaligned or short buffer, S < 0, n <= 0, T < 2, window outside {0} u [2, T], stride < 1 with a window or
+ * U * n >= 2^31 return CGNN_EINVAL before any launch; S == 0 returns CGNN_OK with nothing launched.  Element offsets
+ * into ts and matrices are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+int cgnn_ingest_shrinkage(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                          const float* stats, const float* matrices, double* alpha, int64_t alpha_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
