@@ -192,10 +192,40 @@ fp64; no atomics, every merge in a fixed order: every run and every grid gives t
 non-finite frame gives its unit a NaN.  One launch (csrc/shrinkage.hip): one read of the frames and one of the upper
 triangles; ``n <= PARTIAL_MAX_NODES``.  A ``[U]`` shrinkage tensor is float64 (float32 is converted) on the matrices'
 device; its values are read by the kernel only: a unit whose value is NaN or outside ``[0, 1]`` is all NaN.
+
+Cleaning comes first: ``filter_timeseries(timeseries, t_r=, high_pass=, low_pass=)`` removes the mean,
+the slow drift and what lies above the band from every column, on the device (csrc/filter.hip), and gives float32
+``[S, T, n]``: what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.  It is nilearn's
+``signal.clean(detrend=False, standardize=False, filter="cosine")`` extended to a low-pass, SPM's DCT drift set, an ideal
+band-pass on the DCT-II grid.  Everything is per subject and per column ``i``, on the ``T`` frames of the whole run;
+windows are cut afterwards.
+
+* Basis: ``b_k[t] = sqrt(2 / T) cos(pi (2 t + 1) k / (2 T))`` for ``k = 1 .. T - 1``, the orthonormal DCT-II
+  (``scipy.fft.dct(type=2, norm="ortho")``); component ``k`` has frequency ``k / (2 T t_r)`` Hz.
+* Pass band, ``filter_components(T, t_r, high_pass, low_pass)``, in Python floats on the host: ``k_lo = 1`` without a
+  ``high_pass``, else ``floor(2 T t_r high_pass) + 1``; ``k_hi = T - 1`` without a ``low_pass``, else
+  ``min(T - 1, floor(2 T t_r low_pass))``.  The dropped low set ``1 .. k_lo - 1`` is nilearn's and SPM's cosine drift
+  set for that ``high_pass``.  A band without a component is a ``ValueError``.
+* Centring: ``m_i`` is the column mean, summed in fp64 in a fixed order, and ``xc[t, i] = fl32(double(x[t, i]) - m_i)``:
+  one rounding.  (Subtracting an fp32 mean leaves an offset of ``2^-24 |m_i|`` that the complement form keeps.)
+* Projection, with ``Kp = {k_lo .. k_hi}`` and ``Kd`` the other components: ``y = sum_{k in Kp} b_k (b_k . xc)`` if
+  ``|Kp| <= |Kd|`` (the *keep* form), else ``y = xc - sum_{k in Kd} b_k (b_k . xc)`` (the *complement* form) -- the same
+  function in exact arithmetic, the basis being orthonormal on the ``T`` samples; the call multiplies by the smaller
+  set.  Without bounds ``y = xc`` and no product is launched.
+* The smaller set holds at most ``FILTER_MAX_COMPONENTS = 256`` components (a ``ValueError`` names both counts):
+  1200 frames at ``t_r = 0.72`` keep 155 in 0.01 - 0.1 Hz, and ``high_pass = 0.01`` alone drops 17.
+
+Arithmetic: a basis value is an fp64 ``cospi`` of the exactly reduced argument ``((2 t + 1) k mod 4 T) / (2 T)``, scaled
+in fp64 and rounded to fp32 once; the products run on the fp32 matrix pipe, every sum in ascending order of its index.
+No atomics, and no work assignment depends on the grid: every run and every grid gives the same bits.  Columns never
+mix: a constant column gives exactly ``0.0`` in every frame, and a non-finite value makes its own column of its own
+subject non-finite and changes no other bit.  ``out=timeseries`` filters in place with the same bits (a workgroup owns
+all frames of the columns it writes); no other overlap of ``out`` and ``timeseries`` is checked.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -212,6 +242,8 @@ WEIGHTED_PATH_MAX_NODES = 1024                        # CGNN_WPATH_MAX_NODES: bo
 PARTIAL_MAX_NODES = 1024                              # CGNN_PARTIAL_MAX_NODES: the row panel of a round must fit LDS
 KINDS = ("correlation", "partial")                    # correlation_matrices's kind=
 SHRINKAGES = ("ledoit_wolf",)                         # correlation_matrices's shrinkage=, besides a float or a tensor
+FILTER_MAX_COMPONENTS = 256                           # CGNN_FILTER_MAX_COMPONENTS: the coefficients of 64 columns must fit LDS
+_FILTER_MAX_FRAMES = 2 ** 30                          # cgnn_ingest_filter's bound on T
 
 
 class _Family(NamedTuple):
@@ -338,6 +370,99 @@ def _require_resident_timeseries(timeseries: torch.Tensor) -> None:
         raise RuntimeError(
             f"timeseries are on {timeseries.device}: connectome_gnn_amd correlates ROI time series on a ROCm "
             "device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+def _finite_number(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError(f"{name} must be a float, got {type(v).__name__}")
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError(f"{name} must be finite, got {v}")
+    return v
+
+
+def filter_components(T: int, t_r, high_pass=None, low_pass=None) -> tuple:
+    """``(k_lo, k_hi)``: the DCT-II components ``k_lo .. k_hi`` of a ``T``-frame run sampled every ``t_r`` seconds that
+    the band ``[high_pass, low_pass]`` Hz passes (module docstring); component ``k`` has frequency ``k / (2 T t_r)``.
+    ``k_lo - 1 = floor(2 T t_r high_pass)`` is the order of nilearn's and SPM's cosine drift set.  Host only: Python
+    floats, no tensor, no device.  ``k_lo > k_hi`` says that the band holds no component."""
+    if isinstance(T, bool) or not isinstance(T, int):
+        raise TypeError(f"T must be an int, got {type(T).__name__}")
+    if T < 2:
+        raise ValueError(f"a run has T >= 2 frames, got T = {T}")
+    t_r = _finite_number("t_r", t_r)
+    if t_r <= 0.0:
+        raise ValueError(f"t_r must be > 0, got {t_r}")
+    k_lo, k_hi = 1, T - 1
+    if high_pass is not None:
+        high_pass = _finite_number("high_pass", high_pass)
+        if high_pass < 0.0:
+            raise ValueError(f"high_pass must be >= 0, got {high_pass}")
+        k_lo = math.floor(2 * T * t_r * high_pass) + 1
+    if low_pass is not None:
+        low_pass = _finite_number("low_pass", low_pass)
+        if low_pass <= 0.0:
+            raise ValueError(f"low_pass must be > 0, got {low_pass}")
+        k_hi = min(T - 1, math.floor(2 * T * t_r * low_pass))
+    if high_pass is not None and low_pass is not None and not high_pass < low_pass:
+        raise ValueError(f"high_pass must lie below low_pass, got {high_pass} >= {low_pass}")
+    return k_lo, k_hi
+
+
+def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None) -> torch.Tensor:
+    """The time series centred and band-passed column by column, by projection on the DCT-II components
+    ``filter_components(T, t_r, high_pass, low_pass)`` of the whole run: float32 ``[S, T, n]`` on the time series'
+    device (module docstring), what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.
+    Both bounds ``None`` removes the column means only.  ``out`` is where the result goes: a float32 contiguous tensor
+    of the same shape on the same device, which is returned; it may be ``timeseries`` itself (in place, the same bits as
+    out of place).  Any other overlap of the two is not checked and gives unspecified values.  Three launches on
+    resident data (two without a bound); the temporaries are the basis table ``[T, Kpad]`` and the means ``[S, n]``.
+    No read-back."""
+    S, T, n = _check_timeseries(timeseries, None, None)[:3]
+    if T > _FILTER_MAX_FRAMES:
+        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+    k_lo, k_hi = filter_components(T, t_r, high_pass, low_pass)
+    if k_lo > k_hi:
+        raise ValueError(f"the band high_pass={high_pass}, low_pass={low_pass} at t_r={t_r} holds no component of a "
+                         f"{T}-frame run (components {k_lo} .. {k_hi}; component k has k / (2 T t_r) Hz)")
+    kept = k_hi - k_lo + 1
+    dropped = T - 1 - kept
+    complement = kept > dropped                       # the smaller set is the one that is multiplied
+    K = dropped if complement else kept
+    if K > FILTER_MAX_COMPONENTS:
+        raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
+                         f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
+        if out.dtype != torch.float32:
+            raise TypeError(f"out must be float32, got {out.dtype}")
+        if out.shape != timeseries.shape:
+            raise ValueError(f"out must be {tuple(timeseries.shape)} as the time series are, got {tuple(out.shape)}")
+        if out.device != timeseries.device:
+            raise ValueError(f"out is on {out.device}, the time series on {timeseries.device}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    _require_resident_timeseries(timeseries)
+    if out is None:
+        out = torch.empty_like(timeseries)
+    if S == 0:
+        return out
+    if complement:
+        comps = list(range(1, k_lo)) + list(range(k_hi + 1, T))
+    else:
+        comps = list(range(k_lo, k_hi + 1))
+    dev = timeseries.device
+    lib = _lib.load()
+    with _lib.device_guard(dev):
+        need = lib.cgnn_ingest_filter_workspace_bytes(S, T, n, K)
+        if need < 0:
+            raise _lib.CgnnError(f"cgnn_ingest_filter_workspace_bytes({S}, {T}, {n}, {K}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cgnn_ingest_filter(_lib.ptr(timeseries), S, T, n, (ctypes.c_int32 * K)(*comps), K,
+                                          int(complement), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
+                                          _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_filter")
+    return out
 
 
 def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool) -> tuple:

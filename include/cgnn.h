@@ -639,6 +639,41 @@ int cgnn_ingest_partial_each(const float* matrices, int64_t U, int32_t n, const 
 int cgnn_ingest_shrinkage(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
                           const float* stats, const float* matrices, double* alpha, int64_t alpha_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Band-pass / detrend of ROI time series by projection on the orthonormal DCT-II basis: what comes
+ * in front of cgnn_ingest_corr.  ts: float [S, T, n] as cgnn_ingest_corr takes it.  Per subject and column i, on the T
+ * frames of the whole run:
+ *   basis      b_k[t] = sqrt(2 / T) cos(pi (2 t + 1) k / (2 T)), k = 1 .. T - 1 (component k: k / (2 T t_r) Hz): an
+ *              fp64 cospi of the exactly reduced argument ((2 t + 1) k mod 4 T) / (2 T), scaled in fp64, rounded to
+ *              fp32 once
+ *   centring   m_i = the column mean, summed in fp64 in a fixed order; xc[t,i] = fl32(double(x[t,i]) - m_i)
+ *   comps      K ascending components in [1, T - 1], a HOST array the call reads before it returns
+ *   output     complement == 0:  y = sum_{k in comps} b_k (b_k . xc)        (the components are what is kept)
+ *              complement != 0:  y = xc - sum_{k in comps} b_k (b_k . xc)   (the components are what is dropped)
+ *              K == 0 with complement != 0 is pure centring, y = xc, and launches no product.
+ *   arithmetic the products on the fp32 matrix pipe, every sum in ascending order of its index.  Columns never mix: a
+ *              constant column gives exactly 0 in every frame, a non-finite entry makes its own column of its own
+ *              subject non-finite and changes no other bit.
+ *   out        float [S, T, n]; may be `ts` itself (a workgroup owns all T frames of the columns it writes); any other
+ *              overlap is not checked
+ *   workspace  cgnn_ingest_filter_workspace_bytes(S, T, n, K) bytes, 16-byte aligned: the basis table float [T, Kpad]
+ *              (Kpad = K rounded up to 32) and the means double [S, n]; nothing cohort-sized
+ * Launches on `stream`: the table (K > 0), the means (a streaming pass of its own: a lane per column, a wave per frame
+ * phase, merged in wave order), then a persistent grid over the items (subject, 64 columns), grid stride: the
+ * coefficients C = B^T xc [Kpad, 64] with the frames 32 at a time, kept in LDS, then y chunk by chunk of 32 frames (the
+ * complement form reads x again).  No atomics, nothing depends on the grid: the same bits on every run and for every
+ * grid.
+ * K > CGNN_FILTER_MAX_COMPONENTS, K < 0, K == 0 with complement == 0 (nothing is kept), a component outside
+ * [1, T - 1] or not ascending, T < 2, T > 2^30, S < 0, n <= 0, S * n >= 2^31, a NULL, misaligned or short buffer
+ * return CGNN_EINVAL before any launch (the byte count: a negative value); S == 0 returns CGNN_OK with nothing
+ * launched.  Element offsets are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_FILTER_MAX_COMPONENTS 256
+int64_t cgnn_ingest_filter_workspace_bytes(int64_t S, int32_t T, int32_t n, int32_t K);
+int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t n, const int32_t* comps, int32_t K,
+                       int32_t complement, void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
+                       void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
