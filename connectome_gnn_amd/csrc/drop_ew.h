@@ -5,7 +5,8 @@
 // a fused consumer draws exactly the bits the stand-alone apply pass would, and cgnn_rng_advance, the
 // one-launch finaliser and a producer's BatchNorm tail advance the words alike, so graph replay draws the
 // masks an eager run would.  head.hip draws a stream of its own (its own keys, 16 bits per element) with
-// the same mixer.
+// the same mixer.  Held to this by tests/test_gpu_dropout.py (every draw site and advancer, bit for bit against
+// the host model of tests/dropout_data.py) and tests/test_dropout_math.py (that model's statistics); DESIGN.md 4.2e.
 #pragma once
 #include "common.h"
 

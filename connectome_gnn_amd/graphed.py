@@ -79,6 +79,7 @@ class GraphedTrainStep:
         self._local_graphs = None if local_graphs is None else int(local_graphs)
         if warmup < 1:
             raise ValueError("warmup >= 1: the optimizer state must exist before capture")
+        self._own_rng_words(model, dev)
         split = grad_sync is not None and collectives == "split"
         if split and self._has_sync_bn():
             raise ValueError("SyncBatchNorm exchanges statistics inside forward/backward: a captured "
@@ -90,8 +91,6 @@ class GraphedTrainStep:
                 "(a kept, non-detached `loss` or output tensor).  Its AccumulateGrad nodes are bound to the stream "
                 "that step ran on, and capturing a backward pass through them crashes the process.  Drop those "
                 "tensors (`del loss`, or keep `loss.detach()` / `float(loss)`) before building a captured step.")
-        if getattr(model, "rng_device_state", None) is None:
-            model.rng_device_state = torch.randint(0, 2 ** 31 - 1, (16,), dtype=torch.int32, device=dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                       # warm-up off the capture stream
@@ -122,6 +121,28 @@ class GraphedTrainStep:
                 prm.grad = None
             if hasattr(grad_sync, "zero_grad"):
                 grad_sync.zero_grad()
+
+    RNG_MIN_WORDS, RNG_MAX_WORDS = 16, 64        # (64: what cgnn_rng_advance and the BatchNorm tails advance at most)
+
+    @classmethod
+    def _own_rng_words(cls, model, dev) -> None:
+        """``model.rng_device_state``: one uint32 word per encoder layer and one for the classifier (which reads word
+        ``num_layers``), all refreshed by every captured step -- so the state is sized from the model, and a model with
+        more layers than the kernels advance, or a preset state that is too short, is refused here, before capture."""
+        convs = getattr(model, "convs", None)
+        need = (len(convs) if convs is not None else cls.RNG_MIN_WORDS - 1) + 1
+        if need > cls.RNG_MAX_WORDS:
+            raise ValueError(f"GraphedTrainStep: a model of {need - 1} layers needs {need} dropout words per step; "
+                             f"the kernels advance at most {cls.RNG_MAX_WORDS}")
+        state = getattr(model, "rng_device_state", None)
+        if state is None:
+            model.rng_device_state = torch.randint(0, 2 ** 31 - 1, (max(cls.RNG_MIN_WORDS, need),), dtype=torch.int32,
+                                                   device=dev)
+        elif state.dtype != torch.int32 or state.dim() != 1 or not state.is_contiguous() \
+                or state.device.type != torch.device(dev).type or int(state.numel()) < need:
+            raise ValueError(f"GraphedTrainStep: model.rng_device_state must be a contiguous int32 vector of at least "
+                             f"{need} words (num_layers + 1) on the batch's device, got {tuple(state.shape)} "
+                             f"{state.dtype} on {state.device}")
 
     def _capture(self, split: bool, mode: dict) -> None:
         # The cyclic garbage collector stays OFF while a stream is capturing: a collection pass runs in whichever
