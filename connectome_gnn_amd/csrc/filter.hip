@@ -1,6 +1,7 @@
 // filter.hip -- a device-resident cohort of ROI time series (float [S, T, n], one row per frame) band-passed and
 // detrended by projection on the orthonormal DCT-II basis: cgnn_ingest_filter, the step in front of
-// cgnn_ingest_corr (timeseries.hip).
+// cgnn_ingest_corr (timeseries.hip).  cgnn_ingest_regress is the same kernel in complement form against
+// a table per subject, the orthonormal basis of its confounds (confounds.hip), in place of the one table of the cohort.
 //
 // Per subject and column i, over the T frames of the run: b_k[t] = sqrt(2 / T) cos(pi (2 t + 1) k / (2 T)), m_i = the
 // column mean (fp64), xc[t,i] = fl32(double(x[t,i]) - m_i), and with the K components the caller names
@@ -168,11 +169,12 @@ __device__ __forceinline__ void store4(float* o, int t, int T, int col, int n, f
   }
 }
 
-// `ts` and `out` may be the same array: neither is __restrict__
+// `ts` and `out` may be the same array: neither is __restrict__.  table_stride: floats between the tables of two
+// subjects (cgnn_ingest_regress: a basis per subject), 0 for the one table of the cohort
 template <int kPad, bool kVec>
 __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S, int T, int n, int complement,
-                                                     const float* __restrict__ table, const double* __restrict__ mean,
-                                                     float* out) {
+                                                     const float* __restrict__ tables, int64_t table_stride,
+                                                     const double* __restrict__ mean, float* out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   double* mu = reinterpret_cast<double*>(lds);                // [64] the item's means, 0 past n
   float* area = reinterpret_cast<float*>(mu + kCols);
@@ -199,6 +201,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
     const int col0 = (int)(item - s * chunks) * kCols;
     const float* x = ts + s * T * n;
     float* o = out + s * T * n;
+    const float* __restrict__ table = tables + s * table_stride;
 
     __syncthreads();                          // the previous item's last chunk still reads mu and Y
     if (tid < kCols) mu[tid] = col0 + tid < n ? mean[s * n + col0 + tid] : 0.0;
@@ -381,29 +384,29 @@ int64_t table_bytes(int32_t T, int32_t K) { return cgnn_align_up((int64_t)T * pa
 
 template <int kPad, bool kVec>
 int launch_as(const float* ts, int64_t S, int32_t T, int32_t n, int32_t complement, const float* table,
-              const double* mean, float* out, hipStream_t hs) {
+              int64_t table_stride, const double* mean, float* out, hipStream_t hs) {
   constexpr size_t lds = lds_of(kPad);
   if (!cgnn_raise_lds_limit<k_filter<kPad, kVec>>(kLdsBytes)) return CGNN_ELAUNCH;
   const int64_t items = S * ((n + kCols - 1) / kCols);
   const int grid = cgnn_grid_for(items, cgnn_wg_per_cu_by_lds(lds, kLdsBytes));
-  k_filter<kPad, kVec><<<grid, kThreads, lds, hs>>>(ts, S, T, n, complement, table, mean, out);
+  k_filter<kPad, kVec><<<grid, kThreads, lds, hs>>>(ts, S, T, n, complement, table, table_stride, mean, out);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
 
 template <bool kVec>
 int launch(int kpad, const float* ts, int64_t S, int32_t T, int32_t n, int32_t complement, const float* table,
-           const double* mean, float* out, hipStream_t hs) {
+           int64_t table_stride, const double* mean, float* out, hipStream_t hs) {
   switch (kpad) {
-    case 0: return launch_as<0, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 32: return launch_as<32, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 64: return launch_as<64, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 96: return launch_as<96, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 128: return launch_as<128, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 160: return launch_as<160, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 192: return launch_as<192, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    case 224: return launch_as<224, kVec>(ts, S, T, n, complement, table, mean, out, hs);
-    default: return launch_as<256, kVec>(ts, S, T, n, complement, table, mean, out, hs);
+    case 0: return launch_as<0, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 32: return launch_as<32, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 64: return launch_as<64, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 96: return launch_as<96, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 128: return launch_as<128, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 160: return launch_as<160, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 192: return launch_as<192, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    case 224: return launch_as<224, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+    default: return launch_as<256, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
   }
 }
 
@@ -446,6 +449,38 @@ extern "C" int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t
   k_filter_mean<<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean);
   CGNN_CHECK_LAUNCH();
   const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
-  return vec ? launch<true>(kpad, ts, S, T, n, complement, table, mean, out, hs)
-             : launch<false>(kpad, ts, S, T, n, complement, table, mean, out, hs);
+  return vec ? launch<true>(kpad, ts, S, T, n, complement, table, 0, mean, out, hs)
+             : launch<false>(kpad, ts, S, T, n, complement, table, 0, mean, out, hs);
+}
+
+// ---- confound regression: the complement form against a basis per subject ----
+
+extern "C" int64_t cgnn_ingest_regress_workspace_bytes(int64_t S, int32_t T, int32_t n) {
+  if (check(S, T, n, 0) != CGNN_OK) return CGNN_EINVAL;
+  return S * n * (int64_t)sizeof(double);
+}
+
+extern "C" int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_t n, const float* basis,
+                                   int64_t basis_bytes, int32_t qpad, void* workspace, int64_t workspace_bytes,
+                                   float* out, int64_t out_bytes, void* stream) {
+  if (check(S, T, n, 0) != CGNN_OK || (qpad != 32 && qpad != 64)) return CGNN_EINVAL;
+  if (basis_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
+  if (S == 0) return CGNN_OK;
+  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (!ts || !out || !basis || !workspace || ((bits(ts) | bits(out)) & 3) || ((bits(basis) | bits(workspace)) & 15))
+    return CGNN_EINVAL;
+  CGNN_NEED_BYTES(workspace, workspace_bytes, S * n * (int64_t)sizeof(double));
+  // basis [S][T, qpad] and out [S T][n]: the byte counts are compared by division
+  if (basis_bytes / (int64_t)sizeof(float) / qpad / T < S) return CGNN_EINVAL;
+  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
+
+  hipStream_t hs = cgnn_stream(stream);
+  double* mean = static_cast<double*>(workspace);
+  const int64_t items = S * ((n + kCols - 1) / kCols);
+  k_filter_mean<<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean);
+  CGNN_CHECK_LAUNCH();
+  const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
+  const int64_t stride = (int64_t)T * qpad;
+  return vec ? launch<true>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs)
+             : launch<false>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs);
 }

@@ -221,6 +221,36 @@ No atomics, and no work assignment depends on the grid: every run and every grid
 mix: a constant column gives exactly ``0.0`` in every frame, and a non-finite value makes its own column of its own
 subject non-finite and changes no other bit.  ``out=timeseries`` filters in place with the same bits (a workgroup owns
 all frames of the columns it writes); no other overlap of ``out`` and ``timeseries`` is checked.
+
+Confound regression: ``regress_confounds(timeseries, confounds)`` takes head motion, tissue signals and
+their expansions -- ``confounds``, float32 ``[S, T, q]`` with ``1 <= q <= CONFOUND_MAX = 64``, one row per frame -- out of
+every column of the time series, on the device; ``filter_timeseries(..., confounds=)`` does it after the band-pass.
+Everything is per subject, in fp64 unless it says otherwise.
+
+* Column norms: ``m_j`` is the mean of confound column ``j``, ``cc_j = c_j - m_j``, ``s_j = sqrt(sum_t cc_j[t]^2)``.  An
+  exactly constant column (``s_j == 0``) is *dropped*; the others are ``u_j = cc_j / s_j``.
+* Gram-Schmidt in the given column order: ``r_j = u_j - sum_{k < j, kept} q_k (q_k . u_j)`` and ``d_j = |r_j|^2``.
+  Column ``j`` is *kept* iff ``d_j > CONFOUND_RANK_TOL = 1e-10``, and then ``q_j = r_j / sqrt(d_j)``; otherwise it is
+  dropped: earlier columns explain it (a copy, a multiple, a sum of them).  ``rank`` is the number of kept columns.
+* The basis ``Q``, ``confound_basis(confounds) -> (basis, rank)``: float32 ``[S, T, qpad]``, ``qpad`` = ``q`` rounded up
+  to 32; a kept column is ``fl32(q_j)``, dropped and pad columns are exactly ``0.0``.  ``rank`` is int32 ``[S]``.
+* A NaN or Inf anywhere in a subject's confounds makes its whole ``Q`` NaN and its ``rank`` -1: every output column of
+  that subject is NaN, never "nothing regressed".  Other subjects keep their bits.
+* Output: ``xc[t, i] = fl32(double(x[t, i]) - mean_i)`` exactly as the filter centres, and ``out = xc - Q (Q^T xc)``.
+
+Arithmetic: the basis is a CholeskyQR2 in fp64 (csrc/confounds.hip: the Gram matrix of ``u`` summed over the frames in
+ascending order by a fixed owner per pair, a ``q x q`` Cholesky in LDS whose pivot of column ``j`` is ``d_j``, the same
+again with the kept set held fixed) rounded to fp32 once -- never normal equations in fp32.  The projection is
+``filter_timeseries``'s kernel in complement form with one table per subject: products on the fp32 matrix pipe, sums in
+ascending index order.  No atomics, and no work assignment depends on the grid: every run and every grid gives the same
+bits.  Columns never mix: a constant ROI column gives exactly ``0.0``, a NaN in an ROI column stays in that column of
+that subject.  ``out=timeseries`` regresses in place with the same bits.
+
+``filter_timeseries(..., confounds=c)`` is ``regress_confounds(filter(timeseries), filter(c))`` with the same band, the
+regression in place on the filter's output.  The DCT projector being orthogonal, that equals the joint regression on
+``[dropped cosines | confounds]`` (Frisch-Waugh-Lovell), which is what nilearn's
+``signal.clean(confounds=, filter="cosine")`` computes.  Without ``confounds`` the call launches what it always
+launched and gives the same bits.
 """
 from __future__ import annotations
 
@@ -244,6 +274,8 @@ KINDS = ("correlation", "partial")                    # correlation_matrices's k
 SHRINKAGES = ("ledoit_wolf",)                         # correlation_matrices's shrinkage=, besides a float or a tensor
 FILTER_MAX_COMPONENTS = 256                           # CGNN_FILTER_MAX_COMPONENTS: the coefficients of 64 columns must fit LDS
 _FILTER_MAX_FRAMES = 2 ** 30                          # cgnn_ingest_filter's bound on T
+CONFOUND_MAX = 64                                     # CGNN_CONFOUND_MAX: the widest table of k_filter's regress form
+CONFOUND_RANK_TOL = 1e-10                             # CGNN_CONFOUND_RANK_TOL: a column is kept iff its pivot d_j exceeds it
 
 
 class _Family(NamedTuple):
@@ -409,7 +441,115 @@ def filter_components(T: int, t_r, high_pass=None, low_pass=None) -> tuple:
     return k_lo, k_hi
 
 
-def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None) -> torch.Tensor:
+def _check_out(out, timeseries: torch.Tensor) -> None:
+    if out is None:
+        return
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
+    if out.dtype != torch.float32:
+        raise TypeError(f"out must be float32, got {out.dtype}")
+    if out.shape != timeseries.shape:
+        raise ValueError(f"out must be {tuple(timeseries.shape)} as the time series are, got {tuple(out.shape)}")
+    if out.device != timeseries.device:
+        raise ValueError(f"out is on {out.device}, the time series on {timeseries.device}")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+
+
+def _check_confounds(confounds, S=None, T=None, device=None) -> tuple:
+    """(S, T, q) of valid confounds; with S, T and device given, of confounds that go with those time series."""
+    if not isinstance(confounds, torch.Tensor):
+        raise TypeError(f"confounds must be a torch.Tensor, got {type(confounds).__name__}")
+    if confounds.dtype != torch.float32:
+        raise TypeError(f"confounds must be float32, got {confounds.dtype}")
+    if confounds.dim() != 3:
+        raise ValueError(f"confounds must be [S, T, q], got {tuple(confounds.shape)}")
+    cs, ct, q = (int(v) for v in confounds.shape)
+    if S is not None and (cs, ct) != (S, T):
+        raise ValueError(f"confounds must be [S, T, q] = [{S}, {T}, q] as the time series are, got "
+                         f"{tuple(confounds.shape)}")
+    if not 1 <= q <= CONFOUND_MAX:
+        raise ValueError(f"confounds hold q = {q} columns: 1 <= q <= CONFOUND_MAX = {CONFOUND_MAX}")
+    if ct < 2:
+        raise ValueError(f"confounds need T >= 2 frames, got T = {ct}")
+    if ct > _FILTER_MAX_FRAMES:
+        raise ValueError(f"T = {ct} > 2^30 frames: runs this long are not supported")
+    if cs >= _LIMIT:
+        raise ValueError(f"S = {cs} >= 2^31: ingest the cohort in slices of subjects")
+    if device is not None and confounds.device != device:
+        raise ValueError(f"confounds are on {confounds.device}, the time series on {device}")
+    if not confounds.is_contiguous():
+        raise ValueError("confounds must be contiguous")
+    return cs, ct, q
+
+
+def _require_resident_confounds(confounds: torch.Tensor) -> None:
+    if not confounds.is_cuda:
+        raise RuntimeError(
+            f"confounds are on {confounds.device}: connectome_gnn_amd orthonormalises confounds on a ROCm device only "
+            "(there is no CPU fallback; move them with .to('cuda')).")
+
+
+def _confound_basis(confounds: torch.Tensor, S: int, T: int, q: int) -> tuple:
+    dev = confounds.device
+    qpad = (q + 31) // 32 * 32
+    basis = torch.empty(S, T, qpad, dtype=torch.float32, device=dev)
+    rank = torch.empty(S, dtype=torch.int32, device=dev)
+    if S:
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().cgnn_ingest_confound_basis(_lib.ptr(confounds), S, T, q, _lib.ptr(basis),
+                                                              _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank),
+                                                              _lib.stream_ptr(dev)), "cgnn_ingest_confound_basis")
+    return basis, rank
+
+
+def confound_basis(confounds: torch.Tensor) -> tuple:
+    """``(basis, rank)`` of the confounds float32 ``[S, T, q]``, ``1 <= q <= CONFOUND_MAX``: per subject the orthonormal
+    basis of the centred columns by Gram-Schmidt in the given order (module docstring), float32 ``[S, T, qpad]`` with
+    ``qpad`` = ``q`` rounded up to 32 -- a column that is constant or that earlier columns explain is exactly zero, as
+    the padding is -- and the number of kept columns, int32 ``[S]``; a subject with a non-finite confound has a NaN
+    basis and rank -1.  One launch on resident data; no temporaries, no read-back."""
+    S, T, q = _check_confounds(confounds)
+    _require_resident_confounds(confounds)
+    return _confound_basis(confounds, S, T, q)
+
+
+def _regress(timeseries: torch.Tensor, S: int, T: int, n: int, basis: torch.Tensor, out: torch.Tensor) -> None:
+    dev = timeseries.device
+    lib = _lib.load()
+    with _lib.device_guard(dev):
+        need = lib.cgnn_ingest_regress_workspace_bytes(S, T, n)
+        if need < 0:
+            raise _lib.CgnnError(f"cgnn_ingest_regress_workspace_bytes({S}, {T}, {n}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cgnn_ingest_regress(_lib.ptr(timeseries), S, T, n, _lib.ptr(basis), _lib.nbytes(basis),
+                                           int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
+                                           _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress")
+
+
+def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, out=None) -> torch.Tensor:
+    """The time series centred and with the span of the subject's centred confounds projected out of every column:
+    ``xc - Q (Q^T xc)`` with ``Q = confound_basis(confounds)`` (module docstring), float32 ``[S, T, n]`` on the time
+    series' device.  ``confounds`` is float32 contiguous ``[S, T, q]`` on the same device, ``1 <= q <= CONFOUND_MAX``.
+    ``out`` as in ``filter_timeseries``: it may be ``timeseries`` itself, with the same bits as out of place.  Three
+    launches on resident data; the temporaries are the basis ``[S, T, qpad]`` and the means ``[S, n]``.  No read-back."""
+    S, T, n = _check_timeseries(timeseries, None, None)[:3]
+    if T > _FILTER_MAX_FRAMES:
+        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+    q = _check_confounds(confounds, S, T, timeseries.device)[2]
+    _check_out(out, timeseries)
+    _require_resident_timeseries(timeseries)
+    if out is None:
+        out = torch.empty_like(timeseries)
+    if S == 0:
+        return out
+    basis, _ = _confound_basis(confounds, S, T, q)
+    _regress(timeseries, S, T, n, basis, out)
+    return out
+
+
+def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None,
+                      confounds=None) -> torch.Tensor:
     """The time series centred and band-passed column by column, by projection on the DCT-II components
     ``filter_components(T, t_r, high_pass, low_pass)`` of the whole run: float32 ``[S, T, n]`` on the time series'
     device (module docstring), what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.
@@ -417,7 +557,10 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     of the same shape on the same device, which is returned; it may be ``timeseries`` itself (in place, the same bits as
     out of place).  Any other overlap of the two is not checked and gives unspecified values.  Three launches on
     resident data (two without a bound); the temporaries are the basis table ``[T, Kpad]`` and the means ``[S, n]``.
-    No read-back."""
+    ``confounds`` (float32 contiguous ``[S, T, q]`` on the same device, ``1 <= q <= CONFOUND_MAX``) are filtered with
+    the same band and regressed out of the result in place, ``regress_confounds(filter(timeseries), filter(confounds))``:
+    the joint regression on the dropped cosines and the confounds.  The filtered confounds and their basis
+    ``[S, T, qpad]`` are its only further temporaries.  No read-back."""
     S, T, n = _check_timeseries(timeseries, None, None)[:3]
     if T > _FILTER_MAX_FRAMES:
         raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
@@ -432,17 +575,8 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     if K > FILTER_MAX_COMPONENTS:
         raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
                          f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
-    if out is not None:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
-        if out.dtype != torch.float32:
-            raise TypeError(f"out must be float32, got {out.dtype}")
-        if out.shape != timeseries.shape:
-            raise ValueError(f"out must be {tuple(timeseries.shape)} as the time series are, got {tuple(out.shape)}")
-        if out.device != timeseries.device:
-            raise ValueError(f"out is on {out.device}, the time series on {timeseries.device}")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
+    _check_out(out, timeseries)
+    q = None if confounds is None else _check_confounds(confounds, S, T, timeseries.device)[2]
     _require_resident_timeseries(timeseries)
     if out is None:
         out = torch.empty_like(timeseries)
@@ -462,6 +596,11 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
         _lib.check(lib.cgnn_ingest_filter(_lib.ptr(timeseries), S, T, n, (ctypes.c_int32 * K)(*comps), K,
                                           int(complement), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
                                           _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_filter")
+    if confounds is not None:                         # the same band on the confounds, then out -= Q (Q^T out) in place
+        clean = filter_timeseries(confounds, t_r=t_r, high_pass=high_pass, low_pass=low_pass)
+        basis, _ = _confound_basis(clean, S, T, q)
+        del clean
+        _regress(out, S, T, n, basis, out)
     return out
 
 

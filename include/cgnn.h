@@ -674,6 +674,54 @@ int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t n, const i
                        int32_t complement, void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Confound regression of ROI time series: head motion, tissue signals and their expansions taken out
+ * of every column, per subject.  Two calls: the orthonormal basis of a subject's confounds, and its projection out of
+ * the frames by cgnn_ingest_filter's kernel in complement form with a table per subject.
+ *
+ * cgnn_ingest_confound_basis.  confounds: float [S, T, q], one row per frame, 1 <= q <= CGNN_CONFOUND_MAX.  Per subject,
+ * in fp64:
+ *   norms      m_j = the mean of column j, cc_j = c_j - m_j, s_j = sqrt(sum_t cc_j[t]^2).  A column with s_j == 0 (exactly
+ *              constant) is dropped; the others are u_j = cc_j / s_j.
+ *   basis      Gram-Schmidt in the given order: r_j = u_j - sum_{k < j, kept} q_k (q_k . u_j), d_j = |r_j|^2; column j is
+ *              kept iff d_j > CGNN_CONFOUND_RANK_TOL, and then q_j = r_j / sqrt(d_j) (a positive coefficient on u_j);
+ *              otherwise it is dropped: the columns before it explain it.
+ *   output     basis: float [S, T, qpad], qpad = q rounded up to 32, 16-byte aligned: fl32(q_j) in a kept column,
+ *              exactly 0.0 in a dropped one and in the padding.  rank: int32 [S], the number of kept columns.
+ *   non-finite a subject with a NaN or Inf anywhere in its confounds (a non-finite s_j) gets an all-NaN basis and rank
+ *              -1, so that the regression gives it NaN and never "nothing regressed"; other subjects keep their bits.
+ *   arithmetic CholeskyQR2 in fp64: G = U^T U with a fixed owner per pair (j, k) summing over the frames in ascending
+ *              order, a q x q Cholesky in LDS whose pivot of column j is d_j (the rank rule is applied to it), the same
+ *              again on U R1^-1 with the kept set held fixed, and Q = fl32(U (R2 R1)^-1): one rounding to fp32.
+ *   bytes      cgnn_ingest_confound_basis_bytes(S, T, q) = 4 S T qpad is what `basis` must hold; rank_bytes >= 4 S.
+ * One launch on `stream`: a persistent grid over the subjects, a workgroup of 4 waves per subject; five passes over the
+ * subject's confounds, nothing in LDS depends on T.  No workspace.  No atomics, nothing depends on the grid: the same
+ * bits on every run and for every grid.
+ * q < 1, q > CGNN_CONFOUND_MAX, T < 2, T > 2^30, S < 0, S >= 2^31, a NULL, misaligned or short buffer return CGNN_EINVAL
+ * before any launch (the byte count: a negative value); S == 0 returns CGNN_OK with nothing launched.
+ *
+ * cgnn_ingest_regress.  ts: float [S, T, n] as cgnn_ingest_filter takes it; basis: float [S, T, qpad] as above (any
+ * table whose columns are orthonormal or zero), qpad 32 or 64, 16-byte aligned, basis_bytes >= 4 S T qpad.
+ *   output     xc[t,i] = fl32(double(x[t,i]) - m_i) as cgnn_ingest_filter centres; out = xc - Q (Q^T xc), the products on
+ *              the fp32 matrix pipe, every sum in ascending order of its index.  Columns never mix: a constant column
+ *              gives exactly 0, a NaN stays in its column of its subject; a subject with a NaN basis is all NaN.
+ *   out        float [S, T, n]; may be `ts` itself, with the same bits as out of place
+ *   workspace  cgnn_ingest_regress_workspace_bytes(S, T, n) = 8 S n bytes, 16-byte aligned: the means double [S, n]
+ * Two launches on `stream`: cgnn_ingest_filter's means and its k_filter<qpad> in complement form, whose table pointer
+ * advances by T * qpad floats per subject.  The same bits on every run and for every grid.
+ * qpad outside {32, 64}, T < 2, T > 2^30, S < 0, n <= 0, S * n >= 2^31, a NULL, misaligned or short buffer return
+ * CGNN_EINVAL before any launch; S == 0 returns CGNN_OK with nothing launched.  Element offsets are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+#define CGNN_CONFOUND_MAX 64
+#define CGNN_CONFOUND_RANK_TOL 1e-10
+int64_t cgnn_ingest_confound_basis_bytes(int64_t S, int32_t T, int32_t q);
+int cgnn_ingest_confound_basis(const float* confounds, int64_t S, int32_t T, int32_t q, float* basis,
+                               int64_t basis_bytes, int32_t* rank, int64_t rank_bytes, void* stream);
+int64_t cgnn_ingest_regress_workspace_bytes(int64_t S, int32_t T, int32_t n);
+int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_t n, const float* basis, int64_t basis_bytes,
+                        int32_t qpad, void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
+                        void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
