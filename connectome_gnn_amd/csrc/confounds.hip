@@ -7,6 +7,10 @@
 // Q is float [T, qpad], qpad = q rounded up to 32: fl32(q_j) in a kept column, exactly 0 in a dropped one and in the
 // padding.  A subject with a non-finite s_j (a NaN or Inf anywhere in its confounds) gets an all-NaN Q and rank -1.
 //
+// cgnn_ingest_confound_basis_masked is the same with a frame mask keep [S, T]: every mean, norm, inner
+// product and pivot over the subject's kept frames, zero rows of Q at the censored ones.  The mask is a template argument
+// of the kernel and a predicate beside `t < T` in the two norm passes, in the lambda that stages u and in the final write.
+//
 // The kernel computes that Q by CholeskyQR2: nothing it keeps in LDS depends on T.
 //   k_confound_basis<kQ>  kQ = qpad.  A persistent grid over the subjects, a workgroup of 4 waves per subject, grid
 //                   stride.  Five passes over the subject's confounds (q / n of what the frames are):
@@ -84,9 +88,13 @@ __device__ void invert(const double* r, double* w, int ld, int q, int q4, const 
   __syncthreads();
 }
 
-template <int kQ>
+// kMask: `keep` [S, T] selects the frames.  Every mean, norm, inner product and pivot runs over the
+// kept frames Tk of the subject; a censored frame's values are loaded beside its flag (no load waits for another) and
+// left out by selection: it is a zero row of u and an exact zero row of Q.
+template <int kQ, bool kMask>
 __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __restrict__ conf, int64_t S, int T, int q,
-                                                             float* __restrict__ basis, int32_t* __restrict__ rank) {
+                                                             float* __restrict__ basis, int32_t* __restrict__ rank,
+                                                             const uint8_t* __restrict__ keep) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int kG = kThreads / kQ;           // frame phases of the means and norms
   constexpr int kB = kQ / 16;                 // a thread owns kB x kB pairs of G
@@ -111,6 +119,22 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
   for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
     const float* __restrict__ c = conf + s * T * q;
     float* __restrict__ out = basis + s * T * kQ;
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
+    auto kept_at = [&](int t) {               // frame t (< T) counts
+      if constexpr (kMask) return kp[t] != 0;
+      else return true;
+    };
+    double frames = (double)T;                // Tk: what the means divide by
+    if constexpr (kMask) {                    // counted by everyone, merged through `part` (an integer sum: exact)
+      int cnt = 0;
+      for (int t = tid; t < T; t += kThreads) cnt += kept_at(t);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if ((tid & 63) == 0) part[tid >> 6] = (double)cnt;
+      __syncthreads();
+      frames = ((part[0] + part[1]) + part[2]) + part[3];
+      __syncthreads();                        // the passes below overwrite part
+    }
 
     // ---- means, then centred norms ----
     for (int pass = 0; pass < 2; ++pass) {
@@ -120,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
 #pragma unroll 8
         for (int t = phase; t < T; t += kG) {
           const double v = (double)c[(int64_t)t * q + col] - m;
-          sum += pass ? v * v : v;
+          sum += !kept_at(t) ? 0.0 : pass ? v * v : v;
         }
       }
       part[phase * kQ + col] = sum;
@@ -129,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
         double total = part[tid];
         for (int g = 1; g < kG; ++g) total += part[g * kQ + tid];
         if (!pass) {
-          mu[tid] = total / (double)T;
+          mu[tid] = kMask && frames == 0.0 ? 0.0 : total / frames;
         } else {
           const double sj = sqrt(total);
           sn[tid] = sj;
@@ -142,7 +166,8 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
     bool finite = true;
     for (int j = 0; j < q; ++j) finite = finite && isfinite(sn[j]);
     if (!finite) {                            // never "nothing regressed": the subject's output is NaN
-      for (int64_t e = tid; e < (int64_t)T * kQ; e += kThreads) out[e] = __builtin_nanf("");
+      for (int64_t e = tid; e < (int64_t)T * kQ; e += kThreads)
+        out[e] = kept_at((int)(e / kQ)) ? __builtin_nanf("") : 0.0f;
       if (tid == 0) rank[s] = -1;
       __syncthreads();                        // (the next subject overwrites sn)
       continue;
@@ -151,11 +176,14 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
     // a block of frames: 32 rows of c are 32 q consecutive floats, loaded into registers a block ahead, then centred
     // and scaled into ub; frames past T are zeros, and so are the columns past q, which nobody writes again
     float pv[kSlots];
+    bool pk[kSlots];                          // kMask: the frame of pv[i] is kept
     auto load = [&](int t0) {
 #pragma unroll
       for (int i = 0; i < kSlots; ++i) {
         const int e = tid + kThreads * i;
-        pv[i] = e < kFB * q && t0 + e / q < T ? c[(int64_t)t0 * q + e] : 0.0f;
+        const bool in = e < kFB * q && t0 + e / q < T;
+        pk[i] = in && kept_at(t0 + e / q);
+        pv[i] = in ? c[(int64_t)t0 * q + e] : 0.0f;
       }
     };
     auto store = [&](int t0) {
@@ -164,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
         const int e = tid + kThreads * i;
         if (e < kFB * q) {
           const int f = e / q, j = e - f * q;
-          ub[f * q4 + j] = t0 + f < T ? ((double)pv[i] - mu[j]) * inv[j] : 0.0;
+          ub[f * q4 + j] = (kMask ? pk[i] : t0 + f < T) ? ((double)pv[i] - mu[j]) * inv[j] : 0.0;
         }
       }
     };
@@ -254,7 +282,8 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
       if (t0 + kFB < T) load(t0 + kFB);
       for (int e = tid; e < kFB * kQ; e += kThreads) {
         const int f = e / kQ, j = e - f * kQ;
-        if (t0 + f < T) out[(int64_t)(t0 + f) * kQ + j] = j < q && kept[j] ? (float)apply(A, f * q4 + j) : 0.0f;
+        if (t0 + f < T)
+          out[(int64_t)(t0 + f) * kQ + j] = j < q && kept[j] && kept_at(t0 + f) ? (float)apply(A, f * q4 + j) : 0.0f;
       }
       __syncthreads();
     }
@@ -272,14 +301,34 @@ int check(int64_t S, int32_t T, int32_t q) {
   return q < 1 || q > CGNN_CONFOUND_MAX ? CGNN_EINVAL : CGNN_OK;
 }
 
-template <int kQ>
-int launch(const float* conf, int64_t S, int32_t T, int32_t q, float* basis, int32_t* rank, hipStream_t hs) {
+template <int kQ, bool kMask>
+int launch(const float* conf, int64_t S, int32_t T, int32_t q, const uint8_t* keep, float* basis, int32_t* rank,
+           hipStream_t hs) {
   const size_t lds = lds_of(kQ, q);
-  if (!cgnn_raise_lds_limit<k_confound_basis<kQ>>(kLdsBytes)) return CGNN_ELAUNCH;
+  if (!cgnn_raise_lds_limit<k_confound_basis<kQ, kMask>>(kLdsBytes)) return CGNN_ELAUNCH;
   const int grid = cgnn_grid_for(S, cgnn_wg_per_cu_by_lds(lds, kLdsBytes));
-  k_confound_basis<kQ><<<grid, kThreads, lds, hs>>>(conf, S, T, q, basis, rank);
+  k_confound_basis<kQ, kMask><<<grid, kThreads, lds, hs>>>(conf, S, T, q, basis, rank, keep);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
+}
+
+// what both entry points check and do; keep == nullptr: every frame
+int basis_call(const float* confounds, int64_t S, int32_t T, int32_t q, const uint8_t* keep, int64_t keep_bytes,
+               bool masked, float* basis, int64_t basis_bytes, int32_t* rank, int64_t rank_bytes, void* stream) {
+  if (check(S, T, q) != CGNN_OK || basis_bytes < 0 || rank_bytes < 0 || keep_bytes < 0) return CGNN_EINVAL;
+  if (S == 0) return CGNN_OK;
+  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (!confounds || !basis || !rank || ((bits(confounds) | bits(rank)) & 3) || (bits(basis) & 15)) return CGNN_EINVAL;
+  if (masked && !keep) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(keep, keep_bytes, S * T);
+  CGNN_NEED_BYTES(basis, basis_bytes, cgnn_ingest_confound_basis_bytes(S, T, q));
+  CGNN_NEED_BYTES(rank, rank_bytes, S * (int64_t)sizeof(int32_t));
+  hipStream_t hs = cgnn_stream(stream);
+  if (masked)
+    return pad_of(q) == 32 ? launch<32, true>(confounds, S, T, q, keep, basis, rank, hs)
+                           : launch<64, true>(confounds, S, T, q, keep, basis, rank, hs);
+  return pad_of(q) == 32 ? launch<32, false>(confounds, S, T, q, nullptr, basis, rank, hs)
+                         : launch<64, false>(confounds, S, T, q, nullptr, basis, rank, hs);
 }
 
 }  // namespace
@@ -291,13 +340,12 @@ extern "C" int64_t cgnn_ingest_confound_basis_bytes(int64_t S, int32_t T, int32_
 
 extern "C" int cgnn_ingest_confound_basis(const float* confounds, int64_t S, int32_t T, int32_t q, float* basis,
                                           int64_t basis_bytes, int32_t* rank, int64_t rank_bytes, void* stream) {
-  if (check(S, T, q) != CGNN_OK || basis_bytes < 0 || rank_bytes < 0) return CGNN_EINVAL;
-  if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!confounds || !basis || !rank || ((bits(confounds) | bits(rank)) & 3) || (bits(basis) & 15)) return CGNN_EINVAL;
-  CGNN_NEED_BYTES(basis, basis_bytes, cgnn_ingest_confound_basis_bytes(S, T, q));
-  CGNN_NEED_BYTES(rank, rank_bytes, S * (int64_t)sizeof(int32_t));
-  hipStream_t hs = cgnn_stream(stream);
-  return pad_of(q) == 32 ? launch<32>(confounds, S, T, q, basis, rank, hs)
-                         : launch<64>(confounds, S, T, q, basis, rank, hs);
+  return basis_call(confounds, S, T, q, nullptr, 0, false, basis, basis_bytes, rank, rank_bytes, stream);
+}
+
+// frame censoring: the same launch over the frames keep [S, T] selects
+extern "C" int cgnn_ingest_confound_basis_masked(const float* confounds, int64_t S, int32_t T, int32_t q,
+                                                 const uint8_t* keep, int64_t keep_bytes, float* basis,
+                                                 int64_t basis_bytes, int32_t* rank, int64_t rank_bytes, void* stream) {
+  return basis_call(confounds, S, T, q, keep, keep_bytes, true, basis, basis_bytes, rank, rank_bytes, stream);
 }

@@ -37,6 +37,12 @@
 //                   chunk is 16 frames (one block a wave), which is what fits the second workgroup in; at 256 one
 //                   workgroup has the CU to itself and the chunk of B is double-buffered instead.
 //
+// Frame censoring: cgnn_ingest_regress_masked is cgnn_ingest_regress with a frame mask keep [S, T].  The
+// mask enters k_filter_mean and k_filter as one more template argument and as a predicate beside `t < T`: the mean is
+// the kept frames' sum over their count, centre() gives a censored frame a zero row (phase 1, phase 2 and the kPad == 0
+// stream), and phase 2 selects an exact zero for it.  The unmasked instantiations keep their code.  k_design writes the
+// design of a band that is removed by regression, [table values | confounds] per subject, with k_filter_basis's values.
+//
 // Accumulation is fp32 in ascending order of the frame (phase 1) and of the component (phase 2), no atomics, and no work
 // assignment depends on the grid: the same bits on every run and for every grid.  Columns never mix: column j of xc
 // meets column j of C and of Y only.  Frames past T and columns past n are zeros in LDS, never read from memory and
@@ -92,6 +98,12 @@ struct Comps {
   int32_t k[CGNN_FILTER_MAX_COMPONENTS];
 };
 
+// b_k[t] of a T-frame run, scale = sqrt(2 / T): the one value function of k_filter_basis and k_design
+__device__ __forceinline__ float basis_value(int64_t t, int k, int T, double scale) {
+  const int64_t arg = ((2 * t + 1) * (int64_t)k) % (4 * (int64_t)T);                // cos has period 4 T in it
+  return (float)(scale * cospi((double)arg / (double)(2 * (int64_t)T)));
+}
+
 __global__ __launch_bounds__(kThreads) void k_filter_basis(Comps comps, int K, int kpad, int T,
                                                            float* __restrict__ table) {
   const int64_t total = (int64_t)T * kpad;
@@ -99,19 +111,32 @@ __global__ __launch_bounds__(kThreads) void k_filter_basis(Comps comps, int K, i
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
     const int64_t t = e / kpad;
     const int c = (int)(e - t * kpad);
-    float v = 0.0f;
-    if (c < K) {
-      const int64_t arg = ((2 * t + 1) * (int64_t)comps.k[c]) % (4 * (int64_t)T);     // cos has period 4 T in it
-      v = (float)(scale * cospi((double)arg / (double)(2 * (int64_t)T)));
-    }
-    table[e] = v;
+    table[e] = c < K ? basis_value(t, comps.k[c], T, scale) : 0.0f;
+  }
+}
+
+// The design of a regression under censoring: float [S, T, K + q] = [table values | confounds], the
+// cosines at the frame's own t on the grid of the whole run.  A thread per entry, grid stride.
+__global__ __launch_bounds__(kThreads) void k_design(Comps comps, int K, const float* __restrict__ conf, int64_t S,
+                                                     int T, int q, float* __restrict__ design) {
+  const int w = K + q;
+  const int64_t total = S * T * w;
+  const double scale = sqrt(2.0 / (double)T);
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const int64_t row = e / w;                // s * T + t
+    const int c = (int)(e - row * w);
+    design[e] = c < K ? basis_value(row % T, comps.k[c], T, scale) : conf[row * q + (c - K)];
   }
 }
 
 constexpr int kMeanFrames = 8;                // frames of a block; a thread has the next block's loads in flight
 
+// kMask: `keep` [S, T] selects the frames: the sum and the count run over the kept ones -- a censored
+// frame's value is loaded beside its flag (no load waits for another) and then left out by selection -- and a subject
+// without a kept frame has mean 0
+template <bool kMask>
 __global__ __launch_bounds__(kThreads) void k_filter_mean(const float* __restrict__ ts, int64_t S, int T, int n,
-                                                          double* __restrict__ mean) {
+                                                          double* __restrict__ mean, const uint8_t* __restrict__ keep) {
   __shared__ double part[kThreads / 64][kCols];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int chunks = (n + kCols - 1) / kCols;
@@ -121,34 +146,64 @@ __global__ __launch_bounds__(kThreads) void k_filter_mean(const float* __restric
     const int col = (int)(item - s * chunks) * kCols + lane;
     const bool act = col < n;
     const float* __restrict__ x = ts + s * T * n + (act ? col : 0);
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
+    auto frame = [&](int t) {                 // is frame t one that counts
+      if constexpr (kMask) return t < T && kp[t] != 0;
+      else return t < T;
+    };
+    // kMask: the flags of a block of frames tb, tb + 4, .. are one load, lane i's of frame tb + 4 i, and a ballot (every
+    // lane takes part, so the lanes past n walk column 0 along and write nothing)
+    auto flags = [&](int tb) {
+      if constexpr (kMask) return (unsigned)__ballot(lane < kMeanFrames && frame(tb + 4 * lane));
+      else return 0u;
+    };
     double sum = 0.0;                         // of frames wave, wave + 4, ..., in that order
-    if (act) {
+    int cnt = 0;                              // kMask: this wave's kept frames
+    if (act || kMask) {
       float v[kMeanFrames], nx[kMeanFrames];
+      unsigned vk = 0, nk = flags(wave);      // kMask: bit i says that v[i] / nx[i] is a kept frame
 #pragma unroll
       for (int i = 0; i < kMeanFrames; ++i) nx[i] = wave + 4 * i < T ? x[(int64_t)(wave + 4 * i) * n] : 0.0f;
       for (int t0 = wave; t0 < T; t0 += 4 * kMeanFrames) {
+        vk = nk;
+        nk = flags(t0 + 4 * kMeanFrames);
 #pragma unroll
         for (int i = 0; i < kMeanFrames; ++i) {         // the next block's loads fly while this one is summed
           const int t = t0 + 4 * (kMeanFrames + i);
           v[i] = nx[i];
           nx[i] = t < T ? x[(int64_t)t * n] : 0.0f;
         }
+        if constexpr (kMask) cnt += __builtin_popcount(vk);
 #pragma unroll
-        for (int i = 0; i < kMeanFrames; ++i) sum += (double)v[i];      // (the padding adds zeros)
+        for (int i = 0; i < kMeanFrames; ++i)           // (the padding adds zeros; a censored frame is left out)
+          sum += !kMask || ((vk >> i) & 1) ? (double)v[i] : 0.0;
       }
     }
     part[wave][lane] = sum;
-    __syncthreads();
-    if (wave == 0 && act)
-      mean[s * n + col] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (double)T;
+    if constexpr (kMask) {
+      __shared__ int kept[kThreads / 64][kCols];
+      kept[wave][lane] = cnt;
+      __syncthreads();
+      if (wave == 0 && act) {
+        const int tk = kept[0][lane] + kept[1][lane] + kept[2][lane] + kept[3][lane];
+        const double total = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+        mean[s * n + col] = tk ? total / (double)tk : 0.0;
+      }
+    } else {
+      __syncthreads();
+      if (wave == 0 && act)
+        mean[s * n + col] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (double)T;
+    }
     __syncthreads();
   }
 }
 
 // 4 loaded entries of frame t, columns c .. c + 3 of the item -> xc; frames past T and columns past n give zeros
-__device__ __forceinline__ f32x4 centre(f32x4 v, int t, int T, int c, int col0, int n, const double* mu) {
+// (and so does a censored frame: kept == false)
+__device__ __forceinline__ f32x4 centre(f32x4 v, int t, int T, int c, int col0, int n, const double* mu,
+                                        bool kept = true) {
   f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  if (t < T) {
+  if (t < T && kept) {
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (col0 + c + e < n) z[e] = (float)((double)v[e] - mu[c + e]);
@@ -170,11 +225,14 @@ __device__ __forceinline__ void store4(float* o, int t, int T, int col, int n, f
 }
 
 // `ts` and `out` may be the same array: neither is __restrict__.  table_stride: floats between the tables of two
-// subjects (cgnn_ingest_regress: a basis per subject), 0 for the one table of the cohort
-template <int kPad, bool kVec>
+// subjects (cgnn_ingest_regress: a basis per subject), 0 for the one table of the cohort.  kMask:
+// `keep` [S, T] selects the frames; a censored frame is a zero row of xc in phase 1 and an exact zero row of the output
+// (the table's rows there are zeros too: cgnn_ingest_confound_basis_masked writes them so)
+template <int kPad, bool kVec, bool kMask = false>
 __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S, int T, int n, int complement,
                                                      const float* __restrict__ tables, int64_t table_stride,
-                                                     const double* __restrict__ mean, float* out) {
+                                                     const double* __restrict__ mean, float* out,
+                                                     const uint8_t* __restrict__ keep) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   double* mu = reinterpret_cast<double*>(lds);                // [64] the item's means, 0 past n
   float* area = reinterpret_cast<float*>(mu + kCols);
@@ -202,24 +260,36 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
     const float* x = ts + s * T * n;
     float* o = out + s * T * n;
     const float* __restrict__ table = tables + s * table_stride;
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
+    auto kept_at = [&](int t) {               // kMask: frame t is inside the run and kept
+      if constexpr (kMask) return t < T && kp[t] != 0;
+      else return true;
+    };
 
     __syncthreads();                          // the previous item's last chunk still reads mu and Y
     if (tid < kCols) mu[tid] = col0 + tid < n ? mean[s * n + col0 + tid] : 0.0;
 
     f32x4 px[kXSlots];
-    auto load_x = [&](int t0) {
+    bool fl = true;                           // kMask: frame t0 + (tid & 31) of px's step is kept: one load for the step,
+    auto load_x = [&](int t0) {               // which a ballot turns into the step's 32 flags where they are used
 #pragma unroll
       for (int q = 0; q < kXSlots; ++q) px[q] = load4<kVec>(x, t0 + xrow[q], T, col0 + xcol[q], n);
+      if constexpr (kMask) fl = kept_at(t0 + (tid & 31));
+    };
+    auto kept_rows = [&](bool f) {            // (every thread of the workgroup is here)
+      if constexpr (kMask) return (uint32_t)__ballot(f);
+      else return ~0u;
     };
 
     if constexpr (kPad == 0) {                // pure centring: a stream
       __syncthreads();
       for (int ks = 0; ks < nks; ++ks) {
         load_x(ks * kFS);
+        const uint32_t rows = kept_rows(fl);
 #pragma unroll
         for (int q = 0; q < kXSlots; ++q)
           store4<kVec>(o, ks * kFS + xrow[q], T, col0 + xcol[q], n,
-                       centre(px[q], ks * kFS + xrow[q], T, xcol[q], col0, n, mu));
+                       centre(px[q], ks * kFS + xrow[q], T, xcol[q], col0, n, mu, (rows >> xrow[q]) & 1));
       }
     } else {
       f32x4 pb[kBSlots];
@@ -243,10 +313,11 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
           const int e = 4 * (tid + kThreads * q);
           *reinterpret_cast<f32x4*>(&bb[(e / kPad) * kLd1 + e % kPad]) = pb[q];
         }
+        const uint32_t rows = kept_rows(fl);
 #pragma unroll
         for (int q = 0; q < kXSlots; ++q)
           *reinterpret_cast<f32x4*>(&bx[xrow[q] * kLdX + xcol[q]]) =
-              centre(px[q], t0 + xrow[q], T, xcol[q], col0, n, mu);
+              centre(px[q], t0 + xrow[q], T, xcol[q], col0, n, mu, (rows >> xrow[q]) & 1);
       };
       load_x(0);
       load_b(0);
@@ -304,6 +375,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
       constexpr int kB2Slots = kF2 * kPad / 4 / kThreads, kX2Slots = kF2 * (kCols / 4) / kThreads;
       static_assert(kB2Slots * kThreads * 4 == kF2 * kPad && kX2Slots * kThreads == kF2 * (kCols / 4), "whole slots");
       f32x4 pc2[kB2Slots], px2[kX2Slots];
+      static_assert(!kMask || kF2 <= 32, "a masked chunk's flags are one 32-bit ballot");
       auto load_chunk = [&](int t0) {
         const float* __restrict__ src = table + (int64_t)t0 * kPad;
 #pragma unroll
@@ -336,6 +408,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
 #pragma unroll
           for (int q = 0; q < kX2Slots; ++q) px2[q] = load4<kVec>(x, t0 + xrow[q], T, col0 + xcol[q], n);
         }
+        const bool fl2 = kept_at(t0 + (tid & 31));
         const float* __restrict__ pa = bc + (kDouble ? cur : 0) * chunk_floats(kPad) + fcol * kLd2 + frow;
         const float* __restrict__ pc = cl + frow * kLdX + wave * 16 + fcol;
         f32x4 y[kFB];
@@ -357,10 +430,12 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
         if (kDouble && more) store_chunk(cur ^ 1);
         __syncthreads();                      // Y is whole; every wave is past its reads of this chunk of B
         if (!kDouble && more) store_chunk(0);
+        const uint32_t rows2 = kept_rows(fl2);
 #pragma unroll
         for (int q = 0; q < kX2Slots; ++q) {
           f32x4 v = *reinterpret_cast<const f32x4*>(&yl[xrow[q] * kLdY + xcol[q]]);
           if (complement) v = centre(px2[q], t0 + xrow[q], T, xcol[q], col0, n, mu) - v;
+          if (kMask && !((rows2 >> xrow[q]) & 1)) v = f32x4{0.f, 0.f, 0.f, 0.f};      // selected, never multiplied
           store4<kVec>(o, t0 + xrow[q], T, col0 + xcol[q], n, v);
         }
         __syncthreads();                      // the next chunk overwrites Y
@@ -382,14 +457,15 @@ int check(int64_t S, int32_t T, int32_t n, int32_t K) {
 
 int64_t table_bytes(int32_t T, int32_t K) { return cgnn_align_up((int64_t)T * pad_of(K) * (int64_t)sizeof(float), 16); }
 
-template <int kPad, bool kVec>
+template <int kPad, bool kVec, bool kMask = false>
 int launch_as(const float* ts, int64_t S, int32_t T, int32_t n, int32_t complement, const float* table,
-              int64_t table_stride, const double* mean, float* out, hipStream_t hs) {
+              int64_t table_stride, const double* mean, float* out, hipStream_t hs, const uint8_t* keep = nullptr) {
   constexpr size_t lds = lds_of(kPad);
-  if (!cgnn_raise_lds_limit<k_filter<kPad, kVec>>(kLdsBytes)) return CGNN_ELAUNCH;
+  if (!cgnn_raise_lds_limit<k_filter<kPad, kVec, kMask>>(kLdsBytes)) return CGNN_ELAUNCH;
   const int64_t items = S * ((n + kCols - 1) / kCols);
   const int grid = cgnn_grid_for(items, cgnn_wg_per_cu_by_lds(lds, kLdsBytes));
-  k_filter<kPad, kVec><<<grid, kThreads, lds, hs>>>(ts, S, T, n, complement, table, table_stride, mean, out);
+  k_filter<kPad, kVec, kMask><<<grid, kThreads, lds, hs>>>(ts, S, T, n, complement, table, table_stride, mean, out,
+                                                           keep);
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
 }
@@ -407,6 +483,18 @@ int launch(int kpad, const float* ts, int64_t S, int32_t T, int32_t n, int32_t c
     case 192: return launch_as<192, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
     case 224: return launch_as<224, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
     default: return launch_as<256, kVec>(ts, S, T, n, complement, table, table_stride, mean, out, hs);
+  }
+}
+
+// the masked complement form: pure centring (no table), or a basis of 32 or 64 columns per subject
+template <bool kVec>
+int launch_masked(int qpad, const float* ts, int64_t S, int32_t T, int32_t n, const float* basis, const double* mean,
+                  float* out, hipStream_t hs, const uint8_t* keep) {
+  const int64_t stride = (int64_t)T * qpad;
+  switch (qpad) {
+    case 0: return launch_as<0, kVec, true>(ts, S, T, n, 1, basis, stride, mean, out, hs, keep);
+    case 32: return launch_as<32, kVec, true>(ts, S, T, n, 1, basis, stride, mean, out, hs, keep);
+    default: return launch_as<64, kVec, true>(ts, S, T, n, 1, basis, stride, mean, out, hs, keep);
   }
 }
 
@@ -446,7 +534,7 @@ extern "C" int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t
     CGNN_CHECK_LAUNCH();
   }
   const int64_t items = S * ((n + kCols - 1) / kCols);
-  k_filter_mean<<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean);
+  k_filter_mean<false><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, nullptr);
   CGNN_CHECK_LAUNCH();
   const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
   return vec ? launch<true>(kpad, ts, S, T, n, complement, table, 0, mean, out, hs)
@@ -477,10 +565,72 @@ extern "C" int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_
   hipStream_t hs = cgnn_stream(stream);
   double* mean = static_cast<double*>(workspace);
   const int64_t items = S * ((n + kCols - 1) / kCols);
-  k_filter_mean<<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean);
+  k_filter_mean<false><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, nullptr);
   CGNN_CHECK_LAUNCH();
   const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
   const int64_t stride = (int64_t)T * qpad;
   return vec ? launch<true>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs)
              : launch<false>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs);
+}
+
+// ---- frame censoring: the same two launches with the frames selected by keep [S, T] ----
+
+extern "C" int cgnn_ingest_regress_masked(const float* ts, int64_t S, int32_t T, int32_t n, const uint8_t* keep,
+                                          int64_t keep_bytes, const float* basis, int64_t basis_bytes, int32_t qpad,
+                                          void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
+                                          void* stream) {
+  if (check(S, T, n, 0) != CGNN_OK || (qpad != 0 && qpad != 32 && qpad != 64)) return CGNN_EINVAL;
+  if (keep_bytes < 0 || basis_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
+  if (S == 0) return CGNN_OK;
+  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (!ts || !keep || !out || !workspace || ((bits(ts) | bits(out)) & 3) || ((bits(basis) | bits(workspace)) & 15))
+    return CGNN_EINVAL;
+  if ((qpad == 0) != (basis == nullptr)) return CGNN_EINVAL;  // masked centring has no basis, a regression has one
+  CGNN_NEED_BYTES(keep, keep_bytes, S * T);
+  CGNN_NEED_BYTES(workspace, workspace_bytes, S * n * (int64_t)sizeof(double));
+  if (qpad && basis_bytes / (int64_t)sizeof(float) / qpad / T < S) return CGNN_EINVAL;
+  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
+
+  hipStream_t hs = cgnn_stream(stream);
+  double* mean = static_cast<double*>(workspace);
+  const int64_t items = S * ((n + kCols - 1) / kCols);
+  k_filter_mean<true><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, keep);
+  CGNN_CHECK_LAUNCH();
+  const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
+  return vec ? launch_masked<true>(qpad, ts, S, T, n, basis, mean, out, hs, keep)
+             : launch_masked<false>(qpad, ts, S, T, n, basis, mean, out, hs, keep);
+}
+
+// ---- the design of a regression under censoring: [table values | confounds] per subject ----
+
+namespace {
+int check_design(int64_t S, int32_t T, int32_t K, int32_t q) {
+  if (S < 0 || S >= ((int64_t)1 << 31) || T < 2 || T > kMaxFrames) return CGNN_EINVAL;
+  return K < 0 || q < 0 || K + q < 1 || K + q > CGNN_CONFOUND_MAX ? CGNN_EINVAL : CGNN_OK;
+}
+}  // namespace
+
+extern "C" int64_t cgnn_ingest_design_bytes(int64_t S, int32_t T, int32_t K, int32_t q) {
+  if (check_design(S, T, K, q) != CGNN_OK) return CGNN_EINVAL;
+  return S * T * (K + q) * (int64_t)sizeof(float);            // (S < 2^31, T <= 2^30, 256: below 2^63)
+}
+
+extern "C" int cgnn_ingest_design(const float* confounds, int64_t S, int32_t T, int32_t q, const int32_t* comps,
+                                  int32_t K, float* design, int64_t design_bytes, void* stream) {
+  if (check_design(S, T, K, q) != CGNN_OK || (K > 0 && !comps) || design_bytes < 0) return CGNN_EINVAL;
+  Comps list;
+  for (int i = 0; i < K; ++i) {
+    if (comps[i] < 1 || comps[i] > T - 1 || (i > 0 && comps[i] <= comps[i - 1])) return CGNN_EINVAL;
+    list.k[i] = comps[i];
+  }
+  for (int i = K; i < CGNN_FILTER_MAX_COMPONENTS; ++i) list.k[i] = 0;
+  if ((q == 0) != (confounds == nullptr)) return CGNN_EINVAL;
+  if (S == 0) return CGNN_OK;
+  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (!design || ((bits(confounds) | bits(design)) & 3)) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(design, design_bytes, cgnn_ingest_design_bytes(S, T, K, q));
+  const int64_t blocks = (S * T * (K + q) + kThreads - 1) / kThreads;
+  k_design<<<cgnn_grid_for(blocks, 8), kThreads, 0, cgnn_stream(stream)>>>(list, K, confounds, S, T, q, design);
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
 }

@@ -23,6 +23,9 @@
 //              off-diagonal entries themselves, never as F - p.
 //     merge    the 4 x 8 slot sums and the four waves' triangle sums through LDS, in wave and slot order; thread 0
 //              forms the quotient in fp64.
+// cgnn_ingest_shrinkage_masked: with a frame mask keep [S, T] a unit's frames are its window's kept
+// ones; the kernel counts them (L_u) and L_u stands wherever L does: B = L_u sum_{t kept} s_t^2, a = (B - F) / (L_u O),
+// and L_u <= 2 gives 0.  The mask is a template argument and a predicate beside `t < L`.
 // No atomics, and no work assignment depends on the grid: the same bits on every run and for every grid.  Overlapping
 // windows read their frames again (each window has statistics of its own).  Element offsets into `ts` and `matrices`
 // are 64-bit.
@@ -54,12 +57,17 @@ __device__ __forceinline__ double wave_sum8(const double (&v)[kLwFrames], int la
   return c;
 }
 
+// kMask: `keep` [S, T] selects the frames; a unit's frames are its window's kept ones, L_u of them,
+// counted here, and L_u stands wherever L does in the estimate.  A censored frame's values are loaded beside its flag and
+// left out by selection.
+template <bool kMask>
 __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts, int64_t U, int T, int n, int W, int L,
                                                    int stride, const float* __restrict__ stats,
-                                                   const float* __restrict__ matrices, double* __restrict__ alpha) {
+                                                   const float* __restrict__ matrices, double* __restrict__ alpha,
+                                                   const uint8_t* __restrict__ keep) {
   __shared__ float mean[CGNN_PARTIAL_MAX_NODES], rstd[CGNN_PARTIAL_MAX_NODES];
   __shared__ double part_b[kLwWaves][kLwFrames], part_o[kLwWaves];
-  __shared__ int kept[kLwWaves];
+  __shared__ int kept[kLwWaves], frames[kLwWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slot = (lane >> 3) & 7;           // the frame of a block whose sum wave_sum8 hands this lane
 
@@ -68,6 +76,17 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
     const int w = (int)(u - s * W);
     const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n;
     const float* __restrict__ R = matrices + u * (int64_t)n * n;
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
+    auto frame = [&](int t) {                 // frame t of the window counts
+      if constexpr (kMask) return t < L && kp[t] != 0;
+      else return t < L;
+    };
+    int lu = 0;                               // kMask: this wave's share of L_u
+    if constexpr (kMask) {
+      for (int t = threadIdx.x; t < L; t += kLwThreads) lu += frame(t);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lu += __shfl_xor(lu, o, 64);
+    }
 
     // ---- stage ----
     int p = 0;
@@ -88,6 +107,8 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
       double sq[kLwFrames];
 #pragma unroll
       for (int i = 0; i < kLwFrames; ++i) sq[i] = 0.0;
+      unsigned kf = 0;                        // kMask: bit i says that frame t0 + 4 i counts: lane i's load, one ballot
+      if constexpr (kMask) kf = (unsigned)__ballot(lane < kLwFrames && frame(t0 + kLwWaves * lane));
       for (int c = lane; c < n; c += 64) {
         const float m = mean[c], r = rstd[c];
         float v[kLwFrames];
@@ -99,11 +120,12 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
 #pragma unroll
         for (int i = 0; i < kLwFrames; ++i) {
           const float z = (v[i] - m) * r;
-          sq[i] += (double)z * (double)z;
+          sq[i] += !kMask || ((kf >> i) & 1) ? (double)z * (double)z : 0.0;
         }
       }
       const double st = wave_sum8(sq, lane);
-      if (t0 + kLwWaves * slot < L) b += st * st;         // (a frame past L holds nothing that counts)
+      if (kMask ? (kf >> slot) & 1 : t0 + kLwWaves * slot < L) b += st * st;      // (a frame past L, or censored, holds
+                                                                                  // nothing that counts)
     }
 
     // ---- triangle ----
@@ -128,6 +150,7 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
     if (lane == 0) {
       part_o[wave] = o;
       kept[wave] = p;
+      frames[wave] = lu;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -138,11 +161,13 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
         os += part_o[k];
         ps += kept[k];
       }
-      const double B = (double)L * bs, O = 2.0 * os, F = (double)ps + O;
+      int lc = L;                             // the unit's frame count: L, or L_u under a mask
+      if constexpr (kMask) lc = frames[0] + frames[1] + frames[2] + frames[3];
+      const double B = (double)lc * bs, O = 2.0 * os, F = (double)ps + O;
       double a = 0.0;
       if (O != 0.0) {                         // (a NaN is not 0)
-        const double q = (B - F) / ((double)L * O);
-        a = q != q ? q : (L == 2 || q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q));
+        const double q = (B - F) / ((double)lc * O);
+        a = q != q ? q : ((kMask ? lc <= 2 : lc == 2) || q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q));
       }
       alpha[u] = a;
     }
@@ -155,11 +180,11 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
 #define CGNN_LW_PER_CU 4
 #endif
 
-}  // namespace
-
-extern "C" int cgnn_ingest_shrinkage(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
-                                     const float* stats, const float* matrices, double* alpha, int64_t alpha_bytes,
-                                     void* stream) {
+// what both entry points check and do; masked: keep [S, T] selects the frames, and stats and matrices come with their
+// byte counts
+int lw_call(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride, const uint8_t* keep,
+            int64_t keep_bytes, bool masked, const float* stats, int64_t stats_bytes, const float* matrices,
+            int64_t matrices_bytes, double* alpha, int64_t alpha_bytes, void* stream) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
   if (cgnn_check_cohort_upto(S, n, CGNN_PARTIAL_MAX_NODES) != CGNN_OK || T < 2) return CGNN_EINVAL;
   if (window != 0 && (window < 2 || window > T || stride < 1)) return CGNN_EINVAL;
@@ -167,14 +192,40 @@ extern "C" int cgnn_ingest_shrinkage(const float* ts, int64_t S, int32_t T, int3
   const int st = window ? stride : T;
   const int64_t W = (T - L) / st + 1;
   const int64_t U = S * W;
-  if (U * n >= kLimit || alpha_bytes < 0) return CGNN_EINVAL;
+  if (U * n >= kLimit || keep_bytes < 0 || stats_bytes < 0 || matrices_bytes < 0 || alpha_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
   const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!ts || !stats || !matrices || !alpha) return CGNN_EINVAL;
+  if (!ts || !stats || !matrices || !alpha || (masked && !keep)) return CGNN_EINVAL;
   if (((bits(ts) | bits(stats) | bits(matrices)) & 3) || (bits(alpha) & 7)) return CGNN_EINVAL;
   CGNN_NEED_BYTES(alpha, alpha_bytes, U * (int64_t)sizeof(double));
-  k_lw<<<cgnn_grid_for(U, CGNN_LW_PER_CU), kLwThreads, 0, cgnn_stream(stream)>>>(ts, U, T, n, (int)W, L, st, stats,
-                                                                                 matrices, alpha);
+  const int grid = cgnn_grid_for(U, CGNN_LW_PER_CU);
+  hipStream_t hs = cgnn_stream(stream);
+  if (masked) {
+    CGNN_NEED_BYTES(keep, keep_bytes, S * (int64_t)T);
+    CGNN_NEED_BYTES(stats, stats_bytes, U * n * 2 * (int64_t)sizeof(float));
+    CGNN_NEED_BYTES(matrices, matrices_bytes, U * n * (int64_t)n * (int64_t)sizeof(float));
+    k_lw<true><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, matrices, alpha, keep);
+  } else {
+    k_lw<false><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, matrices, alpha, nullptr);
+  }
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgnn_ingest_shrinkage(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                                     const float* stats, const float* matrices, double* alpha, int64_t alpha_bytes,
+                                     void* stream) {
+  return lw_call(ts, S, T, n, window, stride, nullptr, 0, false, stats, 0, matrices, 0, alpha, alpha_bytes, stream);
+}
+
+// frame censoring: the same launch over the frames keep [S, T] selects; stats and matrices are what
+// cgnn_ingest_corr_masked left for the same mask
+extern "C" int cgnn_ingest_shrinkage_masked(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window,
+                                            int32_t stride, const uint8_t* keep, int64_t keep_bytes, const float* stats,
+                                            int64_t stats_bytes, const float* matrices, int64_t matrices_bytes,
+                                            double* alpha, int64_t alpha_bytes, void* stream) {
+  return lw_call(ts, S, T, n, window, stride, keep, keep_bytes, true, stats, stats_bytes, matrices, matrices_bytes, alpha,
+                 alpha_bytes, stream);
 }

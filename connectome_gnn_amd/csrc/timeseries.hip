@@ -21,6 +21,11 @@
 //                  register; in a diagonal tile only i <= j is stored (and mirrored), and r[i,i] is written as
 //                  1 (0 for a constant column) -- so the matrix is bit-symmetric by construction.
 //
+// cgnn_ingest_corr_masked is the same with a frame mask keep [S, T]: a unit's frames are its window's
+// kept ones.  The mask is a template argument of both kernels: in k_corr_stats a block's count is its kept frames and the
+// waves' counts go through LDS; in k_corr a censored frame is staged as a zero row (the 32 flags of a step are one ballot,
+// fetched a step ahead).  The unmasked instantiations keep their code.
+//
 // Accumulation is fp32 over the frames in ascending order, no atomics: the same bits on every run and for every
 // grid.  Frames past L and columns past n are zeros in LDS and are never read from memory.  Element offsets
 // into `ts` and `out` are 64-bit.
@@ -32,6 +37,7 @@
 namespace {
 
 using namespace gram;
+static_assert(kKS == 32, "k_corr<., true> keeps the flags of a step in one 32-bit ballot");
 
 constexpr int kStatCols = 64;                 // k_corr_stats: columns per workgroup
 constexpr int kStatThreads = 256;
@@ -47,8 +53,13 @@ __device__ __forceinline__ void merge_moments(int& cnt, double& mean, double& m2
   cnt = tot;
 }
 
+// kMask: `keep` [S, T] selects the frames.  A unit's frames are its window's kept ones: a censored
+// frame's value is loaded beside its flag (no load waits for another) and left out by selection; it is in no count, and
+// the waves' counts go through LDS instead of being derived from L.
+template <bool kMask>
 __global__ __launch_bounds__(kStatThreads) void k_corr_stats(const float* __restrict__ ts, int64_t U, int T, int n,
-                                                             int W, int L, int stride, float* __restrict__ stats) {
+                                                             int W, int L, int stride, float* __restrict__ stats,
+                                                             const uint8_t* __restrict__ keep) {
   __shared__ double part[2][kStatThreads / 64][kStatCols];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int chunks = (n + kStatCols - 1) / kStatCols;
@@ -60,15 +71,29 @@ __global__ __launch_bounds__(kStatThreads) void k_corr_stats(const float* __rest
     const int w = (int)(u - s * W);
     const bool act = col < n;
     const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n + (act ? col : 0);
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
+    auto frame = [&](int t) {                 // frame t of the window counts
+      if constexpr (kMask) return t < L && kp[t] != 0;
+      else return t < L;
+    };
     // this wave's frames are wave, wave + 4, ...: blocks of kStatBlock of them are centred in registers
     // and merged into the running moments, so every frame is read once
+    // kMask: the flags of a block of frames tb, tb + 4, .. are one load, lane i's of frame tb + 4 i, and a ballot (every
+    // lane takes part, so the lanes past n walk column 0 along and write nothing)
+    auto flags = [&](int tb) {
+      if constexpr (kMask) return (unsigned)__ballot(lane < kStatBlock && frame(tb + 4 * lane));
+      else return 0u;
+    };
     int cnt = 0;
     double mean = 0.0, m2 = 0.0;
-    if (act) {
+    if (act || kMask) {
       float v[kStatBlock], nx[kStatBlock];
 #pragma unroll
       for (int i = 0; i < kStatBlock; ++i) nx[i] = wave + 4 * i < L ? x[(int64_t)(wave + 4 * i) * n] : 0.0f;
+      unsigned vk = 0, nk = flags(wave);        // kMask: bit i says that v[i] / nx[i] is a kept frame
       for (int t0 = wave; t0 < L; t0 += 4 * kStatBlock) {
+        vk = nk;
+        nk = flags(t0 + 4 * kStatBlock);
 #pragma unroll
         for (int i = 0; i < kStatBlock; ++i) {          // the next block's loads fly while this one is reduced
           const int t = t0 + 4 * (kStatBlock + i);
@@ -76,28 +101,39 @@ __global__ __launch_bounds__(kStatThreads) void k_corr_stats(const float* __rest
           nx[i] = t < L ? x[(int64_t)t * n] : 0.0f;
         }
         const int left = (L - t0 + 3) / 4;
-        const int cb = left < kStatBlock ? left : kStatBlock;
+        const int cb = kMask ? __builtin_popcount(vk) : (left < kStatBlock ? left : kStatBlock);
         double sum = 0.0;
 #pragma unroll
-        for (int i = 0; i < kStatBlock; ++i) sum += (double)v[i];      // (the padding adds zeros)
-        const double mb = sum / (double)cb;
+        for (int i = 0; i < kStatBlock; ++i)             // (the padding adds zeros; a censored frame is left out)
+          sum += !kMask || ((vk >> i) & 1) ? (double)v[i] : 0.0;
+        const double mb = sum / (double)cb;     // (cb == 0: nothing of this block is merged)
         double m2b = 0.0;
 #pragma unroll
         for (int i = 0; i < kStatBlock; ++i) {
           const double d = (double)v[i] - mb;
-          if (i < cb) m2b += d * d;
+          if (kMask ? (vk >> i) & 1 : i < cb) m2b += d * d;
         }
         merge_moments(cnt, mean, m2, cb, mb, m2b);
       }
     }
     part[0][wave][lane] = mean;
     part[1][wave][lane] = m2;
-    __syncthreads();
-    if (wave == 0 && act) {                    // the four waves' moments, in wave order
-      for (int k = 1; k < kStatThreads / 64; ++k) {
-        const int ck = k < L ? (L - k + 3) / 4 : 0;
-        merge_moments(cnt, mean, m2, ck, part[0][k][lane], part[1][k][lane]);
-      }
+    if constexpr (kMask) {
+      __shared__ int counts[kStatThreads / 64][kStatCols];
+      counts[wave][lane] = cnt;
+      __syncthreads();
+      if (wave == 0 && act)
+        for (int k = 1; k < kStatThreads / 64; ++k)
+          merge_moments(cnt, mean, m2, counts[k][lane], part[0][k][lane], part[1][k][lane]);
+    } else {
+      __syncthreads();
+      if (wave == 0 && act)                    // the four waves' moments, in wave order
+        for (int k = 1; k < kStatThreads / 64; ++k) {
+          const int ck = k < L ? (L - k + 3) / 4 : 0;
+          merge_moments(cnt, mean, m2, ck, part[0][k][lane], part[1][k][lane]);
+        }
+    }
+    if (wave == 0 && act) {
       float* __restrict__ o = stats + (u * n + col) * 2;
       o[0] = (float)mean;
       o[1] = m2 == 0.0 ? 0.0f : (float)(1.0 / sqrt(m2));   // (a NaN stays a NaN)
@@ -112,10 +148,11 @@ struct alignas(16) CorrShared {
   float rstd[2][kTile];
 };
 
-template <bool kVec>
+// kMask: a censored frame of the window is staged as a zero row, whatever it holds
+template <bool kVec, bool kMask>
 __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts, int64_t U, int T, int n, int W, int L,
                                                    int stride, int absolute, const float* __restrict__ stats,
-                                                   float* __restrict__ out) {
+                                                   float* __restrict__ out, const uint8_t* __restrict__ keep) {
   __shared__ CorrShared sh;
   const Thread th;
   const int nt = tiles_of(n);
@@ -126,6 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
     const int64_t u = it.unit, s = u / W;
     const int w = (int)(u - s * W);
     const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n;
+    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
 
     __syncthreads();                          // the previous item's epilogue still reads sh.rstd
     if (th.tid < 2 * kTile) {
@@ -142,6 +180,17 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
     }
     f32x4 pre[2][kSlots], acc[3][3];
     load_panels<kVec>(pre, x, L, n, 0, it, th);
+    // kMask: the 32 flags of a step are one ballot.  Lane l fetches the flag of frame k0 + (l & 31) a step ahead -- when
+    // the step before it is staged, so the load flies under that step's MFMAs -- and the first slot staged of a step
+    // turns the fetched flags into the step's bits.
+    bool flag = false;
+    uint64_t bits = 0;
+    int bits_k0 = -1;
+    auto fetch = [&](int k0) {
+      const int t = k0 + (th.tid & 31);
+      flag = t < L && kp[t] != 0;
+    };
+    if constexpr (kMask) fetch(0);
     __syncthreads();
 
     // centred and scaled; frames past L become zeros
@@ -149,7 +198,16 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
       const f32x4 m = *reinterpret_cast<const f32x4*>(&sh.mean[side][c]);
       const f32x4 r = *reinterpret_cast<const f32x4*>(&sh.rstd[side][c]);
       f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      if (t < L) z = (v - m) * r;
+      bool in = t < L;
+      if constexpr (kMask) {
+        if ((t & ~31) != bits_k0) {           // (uniform: every thread stages the same step)
+          bits_k0 = t & ~31;
+          bits = __ballot(flag);
+          fetch(bits_k0 + kKS);
+        }
+        in = (bits >> (t & 31)) & 1;          // (a frame past L has no flag set)
+      }
+      if (in) z = (v - m) * r;
       return z;
     });
 
@@ -193,9 +251,12 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
 
 }  // namespace
 
-extern "C" int cgnn_ingest_corr(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
-                                int32_t absolute, float* stats, int64_t stats_bytes, float* out, int64_t out_bytes,
-                                void* stream) {
+namespace {
+
+// what both entry points check and do; masked: keep [S, T] selects the frames
+int corr_call(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride, int32_t absolute,
+              const uint8_t* keep, int64_t keep_bytes, bool masked, float* stats, int64_t stats_bytes, float* out,
+              int64_t out_bytes, void* stream) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
   if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2) return CGNN_EINVAL;
   if (window != 0 && (window < 2 || window > T || stride < 1)) return CGNN_EINVAL;
@@ -203,23 +264,51 @@ extern "C" int cgnn_ingest_corr(const float* ts, int64_t S, int32_t T, int32_t n
   const int st = window ? stride : T;
   const int64_t W = (T - L) / st + 1;
   const int64_t U = S * W;
-  if (U * n >= kLimit) return CGNN_EINVAL;
+  if (U * n >= kLimit || keep_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
   if (!ts || !stats || !out || (reinterpret_cast<uintptr_t>(ts) & 3)) return CGNN_EINVAL;
   if ((reinterpret_cast<uintptr_t>(stats) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return CGNN_EINVAL;
+  if (masked && !keep) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(keep, keep_bytes, S * (int64_t)T);
   CGNN_NEED_BYTES(stats, stats_bytes, U * n * 2 * (int64_t)sizeof(float));
   CGNN_NEED_BYTES(out, out_bytes, U * n * (int64_t)n * (int64_t)sizeof(float));
   hipStream_t hs = cgnn_stream(stream);
   const int64_t chunks = (n + kStatCols - 1) / kStatCols;
   const int stat_grid = cgnn_grid_for(U * chunks, CGNN_CORR_STATS_PER_CU);
-  k_corr_stats<<<stat_grid, kStatThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats);
+  if (masked)
+    k_corr_stats<true><<<stat_grid, kStatThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, keep);
+  else
+    k_corr_stats<false><<<stat_grid, kStatThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, nullptr);
   CGNN_CHECK_LAUNCH();
   const int grid = cgnn_grid_for(U * pairs_of(tiles_of(n)), CGNN_CORR_WG_PER_CU);
   const bool vec = n % 4 == 0 && !(reinterpret_cast<uintptr_t>(ts) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15);
-  if (vec)
-    k_corr<true><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out);
-  else
-    k_corr<false><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out);
+  if (masked) {
+    if (vec)
+      k_corr<true, true><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, keep);
+    else
+      k_corr<false, true><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, keep);
+  } else {
+    if (vec)
+      k_corr<true, false><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, nullptr);
+    else
+      k_corr<false, false><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, nullptr);
+  }
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgnn_ingest_corr(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                                int32_t absolute, float* stats, int64_t stats_bytes, float* out, int64_t out_bytes,
+                                void* stream) {
+  return corr_call(ts, S, T, n, window, stride, absolute, nullptr, 0, false, stats, stats_bytes, out, out_bytes, stream);
+}
+
+// frame censoring: the same two launches over the frames keep [S, T] selects
+extern "C" int cgnn_ingest_corr_masked(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                                       int32_t absolute, const uint8_t* keep, int64_t keep_bytes, float* stats,
+                                       int64_t stats_bytes, float* out, int64_t out_bytes, void* stream) {
+  return corr_call(ts, S, T, n, window, stride, absolute, keep, keep_bytes, true, stats, stats_bytes, out, out_bytes,
+                   stream);
 }

@@ -251,6 +251,51 @@ regression in place on the filter's output.  The DCT projector being orthogonal,
 ``[dropped cosines | confounds]`` (Frisch-Waugh-Lovell), which is what nilearn's
 ``signal.clean(confounds=, filter="cosine")`` computes.  Without ``confounds`` the call launches what it always
 launched and gives the same bits.
+
+Frame censoring, or scrubbing: every time-series entry point takes ``sample_mask``, a per-subject frame
+mask -- ``torch.bool`` ``[S, T]``, contiguous, on the time series' device, ``True`` = the frame is kept (what
+``nilearn.interfaces.fmriprep.load_confounds(scrub=...)`` hands to ``signal.clean``).  Frames keep their place in time
+and no shape changes.  A censored frame takes part in no mean, norm, inner product or count, and its stored values are
+never looked at, whatever they are: selection, never multiplication.  Without ``sample_mask`` every call launches what
+it always launched and gives the same bits.  For subject ``s``, ``K`` is the set of kept frames and ``Tk = |K|``.
+
+* Centring: ``m_i`` is the mean of column ``i`` over ``K``, summed in fp64 in a fixed order;
+  ``xc[t, i] = fl32(double(x[t, i]) - m_i)`` for ``t`` in ``K`` and exactly ``0.0`` elsewhere.  ``Tk == 0`` gives
+  ``m_i = 0`` and zeros everywhere.
+* ``confound_basis(confounds, sample_mask=)``: the statement above with every mean, norm ``s_j``, inner product and
+  pivot ``d_j`` taken over ``K``.  Rows of ``Q`` at censored frames are exactly ``0.0``.  The rank rule
+  (``d_j > CONFOUND_RANK_TOL``) is unchanged: once ``Tk - 1`` independent columns are kept it drops the rest, and no
+  separate case handles that.  A non-finite value in a *kept* frame of a subject's confounds makes that subject's ``Q``
+  NaN and its ``rank`` -1, as without a mask; one in a censored frame changes nothing.
+* ``regress_confounds(timeseries, confounds, sample_mask=, out=)``: ``out = xc - Q (Q^T xc)``, products and sums as
+  above.  Censored frames of ``out`` are exactly ``0.0``; on the kept frames this is the fp64 least-squares residual of
+  ``x[K]`` on ``[1 | c[K]]``.
+* ``filter_timeseries(..., sample_mask=)``: the cosines are not orthogonal on ``K``, so the band is removed by
+  regression.  The design is one column ``fl32(b_k[t])`` for each component the band drops -- those
+  ``filter_components`` leaves out, in ascending ``k``, each at the frame's own ``t`` on the grid of the whole run,
+  exactly the value the filter's table holds -- followed by the confound columns if any, and
+  ``out = regress_confounds(timeseries, design, sample_mask=)``: the joint residual on
+  ``[1 | dropped cosines | confounds]`` sampled at the kept frames, which is what
+  ``nilearn.signal.clean(filter="cosine", confounds=, sample_mask=)`` computes on the rows it returns.  Dropped
+  components plus confound columns must not exceed ``CONFOUND_MAX = 64``: otherwise a ``ValueError`` names both counts
+  and says that a ``low_pass`` under censoring would need the frames interpolated, which is not built; a ``low_pass``
+  passes only if it fits that bound.  With no bounds and no confounds the call is masked centring, no product launched.
+* ``correlation_matrices`` / ``ledoit_wolf_shrinkage`` / ``from_timeseries(..., sample_mask=)``: a unit's frames are its
+  window intersected with ``K``, ``L_u`` of them.  ``m_i`` and ``q_i`` run over those frames, as centred fp64 sums;
+  ``z[t, i]`` is as above on them and ``0`` elsewhere; clamp, exact unit diagonal, mirror store, ``absolute`` and
+  ``kind="partial"`` are as without a mask.  A unit with ``L_u < 2`` has ``q_i == 0`` for every ROI: by the
+  constant-column rule an exactly all-zero matrix, hence a graph without edges.  Ledoit-Wolf uses ``L_u`` wherever it
+  uses ``L``: ``B = L_u sum_{t kept} s_t^2``, ``a = (B - F) / (L_u O)``, and ``L_u <= 2`` or ``O == 0`` give exactly 0.
+  The host-side ``ValueError`` for ``shrinkage == 0`` stays on ``L``: kept counts live on the device and are not read
+  back; a unit whose kept frames make it singular is all NaN by the pivot rule.
+
+An all-``True`` mask gives the bits of the unmasked call (``confound_basis``, ``regress_confounds``,
+``correlation_matrices`` of both kinds, ``ledoit_wolf_shrinkage``).  NaN, Inf or ``1e30`` in censored frames of the series
+or the confounds change no bit of any output.  An ROI that is constant over its kept frames is exactly 0, even if it
+varies in censored ones; a NaN in a kept frame of an ROI stays in its column of its subject.  ``out=timeseries`` gives the
+out-of-place bits.  No atomics, no read-back, and every run and every grid gives the same bits.  Interpolating censored
+frames (so that a band-pass can run), deriving the mask from framewise displacement and per-subject run lengths are not
+built.
 """
 from __future__ import annotations
 
@@ -483,6 +528,23 @@ def _check_confounds(confounds, S=None, T=None, device=None) -> tuple:
     return cs, ct, q
 
 
+def _check_sample_mask(sample_mask, S: int, T: int, device):
+    """A valid ``sample_mask=`` for data of ``S`` subjects and ``T`` frames on ``device``: None, or bool ``[S, T]``."""
+    if sample_mask is None:
+        return None
+    if not isinstance(sample_mask, torch.Tensor):
+        raise TypeError(f"sample_mask must be a torch.Tensor or None, got {type(sample_mask).__name__}")
+    if sample_mask.dtype != torch.bool:
+        raise TypeError(f"sample_mask must be bool (True: the frame is kept), got {sample_mask.dtype}")
+    if tuple(sample_mask.shape) != (S, T):
+        raise ValueError(f"sample_mask must be [S, T] = [{S}, {T}], one flag per frame, got {tuple(sample_mask.shape)}")
+    if sample_mask.device != device:
+        raise ValueError(f"sample_mask is on {sample_mask.device}, the data on {device}")
+    if not sample_mask.is_contiguous():
+        raise ValueError("sample_mask must be contiguous")
+    return sample_mask
+
+
 def _require_resident_confounds(confounds: torch.Tensor) -> None:
     if not confounds.is_cuda:
         raise RuntimeError(
@@ -490,31 +552,42 @@ def _require_resident_confounds(confounds: torch.Tensor) -> None:
             "(there is no CPU fallback; move them with .to('cuda')).")
 
 
-def _confound_basis(confounds: torch.Tensor, S: int, T: int, q: int) -> tuple:
+def _confound_basis(confounds: torch.Tensor, S: int, T: int, q: int, keep=None) -> tuple:
     dev = confounds.device
     qpad = (q + 31) // 32 * 32
     basis = torch.empty(S, T, qpad, dtype=torch.float32, device=dev)
     rank = torch.empty(S, dtype=torch.int32, device=dev)
     if S:
+        lib = _lib.load()
         with _lib.device_guard(dev):
-            _lib.check(_lib.load().cgnn_ingest_confound_basis(_lib.ptr(confounds), S, T, q, _lib.ptr(basis),
-                                                              _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank),
-                                                              _lib.stream_ptr(dev)), "cgnn_ingest_confound_basis")
+            if keep is None:
+                _lib.check(lib.cgnn_ingest_confound_basis(_lib.ptr(confounds), S, T, q, _lib.ptr(basis),
+                                                          _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank),
+                                                          _lib.stream_ptr(dev)), "cgnn_ingest_confound_basis")
+            else:
+                _lib.check(lib.cgnn_ingest_confound_basis_masked(
+                    _lib.ptr(confounds), S, T, q, _lib.ptr(keep), _lib.nbytes(keep), _lib.ptr(basis),
+                    _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank), _lib.stream_ptr(dev)),
+                    "cgnn_ingest_confound_basis_masked")
     return basis, rank
 
 
-def confound_basis(confounds: torch.Tensor) -> tuple:
+def confound_basis(confounds: torch.Tensor, *, sample_mask=None) -> tuple:
     """``(basis, rank)`` of the confounds float32 ``[S, T, q]``, ``1 <= q <= CONFOUND_MAX``: per subject the orthonormal
     basis of the centred columns by Gram-Schmidt in the given order (module docstring), float32 ``[S, T, qpad]`` with
     ``qpad`` = ``q`` rounded up to 32 -- a column that is constant or that earlier columns explain is exactly zero, as
     the padding is -- and the number of kept columns, int32 ``[S]``; a subject with a non-finite confound has a NaN
-    basis and rank -1.  One launch on resident data; no temporaries, no read-back."""
+    basis and rank -1.  One launch on resident data; no temporaries, no read-back.  ``sample_mask`` (bool ``[S, T]``,
+    True: kept) takes every mean, norm and pivot over the subject's kept frames; the rows of the basis at censored
+    frames are exactly zero, and a non-finite confound counts only in a kept frame."""
     S, T, q = _check_confounds(confounds)
+    keep = _check_sample_mask(sample_mask, S, T, confounds.device)
     _require_resident_confounds(confounds)
-    return _confound_basis(confounds, S, T, q)
+    return _confound_basis(confounds, S, T, q, keep)
 
 
-def _regress(timeseries: torch.Tensor, S: int, T: int, n: int, basis: torch.Tensor, out: torch.Tensor) -> None:
+def _regress(timeseries: torch.Tensor, S: int, T: int, n: int, basis, out: torch.Tensor, keep=None) -> None:
+    """``basis`` None (with ``keep``): masked centring alone."""
     dev = timeseries.device
     lib = _lib.load()
     with _lib.device_guard(dev):
@@ -522,34 +595,75 @@ def _regress(timeseries: torch.Tensor, S: int, T: int, n: int, basis: torch.Tens
         if need < 0:
             raise _lib.CgnnError(f"cgnn_ingest_regress_workspace_bytes({S}, {T}, {n}) refused its arguments")
         work = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cgnn_ingest_regress(_lib.ptr(timeseries), S, T, n, _lib.ptr(basis), _lib.nbytes(basis),
-                                           int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
-                                           _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress")
+        if keep is None:
+            _lib.check(lib.cgnn_ingest_regress(_lib.ptr(timeseries), S, T, n, _lib.ptr(basis), _lib.nbytes(basis),
+                                               int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
+                                               _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress")
+        else:
+            _lib.check(lib.cgnn_ingest_regress_masked(
+                _lib.ptr(timeseries), S, T, n, _lib.ptr(keep), _lib.nbytes(keep), _lib.ptr(basis), _lib.nbytes(basis),
+                0 if basis is None else int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
+                _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress_masked")
 
 
-def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, out=None) -> torch.Tensor:
+def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, sample_mask=None, out=None) -> torch.Tensor:
     """The time series centred and with the span of the subject's centred confounds projected out of every column:
     ``xc - Q (Q^T xc)`` with ``Q = confound_basis(confounds)`` (module docstring), float32 ``[S, T, n]`` on the time
     series' device.  ``confounds`` is float32 contiguous ``[S, T, q]`` on the same device, ``1 <= q <= CONFOUND_MAX``.
     ``out`` as in ``filter_timeseries``: it may be ``timeseries`` itself, with the same bits as out of place.  Three
-    launches on resident data; the temporaries are the basis ``[S, T, qpad]`` and the means ``[S, n]``.  No read-back."""
+    launches on resident data; the temporaries are the basis ``[S, T, qpad]`` and the means ``[S, n]``.  No read-back.
+    ``sample_mask`` (bool ``[S, T]``, True: kept): the regression runs on the subject's kept frames alone -- the fp64
+    least-squares residual of ``x[K]`` on ``[1 | c[K]]`` -- and the censored frames of the result are exactly ``0.0``."""
     S, T, n = _check_timeseries(timeseries, None, None)[:3]
     if T > _FILTER_MAX_FRAMES:
         raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
     q = _check_confounds(confounds, S, T, timeseries.device)[2]
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _check_out(out, timeseries)
     _require_resident_timeseries(timeseries)
     if out is None:
         out = torch.empty_like(timeseries)
     if S == 0:
         return out
-    basis, _ = _confound_basis(confounds, S, T, q)
-    _regress(timeseries, S, T, n, basis, out)
+    basis, _ = _confound_basis(confounds, S, T, q, keep)
+    _regress(timeseries, S, T, n, basis, out, keep)
+    return out
+
+
+def _filter_censored(timeseries: torch.Tensor, S: int, T: int, n: int, k_lo: int, k_hi: int, confounds, q, keep,
+                     out) -> torch.Tensor:
+    """``filter_timeseries`` under a mask: the band removed by regression on ``[dropped cosines | confounds]`` at the
+    kept frames (module docstring).  The design and its basis are the only temporaries besides the means."""
+    comps = list(range(1, k_lo)) + list(range(k_hi + 1, T))           # what the band drops, ascending
+    K, nq = len(comps), q or 0
+    if K + nq > CONFOUND_MAX:
+        raise ValueError(f"under a sample_mask the band is removed by regression: it drops {K} components, and with "
+                         f"{nq} confound columns that is more than CONFOUND_MAX = {CONFOUND_MAX} regressors (a low_pass "
+                         "under censoring would need the censored frames interpolated, which is not built)")
+    _require_resident_timeseries(timeseries)
+    if out is None:
+        out = torch.empty_like(timeseries)
+    if S == 0:
+        return out
+    if K + nq == 0:                                   # masked centring: no product launched
+        _regress(timeseries, S, T, n, None, out, keep)
+        return out
+    design = confounds
+    if K:
+        dev = timeseries.device
+        design = torch.empty(S, T, K + nq, dtype=torch.float32, device=dev)
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().cgnn_ingest_design(_lib.ptr(confounds), S, T, nq, (ctypes.c_int32 * K)(*comps), K,
+                                                      _lib.ptr(design), _lib.nbytes(design), _lib.stream_ptr(dev)),
+                       "cgnn_ingest_design")
+    basis, _ = _confound_basis(design, S, T, K + nq, keep)
+    del design
+    _regress(timeseries, S, T, n, basis, out, keep)
     return out
 
 
 def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None,
-                      confounds=None) -> torch.Tensor:
+                      confounds=None, sample_mask=None) -> torch.Tensor:
     """The time series centred and band-passed column by column, by projection on the DCT-II components
     ``filter_components(T, t_r, high_pass, low_pass)`` of the whole run: float32 ``[S, T, n]`` on the time series'
     device (module docstring), what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.
@@ -560,7 +674,11 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     ``confounds`` (float32 contiguous ``[S, T, q]`` on the same device, ``1 <= q <= CONFOUND_MAX``) are filtered with
     the same band and regressed out of the result in place, ``regress_confounds(filter(timeseries), filter(confounds))``:
     the joint regression on the dropped cosines and the confounds.  The filtered confounds and their basis
-    ``[S, T, qpad]`` are its only further temporaries.  No read-back."""
+    ``[S, T, qpad]`` are its only further temporaries.  No read-back.  ``sample_mask`` (bool ``[S, T]``, True: kept):
+    the cosines are not orthogonal on a subset of the frames, so the band is removed by regression,
+    ``regress_confounds(timeseries, [dropped cosines | confounds], sample_mask=)``: at most ``CONFOUND_MAX`` regressors
+    in all (a ``ValueError`` beyond, which is what a ``low_pass`` usually meets), the censored frames of the result
+    exactly ``0.0``; the design ``[S, T, K + q]`` and its basis are then the temporaries."""
     S, T, n = _check_timeseries(timeseries, None, None)[:3]
     if T > _FILTER_MAX_FRAMES:
         raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
@@ -568,6 +686,11 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     if k_lo > k_hi:
         raise ValueError(f"the band high_pass={high_pass}, low_pass={low_pass} at t_r={t_r} holds no component of a "
                          f"{T}-frame run (components {k_lo} .. {k_hi}; component k has k / (2 T t_r) Hz)")
+    if sample_mask is not None:
+        keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+        _check_out(out, timeseries)
+        q = None if confounds is None else _check_confounds(confounds, S, T, timeseries.device)[2]
+        return _filter_censored(timeseries, S, T, n, k_lo, k_hi, confounds, q, keep, out)
     kept = k_hi - k_lo + 1
     dropped = T - 1 - kept
     complement = kept > dropped                       # the smaller set is the one that is multiplied
@@ -604,30 +727,44 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     return out
 
 
-def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool) -> tuple:
+def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, keep=None) -> tuple:
     """(the correlations [U, n, n], the statistics [U, n, 2] they were built with)"""
     dev = timeseries.device
     U = S * W
     out = torch.empty(U, n, n, dtype=torch.float32, device=dev)
     stats = torch.empty(U, n, 2, dtype=torch.float32, device=dev)      # (mean, 1 / sqrt(q)) per unit and ROI
+    lib = _lib.load()
     with _lib.device_guard(dev):
-        _lib.check(_lib.load().cgnn_ingest_corr(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
-                                                st if windowed else 0, int(bool(absolute)), _lib.ptr(stats),
-                                                _lib.nbytes(stats), _lib.ptr(out), _lib.nbytes(out),
-                                                _lib.stream_ptr(dev)), "cgnn_ingest_corr")
+        if keep is None:
+            _lib.check(lib.cgnn_ingest_corr(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
+                                            st if windowed else 0, int(bool(absolute)), _lib.ptr(stats),
+                                            _lib.nbytes(stats), _lib.ptr(out), _lib.nbytes(out),
+                                            _lib.stream_ptr(dev)), "cgnn_ingest_corr")
+        else:
+            _lib.check(lib.cgnn_ingest_corr_masked(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
+                                                   st if windowed else 0, int(bool(absolute)), _lib.ptr(keep),
+                                                   _lib.nbytes(keep), _lib.ptr(stats), _lib.nbytes(stats), _lib.ptr(out),
+                                                   _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_corr_masked")
     return out, stats
 
 
 def _estimate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, stats: torch.Tensor,
-              matrices: torch.Tensor) -> torch.Tensor:
+              matrices: torch.Tensor, keep=None) -> torch.Tensor:
     """cgnn_ingest_shrinkage: float64 [U], for the signed correlations and the statistics ``_correlate`` returned."""
     dev = timeseries.device
     alpha = torch.empty(S * W, dtype=torch.float64, device=dev)
+    lib = _lib.load()
     with _lib.device_guard(dev):
-        _lib.check(_lib.load().cgnn_ingest_shrinkage(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
-                                                     st if windowed else 0, _lib.ptr(stats), _lib.ptr(matrices),
-                                                     _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)),
-                   "cgnn_ingest_shrinkage")
+        if keep is None:
+            _lib.check(lib.cgnn_ingest_shrinkage(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
+                                                 st if windowed else 0, _lib.ptr(stats), _lib.ptr(matrices),
+                                                 _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)),
+                       "cgnn_ingest_shrinkage")
+        else:
+            _lib.check(lib.cgnn_ingest_shrinkage_masked(
+                _lib.ptr(timeseries), S, T, n, L if windowed else 0, st if windowed else 0, _lib.ptr(keep),
+                _lib.nbytes(keep), _lib.ptr(stats), _lib.nbytes(stats), _lib.ptr(matrices), _lib.nbytes(matrices),
+                _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)), "cgnn_ingest_shrinkage_masked")
     return alpha
 
 
@@ -715,52 +852,59 @@ def partial_correlation(matrices: torch.Tensor, *, shrinkage=0.0, absolute=False
 
 
 def _connectivity(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, kind: str,
-                  shrinkage) -> torch.Tensor:
+                  shrinkage, keep=None) -> torch.Tensor:
     """The matrices of a valid request: the correlations, or the partial correlations of the signed correlations
     written over them (no second cohort-sized tensor).  A shrinkage named in SHRINKAGES is estimated in between, from
     the frames, the statistics and the signed correlations."""
     if kind == "correlation":
-        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute)[0]
-    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
+        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute, keep)[0]
+    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False, keep)
     if isinstance(shrinkage, str):
-        shrinkage = _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices)
+        shrinkage = _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices, keep)
     del stats
     return _partial(matrices, S * W, n, shrinkage, absolute, matrices)
 
 
-def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None) -> torch.Tensor:
+def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None) -> torch.Tensor:
     """The Ledoit-Wolf shrinkage of every unit's correlation matrix, estimated from the unit's own frames: float64
     ``[U]`` on the time series' device (module docstring); what ``partial_correlation(..., shrinkage=)`` takes.  Three
     launches on resident data (the two of ``correlation_matrices``, then the estimate); the matrices and the statistics
-    are temporaries.  ``n <= PARTIAL_MAX_NODES``.  No read-back."""
+    are temporaries.  ``n <= PARTIAL_MAX_NODES``.  No read-back.  ``sample_mask`` (bool ``[S, T]``, True: kept): a
+    unit's frames are its window's kept ones, ``L_u`` of them, and ``L_u`` stands wherever ``L`` does."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     _check_partial_size(n)
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident_timeseries(timeseries)
     windowed = window is not None
-    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False)
-    return _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices)
+    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False, keep)
+    return _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices, keep)
 
 
 def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
-                         shrinkage=0.0) -> torch.Tensor:
+                         shrinkage=0.0, sample_mask=None) -> torch.Tensor:
     """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
     (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics.
     ``kind="partial"`` gives ``partial_correlation`` of the signed correlations at ``shrinkage``, written in place
     over them by a third launch; ``absolute`` then applies to the partial values.  ``shrinkage`` is a float, a ``[U]``
-    tensor or ``"ledoit_wolf"``: each unit's own estimate (``ledoit_wolf_shrinkage``), a launch between the two."""
+    tensor or ``"ledoit_wolf"``: each unit's own estimate (``ledoit_wolf_shrinkage``), a launch between the two.
+    ``sample_mask`` (bool ``[S, T]``, True: kept): a unit's frames are its window's kept ones; a unit with fewer than
+    two is an all-zero matrix.  The ``n + 2`` frames that ``shrinkage == 0`` asks for are still counted on the window:
+    kept counts stay on the device, and a unit that its kept frames leave singular is all NaN."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     shrinkage = _check_kind(kind, shrinkage, n, L, S * W, timeseries)
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident_timeseries(timeseries)
-    return _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage)
+    return _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage, keep)
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
-                    kind="correlation", shrinkage=0.0) -> RaggedPackedDataset:
+                    kind="correlation", shrinkage=0.0, sample_mask=None) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
-    ``shrinkage`` are ``correlation_matrices``'s.  The one read-back is ``from_matrices``'s."""
+    ``shrinkage`` and ``sample_mask`` are ``correlation_matrices``'s (a unit with fewer than two kept frames is a graph
+    without edges).  The one read-back is ``from_matrices``'s."""
     S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
     U = S * W
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
@@ -772,8 +916,9 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
         if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
                 or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (U, n):
             raise ValueError(f"node_features must be a float32 tensor [U, n, F] = [{U}, {n}, F]")
+    sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident_timeseries(timeseries)
-    matrices = _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage)
+    matrices = _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage, sample_mask)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
                          num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
 

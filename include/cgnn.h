@@ -722,6 +722,65 @@ int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_t n, const 
                         int32_t qpad, void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Frame censoring (scrubbing) of ROI time series: every time-series call above with a per-subject frame
+ * mask.  keep: uint8 [S, T] on the device, nonzero = the frame is kept, keep_bytes >= S T; no alignment is asked of it.
+ * Frames keep their place in time and no shape changes.  A censored frame takes part in no mean, norm, inner product or
+ * count; its stored values are never looked at, whatever they are (selection, never multiplication).  For subject s, K is
+ * the set of its kept frames and Tk = |K|.
+ *   centring   m_i = the mean of column i over K, summed in fp64 in a fixed order; xc[t,i] = fl32(double(x[t,i]) - m_i)
+ *              for t in K and exactly 0.0 elsewhere; Tk == 0 gives m_i = 0 and zeros everywhere.
+ *
+ * cgnn_ingest_confound_basis_masked.  cgnn_ingest_confound_basis's statement with every mean, norm s_j, inner product and
+ * pivot d_j taken over K.  Rows of Q at censored frames are exactly 0.0.  The rank rule is unchanged: once Tk - 1
+ * independent columns are kept it drops the rest.  A non-finite value in a KEPT frame makes the subject's Q NaN (on its
+ * kept frames) and its rank -1; one in a censored frame changes nothing.  With every frame kept the bits are
+ * cgnn_ingest_confound_basis's.  The same launch, buffers and refusals; a NULL or short keep returns CGNN_EINVAL.
+ *
+ * cgnn_ingest_regress_masked.  out = xc - Q (Q^T xc) with xc as above and Q a basis whose rows at censored frames are
+ * zero (cgnn_ingest_confound_basis_masked's, for the same keep): on the kept frames the fp64 least-squares residual of
+ * x[K] on [1 | c[K]], at censored frames exactly 0.0.  qpad == 0 with a NULL basis is masked centring alone, out = xc, and
+ * launches no product; qpad 32 or 64 needs the basis.  The workspace is cgnn_ingest_regress_workspace_bytes(S, T, n).  The
+ * same two launches and refusals as cgnn_ingest_regress; with every frame kept its bits.  out may be ts.
+ *
+ * cgnn_ingest_corr_masked / cgnn_ingest_shrinkage_masked.  A unit's frames are its window intersected with K, L_u of
+ * them.  m_i and q_i run over those frames (centred fp64 sums, as in cgnn_ingest_corr); z[t,i] is cgnn_ingest_corr's on
+ * them and 0 elsewhere; everything after that -- clamp, exact unit diagonal, mirror store, absolute -- is unchanged.  A
+ * unit with L_u < 2 has q_i == 0 for every ROI: an exactly all-zero matrix.  The estimate uses L_u wherever
+ * cgnn_ingest_shrinkage uses L: B = L_u sum_{t kept} s_t^2, a = (B - F) / (L_u O), and L_u <= 2 or O == 0 give exactly 0;
+ * L_u is counted by the kernel.  stats and matrices are what cgnn_ingest_corr_masked left for the same keep, and come with
+ * their byte counts (8 U n and 4 U n n).  With every frame kept the bits are the unmasked calls'.  The same launches and
+ * refusals as the unmasked calls; a NULL or short keep, stats or matrices returns CGNN_EINVAL.
+ *
+ * cgnn_ingest_design.  The design of a band removed by regression (the cosines are not orthogonal on K): float
+ * [S, T, K + q] = [fl32(b_k[t]) for the K components named, ascending in [1, T - 1] | the q confound columns], every
+ * b_k[t] at the frame's own t on the grid of the whole run, the value cgnn_ingest_filter's table holds.  0 <= K, 0 <= q,
+ * 1 <= K + q <= CGNN_CONFOUND_MAX; confounds: float [S, T, q], NULL iff q == 0; comps: a HOST array read before the call
+ * returns.  cgnn_ingest_design_bytes(S, T, K, q) = 4 S T (K + q) is what `design` must hold.  One launch, a thread per
+ * entry.  The band under censoring is then cgnn_ingest_confound_basis_masked of the design and
+ * cgnn_ingest_regress_masked: the joint residual on [1 | dropped cosines | confounds] sampled at the kept frames.
+ *
+ * Every call: a NULL (keep included), misaligned or short buffer and every bad size return CGNN_EINVAL before any launch
+ * (a byte-count query: a negative value); S == 0 returns CGNN_OK with nothing launched.  No atomics, nothing depends on
+ * the grid: the same bits on every run and for every grid.
+ * ------------------------------------------------------------------------------------- */
+int cgnn_ingest_confound_basis_masked(const float* confounds, int64_t S, int32_t T, int32_t q, const uint8_t* keep,
+                                      int64_t keep_bytes, float* basis, int64_t basis_bytes, int32_t* rank,
+                                      int64_t rank_bytes, void* stream);
+int cgnn_ingest_regress_masked(const float* ts, int64_t S, int32_t T, int32_t n, const uint8_t* keep, int64_t keep_bytes,
+                               const float* basis, int64_t basis_bytes, int32_t qpad, void* workspace,
+                               int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream);
+int cgnn_ingest_corr_masked(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                            int32_t absolute, const uint8_t* keep, int64_t keep_bytes, float* stats, int64_t stats_bytes,
+                            float* out, int64_t out_bytes, void* stream);
+int cgnn_ingest_shrinkage_masked(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride,
+                                 const uint8_t* keep, int64_t keep_bytes, const float* stats, int64_t stats_bytes,
+                                 const float* matrices, int64_t matrices_bytes, double* alpha, int64_t alpha_bytes,
+                                 void* stream);
+int64_t cgnn_ingest_design_bytes(int64_t S, int32_t T, int32_t K, int32_t q);
+int cgnn_ingest_design(const float* confounds, int64_t S, int32_t T, int32_t q, const int32_t* comps, int32_t K,
+                       float* design, int64_t design_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
