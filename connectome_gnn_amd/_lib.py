@@ -222,6 +222,8 @@ PROTOTYPES = {
     "cgnn_ingest_shrinkage_masked": (c_int, [P, I64, I32, I32, I32, I32, P, I64, P, I64, P, I64, P, I64, P]),
     "cgnn_ingest_design_bytes": (I64, [I64, I32, I32, I32]),
     "cgnn_ingest_design": (c_int, [P, I64, I32, I32, P, I32, P, I64, P]),
+    "cgnn_ingest_interpolate_workspace_bytes": (I64, [I64, I32, I32]),
+    "cgnn_ingest_interpolate": (c_int, [P, I64, I32, I32, P, I64, P, I64, P, I64, P]),
     "cgnn_gcn_dis": (c_int, [P, P, I64, P, P]),
     "cgnn_fused_grid": (c_int, []),
     "cgnn_set_fused_grid": (c_int, [I32]),

@@ -279,7 +279,8 @@ it always launched and gives the same bits.  For subject ``s``, ``K`` is the set
   ``nilearn.signal.clean(filter="cosine", confounds=, sample_mask=)`` computes on the rows it returns.  Dropped
   components plus confound columns must not exceed ``CONFOUND_MAX = 64``: otherwise a ``ValueError`` names both counts
   and says that a ``low_pass`` under censoring would need the frames interpolated, which is not built; a ``low_pass``
-  passes only if it fits that bound.  With no bounds and no confounds the call is masked centring, no product launched.
+  passes only if it fits that bound.  (That message speaks of this regression path: ``interpolate=True``, below, is the
+  path that interpolates.)  With no bounds and no confounds the call is masked centring, no product launched.
 * ``correlation_matrices`` / ``ledoit_wolf_shrinkage`` / ``from_timeseries(..., sample_mask=)``: a unit's frames are its
   window intersected with ``K``, ``L_u`` of them.  ``m_i`` and ``q_i`` run over those frames, as centred fp64 sums;
   ``z[t, i]`` is as above on them and ``0`` elsewhere; clamp, exact unit diagonal, mirror store, ``absolute`` and
@@ -293,9 +294,50 @@ An all-``True`` mask gives the bits of the unmasked call (``confound_basis``, ``
 ``correlation_matrices`` of both kinds, ``ledoit_wolf_shrinkage``).  NaN, Inf or ``1e30`` in censored frames of the series
 or the confounds change no bit of any output.  An ROI that is constant over its kept frames is exactly 0, even if it
 varies in censored ones; a NaN in a kept frame of an ROI stays in its column of its subject.  ``out=timeseries`` gives the
-out-of-place bits.  No atomics, no read-back, and every run and every grid gives the same bits.  Interpolating censored
-frames (so that a band-pass can run), deriving the mask from framewise displacement and per-subject run lengths are not
-built.
+out-of-place bits.  No atomics, no read-back, and every run and every grid gives the same bits.  Deriving the mask from
+framewise displacement and per-subject run lengths are not built.
+
+Interpolating the censored frames, so that a band-pass can run under a mask:
+``interpolate_censored(timeseries, sample_mask, out=)`` replaces every censored frame by a cubic spline through the
+subject's kept frames, on the device (csrc/interpolate.hip), and gives float32 ``[S, T, n]``; the same call serves
+confounds ``[S, T, q]``.  Per subject and per column ``i``, in fp64 unless it says otherwise: ``t_0 < .. < t_{m-1}`` are the
+kept frame indices (as numbers), ``y_k = double(x[t_k, i])``, ``h_k = t_{k+1} - t_k`` and
+``delta_k = (y_{k+1} - y_k) / h_k``.  ``t_r`` plays no part: the spline through the points does not change when time is
+rescaled.
+
+* Kept frames are bit copies of the input.  Whatever a censored frame holds (NaN, Inf, ``1e30``) is never looked at:
+  selection, never multiplication, as above.
+* ``m == 0``: every frame is exactly ``0.0``.  ``m == 1``: every frame is ``y_0``.
+* Ends: a censored frame before ``t_0`` takes ``x[t_0, i]`` and one after ``t_{m-1}`` takes ``x[t_{m-1}, i]``, both as bit
+  copies.  This departs from ``scipy.interpolate.CubicSpline(extrapolate=True)`` and from nilearn on purpose: a cubic
+  continued over a long censored head grows without bound and would dominate the band-pass, and nilearn's alternative,
+  dropping those frames, does not exist where frames keep their place.
+* Inside ``(t_k, t_{k+1})``: the C2 cubic spline with not-a-knot ends (``CubicSpline``'s default) in Hermite form on the
+  knot derivatives ``s_k``; with ``u = (t - t_k) / h_k``,
+  ``v = (1+2u)(1-u)^2 y_k + u(1-u)^2 h_k s_k + u^2(3-2u) y_{k+1} + u^2(u-1) h_k s_{k+1}``, rounded to fp32 once.
+* Knot derivatives.  ``m == 2``: ``s_0 = s_1 = delta_0`` (the line).  ``m == 3``: ``s_0 + s_1 = 2 delta_0``;
+  ``h_1 s_0 + 2(h_0+h_1) s_1 + h_0 s_2 = 3(h_1 delta_0 + h_0 delta_1)``; ``s_1 + s_2 = 2 delta_1`` (the parabola through the
+  three points, as scipy does).  ``m >= 4``: for ``1 <= k <= m-2``,
+  ``h_k s_{k-1} + 2(h_{k-1}+h_k) s_k + h_{k-1} s_{k+1} = 3(h_k delta_{k-1} + h_{k-1} delta_k)``; first row, with
+  ``d = t_2 - t_0``: ``h_1 s_0 + d s_1 = ((h_0 + 2d) h_1 delta_0 + h_0^2 delta_1) / d``; last row, with
+  ``d = t_{m-1} - t_{m-3}``: ``d s_{m-2} + h_{m-3} s_{m-1} = (h_{m-2}^2 delta_{m-3} + (2d + h_{m-2}) h_{m-3} delta_{m-2}) / d``
+  (scipy's rows).
+
+Arithmetic: the system's matrix depends on the mask alone, so its Thomas factors are formed once per subject in fp64 and
+a column's solve multiplies by them (no division per column); the solve, the Hermite form and the sums are fp64, one
+rounding to fp32 at the store.  Columns never mix: a column constant over its kept frames gives exactly that constant in
+every frame, a non-finite value in a *kept* frame stays in its column of its subject, and an all-``True`` mask gives a bit
+copy.  No atomics, no read-back; every run, every grid and ``out=timeseries`` give the same bits.
+
+``filter_timeseries(..., sample_mask=m, interpolate=True)`` is nilearn's ``signal.clean`` order for scrubbing with a
+band-pass, as this sequence of public calls, bit for bit, ``o`` being the output buffer:
+``o = interpolate_censored(timeseries, m, out=o)``; ``o = filter_timeseries(o, t_r=, high_pass=, low_pass=, out=o)``, the
+orthogonal DCT projection centred over all ``T`` frames; then, with ``confounds=c``,
+``ci = interpolate_censored(c, m)``, ``cf = filter_timeseries(ci, same band, out=ci)`` and
+``o = regress_confounds(o, cf, sample_mask=m, out=o)`` -- the regression on the kept rows alone -- and without confounds
+``o = filter_timeseries(o, t_r=t_r, sample_mask=m, out=o)``, masked centring.  Censored frames of the result are exactly
+``0.0``, as everywhere under a mask.  The checks are the unmasked path's (a non-empty band, the smaller set at most
+``FILTER_MAX_COMPONENTS``); ``interpolate=True`` without a ``sample_mask`` is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -662,8 +704,61 @@ def _filter_censored(timeseries: torch.Tensor, S: int, T: int, n: int, k_lo: int
     return out
 
 
+def _interpolate(timeseries: torch.Tensor, S: int, T: int, n: int, keep: torch.Tensor, out: torch.Tensor) -> None:
+    dev = timeseries.device
+    lib = _lib.load()
+    with _lib.device_guard(dev):
+        need = lib.cgnn_ingest_interpolate_workspace_bytes(S, T, n)
+        if need < 0:
+            raise _lib.CgnnError(f"cgnn_ingest_interpolate_workspace_bytes({S}, {T}, {n}) refused its arguments")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cgnn_ingest_interpolate(_lib.ptr(timeseries), S, T, n, _lib.ptr(keep), _lib.nbytes(keep),
+                                               _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out), _lib.nbytes(out),
+                                               _lib.stream_ptr(dev)), "cgnn_ingest_interpolate")
+
+
+def interpolate_censored(timeseries: torch.Tensor, sample_mask: torch.Tensor, *, out=None) -> torch.Tensor:
+    """The time series with every censored frame replaced by a cubic spline through the subject's kept frames, column by
+    column (module docstring): float32 ``[S, T, n]`` on the time series' device.  ``timeseries`` is float32 contiguous
+    ``[S, T, n]`` on a ROCm device -- confounds ``[S, T, q]`` are served alike -- and ``sample_mask`` bool ``[S, T]``,
+    True: kept.  Kept frames are bit copies; what a censored frame holds is never read; inside the kept range the
+    spline is ``scipy.interpolate.CubicSpline``'s default (C2, not-a-knot), solved and evaluated in fp64 and rounded to
+    fp32 once.  Outside it a censored frame takes the nearest kept value, where ``CubicSpline(extrapolate=True)`` and
+    nilearn continue the cubic: over a long censored head or tail that grows without bound and would dominate a
+    band-pass.  No kept frame gives zeros, one gives its value everywhere.  ``out`` as in ``filter_timeseries``: it may be
+    ``timeseries`` itself, with the same bits as out of place.  Three launches on resident data; the temporary is the
+    workspace of the solve (44 bytes per frame and subject, and a slab that depends on the device alone).  No
+    read-back, no atomics; every run and every grid gives the same bits."""
+    S, T, n = _check_timeseries(timeseries, None, None)[:3]
+    if T > _FILTER_MAX_FRAMES:
+        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+    if sample_mask is None:
+        raise TypeError("sample_mask must be a torch.Tensor, got None: interpolate_censored needs the frames to replace")
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+    _check_out(out, timeseries)
+    _require_resident_timeseries(timeseries)
+    if out is None:
+        out = torch.empty_like(timeseries)
+    if S == 0:
+        return out
+    _interpolate(timeseries, S, T, n, keep, out)
+    return out
+
+
+def _filter_interpolated(timeseries: torch.Tensor, band: dict, confounds, keep, out) -> torch.Tensor:
+    """``filter_timeseries(..., sample_mask=, interpolate=True)``: the sequence of public calls of the module docstring."""
+    _require_resident_timeseries(timeseries)
+    out = interpolate_censored(timeseries, keep, out=out)
+    filter_timeseries(out, out=out, **band)
+    if confounds is None:
+        return filter_timeseries(out, t_r=band["t_r"], sample_mask=keep, out=out)
+    clean = interpolate_censored(confounds, keep)
+    filter_timeseries(clean, out=clean, **band)
+    return regress_confounds(out, clean, sample_mask=keep, out=out)
+
+
 def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None,
-                      confounds=None, sample_mask=None) -> torch.Tensor:
+                      confounds=None, sample_mask=None, interpolate=False) -> torch.Tensor:
     """The time series centred and band-passed column by column, by projection on the DCT-II components
     ``filter_components(T, t_r, high_pass, low_pass)`` of the whole run: float32 ``[S, T, n]`` on the time series'
     device (module docstring), what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.
@@ -678,7 +773,18 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     the cosines are not orthogonal on a subset of the frames, so the band is removed by regression,
     ``regress_confounds(timeseries, [dropped cosines | confounds], sample_mask=)``: at most ``CONFOUND_MAX`` regressors
     in all (a ``ValueError`` beyond, which is what a ``low_pass`` usually meets), the censored frames of the result
-    exactly ``0.0``; the design ``[S, T, K + q]`` and its basis are then the temporaries."""
+    exactly ``0.0``; the design ``[S, T, K + q]`` and its basis are then the temporaries.  ``interpolate=True`` (with a
+    ``sample_mask``; a ``ValueError`` without one) is the way to a band-pass under censoring, in nilearn's order: the
+    censored frames of the series and of the confounds are replaced by ``interpolate_censored``, both are band-passed
+    by the orthogonal projection over all ``T`` frames, and the confounds are regressed on the kept frames alone
+    (without confounds: the kept frames are centred); exactly that sequence of public calls (module docstring), under
+    the checks of the unmasked path, the censored frames of the result exactly ``0.0``.  Its temporaries are the
+    interpolated and filtered confounds and their basis, the filter's table and means, and the interpolation
+    workspace."""
+    if not isinstance(interpolate, bool):
+        raise TypeError(f"interpolate must be a bool, got {type(interpolate).__name__}")
+    if interpolate and sample_mask is None:
+        raise ValueError("interpolate=True replaces the censored frames: give sample_mask= with it")
     S, T, n = _check_timeseries(timeseries, None, None)[:3]
     if T > _FILTER_MAX_FRAMES:
         raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
@@ -686,6 +792,18 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     if k_lo > k_hi:
         raise ValueError(f"the band high_pass={high_pass}, low_pass={low_pass} at t_r={t_r} holds no component of a "
                          f"{T}-frame run (components {k_lo} .. {k_hi}; component k has k / (2 T t_r) Hz)")
+    if interpolate:
+        keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+        kept = k_hi - k_lo + 1
+        dropped = T - 1 - kept
+        if min(kept, dropped) > FILTER_MAX_COMPONENTS:
+            raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
+                             f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
+        _check_out(out, timeseries)
+        if confounds is not None:
+            _check_confounds(confounds, S, T, timeseries.device)
+        band = dict(t_r=t_r, high_pass=high_pass, low_pass=low_pass)
+        return _filter_interpolated(timeseries, band, confounds, keep, out)
     if sample_mask is not None:
         keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
         _check_out(out, timeseries)

@@ -781,6 +781,52 @@ int64_t cgnn_ingest_design_bytes(int64_t S, int32_t T, int32_t K, int32_t q);
 int cgnn_ingest_design(const float* confounds, int64_t S, int32_t T, int32_t q, const int32_t* comps, int32_t K,
                        float* design, int64_t design_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Interpolation of censored frames: every censored frame of ts (float [S, T, n]; confounds [S, T, q]
+ * are served alike) replaced by a cubic spline through the subject's kept frames, so that cgnn_ingest_filter's orthogonal
+ * projection can run under a frame mask.  keep: uint8 [S, T] as in the block above.  Per subject and column i, in fp64
+ * unless it says otherwise: t_0 < .. < t_{m-1} the kept frame indices (as numbers), y_k = double(x[t_k,i]),
+ * h_k = t_{k+1} - t_k, delta_k = (y_{k+1} - y_k) / h_k.  (The sampling period plays no part: the spline through the
+ * points does not change when time is rescaled.)
+ *   kept       frames are bit copies of the input; what a censored frame holds is never looked at (selection)
+ *   m == 0     every frame is exactly 0.0;  m == 1: every frame is y_0
+ *   ends       a censored frame before t_0 takes x[t_0,i], one after t_{m-1} takes x[t_{m-1},i], as bit copies (NOT the
+ *              cubic continued, which scipy's CubicSpline(extrapolate=True) and nilearn give: over a long censored
+ *              head it grows without bound)
+ *   inside     (t_k, t_{k+1}): the C2 cubic spline with not-a-knot ends in Hermite form on the knot derivatives s_k; with
+ *              u = (t - t_k) / h_k,
+ *                v = (1+2u)(1-u)^2 y_k + u(1-u)^2 h_k s_k + u^2(3-2u) y_{k+1} + u^2(u-1) h_k s_{k+1},
+ *              rounded to fp32 once
+ *   s_k        m == 2: s_0 = s_1 = delta_0.   m == 3: s_0 + s_1 = 2 delta_0;
+ *              h_1 s_0 + 2(h_0+h_1) s_1 + h_0 s_2 = 3(h_1 delta_0 + h_0 delta_1);  s_1 + s_2 = 2 delta_1.
+ *              m >= 4: h_k s_{k-1} + 2(h_{k-1}+h_k) s_k + h_{k-1} s_{k+1} = 3(h_k delta_{k-1} + h_{k-1} delta_k) for
+ *              1 <= k <= m-2;  with d = t_2 - t_0:  h_1 s_0 + d s_1 = ((h_0 + 2d) h_1 delta_0 + h_0^2 delta_1) / d;  with
+ *              d = t_{m-1} - t_{m-3}:  d s_{m-2} + h_{m-3} s_{m-1} = (h_{m-2}^2 delta_{m-3} + (2d + h_{m-2}) h_{m-3}
+ *              delta_{m-2}) / d   (scipy's rows)
+ *   arithmetic the Thomas recurrence in fp64; the matrix depends on the mask alone, so its factors are formed once per
+ *              subject and a column multiplies by them: no division per column.  Columns never mix: a column constant
+ *              over its kept frames gives exactly that constant in every frame, a non-finite value in a KEPT frame
+ *              stays in its column of its subject, and with every frame kept the output is a bit copy.
+ *   out        float [S, T, n]; may be `ts` itself (a wave owns all T frames of the columns it writes, reads kept frames
+ *              only and writes censored frames only), with the same bits; any other overlap is not checked
+ *   workspace  cgnn_ingest_interpolate_workspace_bytes(S, T, n) bytes, 16-byte aligned: per (subject, frame) the knot
+ *              index and five fp64 factors (44 bytes), the kept count per subject, and per wave of the launch a slab
+ *              fp64 [ceil(T / 12)][64] of the recurrence at chunk boundaries; the count depends on cgnn_fused_grid() as
+ *              it is when the call is made
+ * Three launches on `stream`: the knots (a wave per subject: the kept frames compacted in order), the factors (a wave
+ * per subject, a sequential fp64 recurrence), and a persistent grid of 3 * cgnn_fused_grid() workgroups of 4 independent
+ * waves over the items (subject, 64 columns), a lane per column: a forward sweep that keeps the recurrence at every 12th
+ * knot only, then the chunks of 12 knots last to first, each formed again in registers from its boundary, substituted
+ * back and its gaps evaluated and stored (two reads of the kept frames).  No atomics, nothing depends on the grid: the
+ * same bits on every run, for every grid, in place and out of place.
+ * T < 2, T > 2^30, S < 0, n <= 0, S * n >= 2^31, S * T > 2^50, a NULL (keep included), misaligned or short buffer return
+ * CGNN_EINVAL before any launch (the byte count: a negative value); S == 0 returns CGNN_OK with nothing launched.  Element
+ * offsets are 64-bit.  No allocation or synchronisation inside.
+ * ------------------------------------------------------------------------------------- */
+int64_t cgnn_ingest_interpolate_workspace_bytes(int64_t S, int32_t T, int32_t n);
+int cgnn_ingest_interpolate(const float* ts, int64_t S, int32_t T, int32_t n, const uint8_t* keep, int64_t keep_bytes,
+                            void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream);
+
 /* GCN degree normalisation, models.py:97-105, every step: dis[i] = (sum of row i of w_src
  * (COO order) + 1 + 1e-8)^-1/2 with w_src the edge weights in src-CSR slot order. */
 int cgnn_gcn_dis(const float* w_src, const int32_t* rowptr_src, int64_t num_nodes, float* dis,
