@@ -32,6 +32,14 @@ static inline int cgnn_device_ordinal() {
 
 static inline int64_t cgnn_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
+// Whether the address of any of `ptrs` has a bit of `low_bits` set: 3 for floats, 15 for 16-byte accesses.  A null
+// pointer is aligned; whether it may be null is the caller's check.
+static inline bool cgnn_misaligned(std::initializer_list<const void*> ptrs, uintptr_t low_bits) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & low_bits) != 0;
+}
+
 // A persistent grid over `items` work items: at most per_cu workgroups per cgnn_fused_grid() (cgnn.h) unit.
 static inline int cgnn_grid_for(int64_t items, int per_cu) {
   const int64_t cap = per_cu * (int64_t)cgnn_fused_grid();

@@ -9,7 +9,7 @@
 //
 // cgnn_ingest_confound_basis_masked is the same with a frame mask keep [S, T]: every mean, norm, inner
 // product and pivot over the subject's kept frames, zero rows of Q at the censored ones.  The mask is a template argument
-// of the kernel and a predicate beside `t < T` in the two norm passes, in the lambda that stages u and in the final write.
+// of the kernel and the predicate of frame_mask.h in the two norm passes, where u is staged and in the final write.
 //
 // The kernel computes that Q by CholeskyQR2: nothing it keeps in LDS depends on T.
 //   k_confound_basis<kQ>  kQ = qpad.  A persistent grid over the subjects, a workgroup of 4 waves per subject, grid
@@ -30,14 +30,15 @@
 // run and for every grid.  Element offsets are 64-bit.
 #include <math.h>
 
+#include "frame_mask.h"
 #include "measure_request.h"
+#include "series_request.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kFB = 32;                       // frames of a block
 constexpr int kLdsBytes = 160 * 1024;
-constexpr int kMaxFrames = 1 << 30;
 
 constexpr int pad_of(int q) { return (q + 31) / 32 * 32; }
 constexpr int q4_of(int q) { return (q + 3) / 4 * 4; }
@@ -119,15 +120,11 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
   for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
     const float* __restrict__ c = conf + s * T * q;
     float* __restrict__ out = basis + s * T * kQ;
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
-    auto kept_at = [&](int t) {               // frame t (< T) counts
-      if constexpr (kMask) return kp[t] != 0;
-      else return true;
-    };
+    const cgnn_frame_mask<kMask> mask(keep, s * T, T);
     double frames = (double)T;                // Tk: what the means divide by
     if constexpr (kMask) {                    // counted by everyone, merged through `part` (an integer sum: exact)
       int cnt = 0;
-      for (int t = tid; t < T; t += kThreads) cnt += kept_at(t);
+      for (int t = tid; t < T; t += kThreads) cnt += mask.kept(t);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
       if ((tid & 63) == 0) part[tid >> 6] = (double)cnt;
@@ -144,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
 #pragma unroll 8
         for (int t = phase; t < T; t += kG) {
           const double v = (double)c[(int64_t)t * q + col] - m;
-          sum += !kept_at(t) ? 0.0 : pass ? v * v : v;
+          sum += !mask.kept(t) ? 0.0 : pass ? v * v : v;
         }
       }
       part[phase * kQ + col] = sum;
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
     for (int j = 0; j < q; ++j) finite = finite && isfinite(sn[j]);
     if (!finite) {                            // never "nothing regressed": the subject's output is NaN
       for (int64_t e = tid; e < (int64_t)T * kQ; e += kThreads)
-        out[e] = kept_at((int)(e / kQ)) ? __builtin_nanf("") : 0.0f;
+        out[e] = mask.censored((int)(e / kQ)) ? 0.0f : __builtin_nanf("");
       if (tid == 0) rank[s] = -1;
       __syncthreads();                        // (the next subject overwrites sn)
       continue;
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
       for (int i = 0; i < kSlots; ++i) {
         const int e = tid + kThreads * i;
         const bool in = e < kFB * q && t0 + e / q < T;
-        pk[i] = in && kept_at(t0 + e / q);
+        pk[i] = in && mask.kept(t0 + e / q);
         pv[i] = in ? c[(int64_t)t0 * q + e] : 0.0f;
       }
     };
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
       for (int e = tid; e < kFB * kQ; e += kThreads) {
         const int f = e / kQ, j = e - f * kQ;
         if (t0 + f < T)
-          out[(int64_t)(t0 + f) * kQ + j] = j < q && kept[j] && kept_at(t0 + f) ? (float)apply(A, f * q4 + j) : 0.0f;
+          out[(int64_t)(t0 + f) * kQ + j] = j < q && kept[j] && mask.kept(t0 + f) ? (float)apply(A, f * q4 + j) : 0.0f;
       }
       __syncthreads();
     }
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void k_confound_basis(const float* __rest
 }
 
 int check(int64_t S, int32_t T, int32_t q) {
-  if (S < 0 || S >= ((int64_t)1 << 31) || T < 2 || T > kMaxFrames) return CGNN_EINVAL;
+  if (S < 0 || S >= ((int64_t)1 << 31) || T < 2 || T > CGNN_MAX_FRAMES) return CGNN_EINVAL;
   return q < 1 || q > CGNN_CONFOUND_MAX ? CGNN_EINVAL : CGNN_OK;
 }
 
@@ -317,8 +314,8 @@ int basis_call(const float* confounds, int64_t S, int32_t T, int32_t q, const ui
                bool masked, float* basis, int64_t basis_bytes, int32_t* rank, int64_t rank_bytes, void* stream) {
   if (check(S, T, q) != CGNN_OK || basis_bytes < 0 || rank_bytes < 0 || keep_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!confounds || !basis || !rank || ((bits(confounds) | bits(rank)) & 3) || (bits(basis) & 15)) return CGNN_EINVAL;
+  if (!confounds || !basis || !rank || cgnn_misaligned({confounds, rank}, 3) || cgnn_misaligned({basis}, 15))
+    return CGNN_EINVAL;
   if (masked && !keep) return CGNN_EINVAL;
   CGNN_NEED_BYTES(keep, keep_bytes, S * T);
   CGNN_NEED_BYTES(basis, basis_bytes, cgnn_ingest_confound_basis_bytes(S, T, q));

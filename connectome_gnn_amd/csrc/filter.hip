@@ -11,11 +11,9 @@
 //
 //   k_filter_basis  the table B [T, Kpad]: an fp64 cospi of the exactly reduced argument ((2 t + 1) k mod 4 T) / (2 T),
 //                   scaled in fp64, rounded to fp32 once.
-//   k_filter_mean   a stream of its own, as k_corr_stats is: a workgroup of 4 waves per (subject, 64 columns), grid
-//                   stride; lane = column (a wave reads 256 consecutive bytes of a frame), wave = frame phase; a
-//                   thread's frames summed in fp64 in ascending order, the four waves' sums in wave order, one
-//                   division.  (The sum of T copies of an fp32 value is exact in fp64, so a constant column's mean is
-//                   the value itself and its xc is exactly 0.)
+//   k_filter_mean   the stream of frame_mask.h, as k_corr_stats is: a thread's frames summed in fp64 in ascending order,
+//                   the four waves' sums in wave order, one division.  (The sum of T copies of an fp32 value is exact
+//                   in fp64, so a constant column's mean is the value itself and its xc is exactly 0.)
 //   k_filter<Kpad, vec>  a persistent grid over the items (subject, 64 columns), grid stride; a workgroup of 4 waves owns
 //                   all T frames of its item, which is what makes out == ts correct: phase 1 has read every frame
 //                   before phase 2 writes the first, and phase 2 reads a chunk again (complement) in the thread that
@@ -37,11 +35,12 @@
 //                   chunk is 16 frames (one block a wave), which is what fits the second workgroup in; at 256 one
 //                   workgroup has the CU to itself and the chunk of B is double-buffered instead.
 //
-// Frame censoring: cgnn_ingest_regress_masked is cgnn_ingest_regress with a frame mask keep [S, T].  The
-// mask enters k_filter_mean and k_filter as one more template argument and as a predicate beside `t < T`: the mean is
-// the kept frames' sum over their count, centre() gives a censored frame a zero row (phase 1, phase 2 and the kPad == 0
-// stream), and phase 2 selects an exact zero for it.  The unmasked instantiations keep their code.  k_design writes the
-// design of a band that is removed by regression, [table values | confounds] per subject, with k_filter_basis's values.
+// Frame censoring: cgnn_ingest_regress_masked is cgnn_ingest_regress with a frame mask keep [S, T], one
+// host body for both (regress_call).  The mask is one more template argument of k_filter_mean and k_filter and the
+// predicate of frame_mask.h: the mean is the kept frames' sum over their count, centre() gives a censored frame a zero
+// row (phase 1, phase 2 and the kPad == 0 stream), and phase 2 selects an exact zero for it.  The unmasked instantiations
+// keep their code.  k_design writes the design of a band that is removed by regression, [table values | confounds] per
+// subject, with k_filter_basis's values.  What the entry points check alike is in series_request.h.
 //
 // Accumulation is fp32 in ascending order of the frame (phase 1) and of the component (phase 2), no atomics, and no work
 // assignment depends on the grid: the same bits on every run and for every grid.  Columns never mix: column j of xc
@@ -49,8 +48,10 @@
 // never stored.  Element offsets into `ts` and `out` are 64-bit.
 #include <math.h>
 
+#include "frame_mask.h"
 #include "gram_tile.h"
 #include "measure_request.h"
+#include "series_request.h"
 
 namespace {
 
@@ -58,14 +59,14 @@ using gram::f32x4;
 using gram::load4;
 
 constexpr int kThreads = 256;
-constexpr int kCols = 64;                     // columns of an item
+constexpr int kCols = kStreamCols;            // columns of an item
 constexpr int kFS = 32;                       // frames per step (phase 1) and per chunk (phase 2)
 constexpr int kLdX = kCols + 16;              // LDS row stride of xc and of C: = 16 (mod 32)
 constexpr int kLdY = kCols + 4;               // of Y: rows of float4
 constexpr int kXSlots = kFS * (kCols / 4) / kThreads;      // float4 slots of a [32, 64] panel per thread
 constexpr int kLdsBytes = 160 * 1024;
-constexpr int kMaxFrames = 1 << 30;           // frame indices a step past T stay inside an int
 static_assert(kXSlots * kThreads == kFS * (kCols / 4), "a panel is a whole number of slots per thread");
+static_assert(kThreads == kStreamThreads, "k_filter_mean runs on the stream of frame_mask.h");
 
 constexpr int pad_of(int K) { return (K + 31) / 32 * 32; }
 
@@ -94,9 +95,7 @@ static_assert(chunk_frames(160) == 32 && !double_chunk(160) && chunk_frames(192)
               "as the comment says");
 static_assert(lds_of(CGNN_FILTER_MAX_COMPONENTS) <= (size_t)kLdsBytes, "the largest Kpad fits the LDS of a CU");
 
-struct Comps {
-  int32_t k[CGNN_FILTER_MAX_COMPONENTS];
-};
+using Comps = cgnn_components;
 
 // b_k[t] of a T-frame run, scale = sqrt(2 / T): the one value function of k_filter_basis and k_design
 __device__ __forceinline__ float basis_value(int64_t t, int k, int T, double scale) {
@@ -129,73 +128,44 @@ __global__ __launch_bounds__(kThreads) void k_design(Comps comps, int K, const f
   }
 }
 
-constexpr int kMeanFrames = 8;                // frames of a block; a thread has the next block's loads in flight
+// The column means, on the stream of frame_mask.h: a thread's frames summed in fp64 in ascending order, the four waves'
+// sums in wave order, one division.  kMask: `keep` [S, T] selects the frames: the sum and the count run
+// over the kept ones, and a subject without a kept frame has mean 0
+struct MeanAcc {
+  double sum = 0.0;                           // of frames wave, wave + 4, ..., in that order
+  int cnt = 0;                                // kMask: this wave's kept frames
+};
 
-// kMask: `keep` [S, T] selects the frames: the sum and the count run over the kept ones -- a censored
-// frame's value is loaded beside its flag (no load waits for another) and then left out by selection -- and a subject
-// without a kept frame has mean 0
 template <bool kMask>
 __global__ __launch_bounds__(kThreads) void k_filter_mean(const float* __restrict__ ts, int64_t S, int T, int n,
                                                           double* __restrict__ mean, const uint8_t* __restrict__ keep) {
-  __shared__ double part[kThreads / 64][kCols];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int chunks = (n + kCols - 1) / kCols;
-  const int64_t items = S * chunks;
-  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-    const int64_t s = item / chunks;
-    const int col = (int)(item - s * chunks) * kCols + lane;
-    const bool act = col < n;
-    const float* __restrict__ x = ts + s * T * n + (act ? col : 0);
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
-    auto frame = [&](int t) {                 // is frame t one that counts
-      if constexpr (kMask) return t < T && kp[t] != 0;
-      else return t < T;
-    };
-    // kMask: the flags of a block of frames tb, tb + 4, .. are one load, lane i's of frame tb + 4 i, and a ballot (every
-    // lane takes part, so the lanes past n walk column 0 along and write nothing)
-    auto flags = [&](int tb) {
-      if constexpr (kMask) return (unsigned)__ballot(lane < kMeanFrames && frame(tb + 4 * lane));
-      else return 0u;
-    };
-    double sum = 0.0;                         // of frames wave, wave + 4, ..., in that order
-    int cnt = 0;                              // kMask: this wave's kept frames
-    if (act || kMask) {
-      float v[kMeanFrames], nx[kMeanFrames];
-      unsigned vk = 0, nk = flags(wave);      // kMask: bit i says that v[i] / nx[i] is a kept frame
+  __shared__ double part[kStreamWaves][kCols];
+  cgnn_stream_columns<kMask, MeanAcc>(
+      ts, keep, S, T, n, 1, T, 0,
+      [](MeanAcc& a, const float (&v)[kStreamBlock], unsigned bits, int) {
+        if constexpr (kMask) a.cnt += __builtin_popcount(bits);
 #pragma unroll
-      for (int i = 0; i < kMeanFrames; ++i) nx[i] = wave + 4 * i < T ? x[(int64_t)(wave + 4 * i) * n] : 0.0f;
-      for (int t0 = wave; t0 < T; t0 += 4 * kMeanFrames) {
-        vk = nk;
-        nk = flags(t0 + 4 * kMeanFrames);
-#pragma unroll
-        for (int i = 0; i < kMeanFrames; ++i) {         // the next block's loads fly while this one is summed
-          const int t = t0 + 4 * (kMeanFrames + i);
-          v[i] = nx[i];
-          nx[i] = t < T ? x[(int64_t)t * n] : 0.0f;
+        for (int i = 0; i < kStreamBlock; ++i)          // (the padding adds zeros; a censored frame is left out)
+          a.sum += !kMask || ((bits >> i) & 1) ? (double)v[i] : 0.0;
+      },
+      [&](const MeanAcc& a, int64_t s, int col, bool act, int lane, int wave) {
+        part[wave][lane] = a.sum;
+        if constexpr (kMask) {
+          __shared__ int kept[kStreamWaves][kCols];
+          kept[wave][lane] = a.cnt;
+          __syncthreads();
+          if (wave == 0 && act) {
+            const int tk = kept[0][lane] + kept[1][lane] + kept[2][lane] + kept[3][lane];
+            const double total = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+            mean[s * n + col] = tk ? total / (double)tk : 0.0;
+          }
+        } else {
+          __syncthreads();
+          if (wave == 0 && act)
+            mean[s * n + col] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (double)T;
         }
-        if constexpr (kMask) cnt += __builtin_popcount(vk);
-#pragma unroll
-        for (int i = 0; i < kMeanFrames; ++i)           // (the padding adds zeros; a censored frame is left out)
-          sum += !kMask || ((vk >> i) & 1) ? (double)v[i] : 0.0;
-      }
-    }
-    part[wave][lane] = sum;
-    if constexpr (kMask) {
-      __shared__ int kept[kThreads / 64][kCols];
-      kept[wave][lane] = cnt;
-      __syncthreads();
-      if (wave == 0 && act) {
-        const int tk = kept[0][lane] + kept[1][lane] + kept[2][lane] + kept[3][lane];
-        const double total = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
-        mean[s * n + col] = tk ? total / (double)tk : 0.0;
-      }
-    } else {
-      __syncthreads();
-      if (wave == 0 && act)
-        mean[s * n + col] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (double)T;
-    }
-    __syncthreads();
-  }
+        __syncthreads();
+      });
 }
 
 // 4 loaded entries of frame t, columns c .. c + 3 of the item -> xc; frames past T and columns past n give zeros
@@ -260,11 +230,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
     const float* x = ts + s * T * n;
     float* o = out + s * T * n;
     const float* __restrict__ table = tables + s * table_stride;
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T : nullptr;
-    auto kept_at = [&](int t) {               // kMask: frame t is inside the run and kept
-      if constexpr (kMask) return t < T && kp[t] != 0;
-      else return true;
-    };
+    const cgnn_frame_mask<kMask> mask(keep, s * T, T);
 
     __syncthreads();                          // the previous item's last chunk still reads mu and Y
     if (tid < kCols) mu[tid] = col0 + tid < n ? mean[s * n + col0 + tid] : 0.0;
@@ -274,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
     auto load_x = [&](int t0) {               // which a ballot turns into the step's 32 flags where they are used
 #pragma unroll
       for (int q = 0; q < kXSlots; ++q) px[q] = load4<kVec>(x, t0 + xrow[q], T, col0 + xcol[q], n);
-      if constexpr (kMask) fl = kept_at(t0 + (tid & 31));
+      if constexpr (kMask) fl = mask.kept(t0 + (tid & 31));
     };
     auto kept_rows = [&](bool f) {            // (every thread of the workgroup is here)
       if constexpr (kMask) return (uint32_t)__ballot(f);
@@ -408,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
 #pragma unroll
           for (int q = 0; q < kX2Slots; ++q) px2[q] = load4<kVec>(x, t0 + xrow[q], T, col0 + xcol[q], n);
         }
-        const bool fl2 = kept_at(t0 + (tid & 31));
+        const bool fl2 = mask.kept(t0 + (tid & 31));
         const float* __restrict__ pa = bc + (kDouble ? cur : 0) * chunk_floats(kPad) + fcol * kLd2 + frow;
         const float* __restrict__ pc = cl + frow * kLdX + wave * 16 + fcol;
         f32x4 y[kFB];
@@ -451,7 +417,7 @@ __global__ __launch_bounds__(kThreads) void k_filter(const float* ts, int64_t S,
 #endif
 
 int check(int64_t S, int32_t T, int32_t n, int32_t K) {
-  if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2 || T > kMaxFrames) return CGNN_EINVAL;
+  if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2 || T > CGNN_MAX_FRAMES) return CGNN_EINVAL;
   return K < 0 || K > CGNN_FILTER_MAX_COMPONENTS ? CGNN_EINVAL : CGNN_OK;
 }
 
@@ -508,21 +474,14 @@ extern "C" int64_t cgnn_ingest_filter_workspace_bytes(int64_t S, int32_t T, int3
 extern "C" int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t n, const int32_t* comps, int32_t K,
                                   int32_t complement, void* workspace, int64_t workspace_bytes, float* out,
                                   int64_t out_bytes, void* stream) {
-  if (check(S, T, n, K) != CGNN_OK || (K > 0 && !comps)) return CGNN_EINVAL;
-  if (K == 0 && !complement) return CGNN_EINVAL;              // (nothing kept: the band is empty)
   Comps list;
-  for (int i = 0; i < K; ++i) {
-    if (comps[i] < 1 || comps[i] > T - 1 || (i > 0 && comps[i] <= comps[i - 1])) return CGNN_EINVAL;
-    list.k[i] = comps[i];
-  }
-  for (int i = K; i < CGNN_FILTER_MAX_COMPONENTS; ++i) list.k[i] = 0;
+  if (check(S, T, n, K) != CGNN_OK || cgnn_check_components(comps, K, T, &list) != CGNN_OK) return CGNN_EINVAL;
+  if (K == 0 && !complement) return CGNN_EINVAL;              // (nothing kept: the band is empty)
   if (workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!ts || !out || !workspace || ((bits(ts) | bits(out)) & 3) || (bits(workspace) & 15)) return CGNN_EINVAL;
+  if (!ts || !out || !workspace || cgnn_misaligned({ts, out}, 3) || cgnn_misaligned({workspace}, 15)) return CGNN_EINVAL;
   CGNN_NEED_BYTES(workspace, workspace_bytes, table_bytes(T, K) + S * n * (int64_t)sizeof(double));
-  // out [S T][n] (S * n < 2^31 and T < 2^31: the byte count is compared by division)
-  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
+  if (!cgnn_holds_floats(out_bytes, S * n, T)) return CGNN_EINVAL;      // out [S T][n]
 
   hipStream_t hs = cgnn_stream(stream);
   const int kpad = pad_of(K);
@@ -536,7 +495,7 @@ extern "C" int cgnn_ingest_filter(const float* ts, int64_t S, int32_t T, int32_t
   const int64_t items = S * ((n + kCols - 1) / kCols);
   k_filter_mean<false><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, nullptr);
   CGNN_CHECK_LAUNCH();
-  const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
+  const bool vec = n % 4 == 0 && !cgnn_misaligned({ts, out}, 15);
   return vec ? launch<true>(kpad, ts, S, T, n, complement, table, 0, mean, out, hs)
              : launch<false>(kpad, ts, S, T, n, complement, table, 0, mean, out, hs);
 }
@@ -548,67 +507,64 @@ extern "C" int64_t cgnn_ingest_regress_workspace_bytes(int64_t S, int32_t T, int
   return S * n * (int64_t)sizeof(double);
 }
 
-extern "C" int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_t n, const float* basis,
-                                   int64_t basis_bytes, int32_t qpad, void* workspace, int64_t workspace_bytes,
-                                   float* out, int64_t out_bytes, void* stream) {
-  if (check(S, T, n, 0) != CGNN_OK || (qpad != 32 && qpad != 64)) return CGNN_EINVAL;
-  if (basis_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
+namespace {
+
+// what both entry points check and do; masked (frame censoring): keep [S, T] selects the frames of the
+// same two launches, and qpad == 0 with a null basis is masked centring alone
+int regress_call(const float* ts, int64_t S, int32_t T, int32_t n, const uint8_t* keep, int64_t keep_bytes, bool masked,
+                 const float* basis, int64_t basis_bytes, int32_t qpad, void* workspace, int64_t workspace_bytes,
+                 float* out, int64_t out_bytes, void* stream) {
+  if (check(S, T, n, 0) != CGNN_OK || (qpad != 32 && qpad != 64 && !(masked && qpad == 0))) return CGNN_EINVAL;
+  if (keep_bytes < 0 || basis_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!ts || !out || !basis || !workspace || ((bits(ts) | bits(out)) & 3) || ((bits(basis) | bits(workspace)) & 15))
-    return CGNN_EINVAL;
+  if (!ts || !out || !workspace || (masked && !keep) || (qpad == 0) != (basis == nullptr)) return CGNN_EINVAL;
+  if (cgnn_misaligned({ts, out}, 3) || cgnn_misaligned({basis, workspace}, 15)) return CGNN_EINVAL;
+  CGNN_NEED_BYTES(keep, keep_bytes, S * T);
   CGNN_NEED_BYTES(workspace, workspace_bytes, S * n * (int64_t)sizeof(double));
-  // basis [S][T, qpad] and out [S T][n]: the byte counts are compared by division
-  if (basis_bytes / (int64_t)sizeof(float) / qpad / T < S) return CGNN_EINVAL;
-  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
+  // basis [S T][qpad] and out [S T][n]
+  if (qpad && !cgnn_holds_floats(basis_bytes, S * T, qpad)) return CGNN_EINVAL;
+  if (!cgnn_holds_floats(out_bytes, S * n, T)) return CGNN_EINVAL;
 
   hipStream_t hs = cgnn_stream(stream);
   double* mean = static_cast<double*>(workspace);
-  const int64_t items = S * ((n + kCols - 1) / kCols);
-  k_filter_mean<false><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, nullptr);
+  const int grid = cgnn_grid_for(S * ((n + kCols - 1) / kCols), CGNN_FILTER_MEAN_PER_CU);
+  if (masked)
+    k_filter_mean<true><<<grid, kThreads, 0, hs>>>(ts, S, T, n, mean, keep);
+  else
+    k_filter_mean<false><<<grid, kThreads, 0, hs>>>(ts, S, T, n, mean, nullptr);
   CGNN_CHECK_LAUNCH();
-  const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
+  const bool vec = n % 4 == 0 && !cgnn_misaligned({ts, out}, 15);
+  if (masked)
+    return vec ? launch_masked<true>(qpad, ts, S, T, n, basis, mean, out, hs, keep)
+               : launch_masked<false>(qpad, ts, S, T, n, basis, mean, out, hs, keep);
   const int64_t stride = (int64_t)T * qpad;
   return vec ? launch<true>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs)
              : launch<false>(qpad, ts, S, T, n, 1, basis, stride, mean, out, hs);
 }
 
-// ---- frame censoring: the same two launches with the frames selected by keep [S, T] ----
+int check_design(int64_t S, int32_t T, int32_t K, int32_t q) {
+  if (S < 0 || S >= ((int64_t)1 << 31) || T < 2 || T > CGNN_MAX_FRAMES) return CGNN_EINVAL;
+  return K < 0 || q < 0 || K + q < 1 || K + q > CGNN_CONFOUND_MAX ? CGNN_EINVAL : CGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgnn_ingest_regress(const float* ts, int64_t S, int32_t T, int32_t n, const float* basis,
+                                   int64_t basis_bytes, int32_t qpad, void* workspace, int64_t workspace_bytes,
+                                   float* out, int64_t out_bytes, void* stream) {
+  return regress_call(ts, S, T, n, nullptr, 0, false, basis, basis_bytes, qpad, workspace, workspace_bytes, out,
+                      out_bytes, stream);
+}
 
 extern "C" int cgnn_ingest_regress_masked(const float* ts, int64_t S, int32_t T, int32_t n, const uint8_t* keep,
                                           int64_t keep_bytes, const float* basis, int64_t basis_bytes, int32_t qpad,
                                           void* workspace, int64_t workspace_bytes, float* out, int64_t out_bytes,
                                           void* stream) {
-  if (check(S, T, n, 0) != CGNN_OK || (qpad != 0 && qpad != 32 && qpad != 64)) return CGNN_EINVAL;
-  if (keep_bytes < 0 || basis_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
-  if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!ts || !keep || !out || !workspace || ((bits(ts) | bits(out)) & 3) || ((bits(basis) | bits(workspace)) & 15))
-    return CGNN_EINVAL;
-  if ((qpad == 0) != (basis == nullptr)) return CGNN_EINVAL;  // masked centring has no basis, a regression has one
-  CGNN_NEED_BYTES(keep, keep_bytes, S * T);
-  CGNN_NEED_BYTES(workspace, workspace_bytes, S * n * (int64_t)sizeof(double));
-  if (qpad && basis_bytes / (int64_t)sizeof(float) / qpad / T < S) return CGNN_EINVAL;
-  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
-
-  hipStream_t hs = cgnn_stream(stream);
-  double* mean = static_cast<double*>(workspace);
-  const int64_t items = S * ((n + kCols - 1) / kCols);
-  k_filter_mean<true><<<cgnn_grid_for(items, CGNN_FILTER_MEAN_PER_CU), kThreads, 0, hs>>>(ts, S, T, n, mean, keep);
-  CGNN_CHECK_LAUNCH();
-  const bool vec = n % 4 == 0 && !((bits(ts) | bits(out)) & 15);
-  return vec ? launch_masked<true>(qpad, ts, S, T, n, basis, mean, out, hs, keep)
-             : launch_masked<false>(qpad, ts, S, T, n, basis, mean, out, hs, keep);
+  return regress_call(ts, S, T, n, keep, keep_bytes, true, basis, basis_bytes, qpad, workspace, workspace_bytes, out,
+                      out_bytes, stream);
 }
 
 // ---- the design of a regression under censoring: [table values | confounds] per subject ----
-
-namespace {
-int check_design(int64_t S, int32_t T, int32_t K, int32_t q) {
-  if (S < 0 || S >= ((int64_t)1 << 31) || T < 2 || T > kMaxFrames) return CGNN_EINVAL;
-  return K < 0 || q < 0 || K + q < 1 || K + q > CGNN_CONFOUND_MAX ? CGNN_EINVAL : CGNN_OK;
-}
-}  // namespace
 
 extern "C" int64_t cgnn_ingest_design_bytes(int64_t S, int32_t T, int32_t K, int32_t q) {
   if (check_design(S, T, K, q) != CGNN_OK) return CGNN_EINVAL;
@@ -617,17 +573,11 @@ extern "C" int64_t cgnn_ingest_design_bytes(int64_t S, int32_t T, int32_t K, int
 
 extern "C" int cgnn_ingest_design(const float* confounds, int64_t S, int32_t T, int32_t q, const int32_t* comps,
                                   int32_t K, float* design, int64_t design_bytes, void* stream) {
-  if (check_design(S, T, K, q) != CGNN_OK || (K > 0 && !comps) || design_bytes < 0) return CGNN_EINVAL;
   Comps list;
-  for (int i = 0; i < K; ++i) {
-    if (comps[i] < 1 || comps[i] > T - 1 || (i > 0 && comps[i] <= comps[i - 1])) return CGNN_EINVAL;
-    list.k[i] = comps[i];
-  }
-  for (int i = K; i < CGNN_FILTER_MAX_COMPONENTS; ++i) list.k[i] = 0;
-  if ((q == 0) != (confounds == nullptr)) return CGNN_EINVAL;
+  if (check_design(S, T, K, q) != CGNN_OK || design_bytes < 0) return CGNN_EINVAL;
+  if (cgnn_check_components(comps, K, T, &list) != CGNN_OK || (q == 0) != (confounds == nullptr)) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!design || ((bits(confounds) | bits(design)) & 3)) return CGNN_EINVAL;
+  if (!design || cgnn_misaligned({confounds, design}, 3)) return CGNN_EINVAL;
   CGNN_NEED_BYTES(design, design_bytes, cgnn_ingest_design_bytes(S, T, K, q));
   const int64_t blocks = (S * T * (K + q) + kThreads - 1) / kThreads;
   k_design<<<cgnn_grid_for(blocks, 8), kThreads, 0, cgnn_stream(stream)>>>(list, K, confounds, S, T, q, design);

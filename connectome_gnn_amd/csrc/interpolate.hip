@@ -40,7 +40,7 @@
 // only.  No atomics, no work assignment depends on the grid, and which buffer `out` is changes no arithmetic: the same
 // bits on every run, for every grid, in place and out of place.  Columns never mix (a lane is a column); a censored
 // frame's stored value is never loaded.  Element offsets into `ts` and `out` are 64-bit.
-#include "common.h"
+#include "series_request.h"
 
 #pragma clang fp contract(off)                // every fused multiply-add below is written as one
 
@@ -62,7 +62,6 @@ constexpr int kC = CGNN_INTERP_CHUNK;
 constexpr int kY = kC + 3;                    // rows of x a chunk needs: knots k0 - 2 .. k0 + kC
 constexpr int kPerCu = CGNN_INTERP_PER_CU;
 constexpr int kPrepPerCu = 16;                // single-wave workgroups of the two per-subject kernels
-constexpr int kMaxFrames = 1 << 30;
 constexpr int64_t kMaxKnots = (int64_t)1 << 50;               // S T: the byte counts below stay inside an int64
 static_assert(kY <= kWave && kC >= 2, "a chunk's knots are one load of a wave; row 0 looks two knots ahead");
 
@@ -349,7 +348,7 @@ __global__ __launch_bounds__(kThreads) void k_interp(const float* ts, int64_t S,
 }
 
 int check(int64_t S, int32_t T, int32_t n) {
-  if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2 || T > kMaxFrames) return CGNN_EINVAL;
+  if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2 || T > CGNN_MAX_FRAMES) return CGNN_EINVAL;
   return S * (int64_t)T > kMaxKnots ? CGNN_EINVAL : CGNN_OK;
 }
 
@@ -366,13 +365,12 @@ extern "C" int cgnn_ingest_interpolate(const float* ts, int64_t S, int32_t T, in
   if (check(S, T, n) != CGNN_OK) return CGNN_EINVAL;
   if (keep_bytes < 0 || workspace_bytes < 0 || out_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!ts || !keep || !out || !workspace || ((bits(ts) | bits(out)) & 3) || (bits(workspace) & 15)) return CGNN_EINVAL;
+  if (!ts || !keep || !out || !workspace || cgnn_misaligned({ts, out}, 3) || cgnn_misaligned({workspace}, 15))
+    return CGNN_EINVAL;
   const Layout w = layout(S, T);
   CGNN_NEED_BYTES(keep, keep_bytes, S * T);
   CGNN_NEED_BYTES(workspace, workspace_bytes, w.total);
-  // out [S T][n] (S * n < 2^31 and T < 2^31: the byte count is compared by division)
-  if (out_bytes / (int64_t)sizeof(float) / T < S * n) return CGNN_EINVAL;
+  if (!cgnn_holds_floats(out_bytes, S * n, T)) return CGNN_EINVAL;      // out [S T][n]
 
   hipStream_t hs = cgnn_stream(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);

@@ -47,8 +47,7 @@ inline int cgnn_check_cohort_upto(int64_t S, int32_t n, int32_t max_n) {
 // product times 4 could wrap 64 bits, so the byte count is compared by division.
 inline int cgnn_check_cohort_buffers(const void* matrices, const void* thr, const void* workspace, const void* x,
                                      int64_t x_bytes, bool want_x, int64_t rows, int32_t ldx) {
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (!matrices || !thr || ((bits(matrices) | bits(thr) | bits(x)) & 3) || (bits(workspace) & 15)) return CGNN_EINVAL;
+  if (!matrices || !thr || cgnn_misaligned({matrices, thr, x}, 3) || cgnn_misaligned({workspace}, 15)) return CGNN_EINVAL;
   if (want_x && (!x || x_bytes < 0 || x_bytes / (int64_t)sizeof(float) / ldx < rows)) return CGNN_EINVAL;
   return CGNN_OK;
 }

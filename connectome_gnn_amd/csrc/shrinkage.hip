@@ -25,13 +25,15 @@
 //              forms the quotient in fp64.
 // cgnn_ingest_shrinkage_masked: with a frame mask keep [S, T] a unit's frames are its window's kept
 // ones; the kernel counts them (L_u) and L_u stands wherever L does: B = L_u sum_{t kept} s_t^2, a = (B - F) / (L_u O),
-// and L_u <= 2 gives 0.  The mask is a template argument and a predicate beside `t < L`.
+// and L_u <= 2 gives 0.  The mask is a template argument and the predicate of frame_mask.h.
 // No atomics, and no work assignment depends on the grid: the same bits on every run and for every grid.  Overlapping
 // windows read their frames again (each window has statistics of its own).  Element offsets into `ts` and `matrices`
 // are 64-bit.
 #include <math.h>
 
+#include "frame_mask.h"
 #include "measure_request.h"
+#include "series_request.h"
 
 namespace {
 
@@ -72,18 +74,13 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
   const int slot = (lane >> 3) & 7;           // the frame of a block whose sum wave_sum8 hands this lane
 
   for (int64_t u = blockIdx.x; u < U; u += gridDim.x) {
-    const int64_t s = u / W;
-    const int w = (int)(u - s * W);
-    const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n;
+    const int64_t first = cgnn_first_frame(u, W, T, stride);
+    const float* __restrict__ x = ts + first * n;
     const float* __restrict__ R = matrices + u * (int64_t)n * n;
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
-    auto frame = [&](int t) {                 // frame t of the window counts
-      if constexpr (kMask) return t < L && kp[t] != 0;
-      else return t < L;
-    };
+    const cgnn_frame_mask<kMask> mask(keep, first, L);
     int lu = 0;                               // kMask: this wave's share of L_u
     if constexpr (kMask) {
-      for (int t = threadIdx.x; t < L; t += kLwThreads) lu += frame(t);
+      for (int t = threadIdx.x; t < L; t += kLwThreads) lu += mask.kept(t);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) lu += __shfl_xor(lu, o, 64);
     }
@@ -107,8 +104,7 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
       double sq[kLwFrames];
 #pragma unroll
       for (int i = 0; i < kLwFrames; ++i) sq[i] = 0.0;
-      unsigned kf = 0;                        // kMask: bit i says that frame t0 + 4 i counts: lane i's load, one ballot
-      if constexpr (kMask) kf = (unsigned)__ballot(lane < kLwFrames && frame(t0 + kLwWaves * lane));
+      const unsigned kf = mask.block(t0, kLwWaves, kLwFrames, lane);       // kMask: bit i says that frame t0 + 4 i counts
       for (int c = lane; c < n; c += 64) {
         const float m = mean[c], r = rstd[c];
         float v[kLwFrames];
@@ -124,8 +120,8 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
         }
       }
       const double st = wave_sum8(sq, lane);
-      if (kMask ? (kf >> slot) & 1 : t0 + kLwWaves * slot < L) b += st * st;      // (a frame past L, or censored, holds
-                                                                                  // nothing that counts)
+      if (kMask ? (kf >> slot) & 1 : mask.kept(t0 + kLwWaves * slot)) b += st * st;        // (a frame past L, or censored,
+                                                                                         // holds nothing that counts)
     }
 
     // ---- triangle ----
@@ -185,18 +181,14 @@ __global__ __launch_bounds__(kLwThreads) void k_lw(const float* __restrict__ ts,
 int lw_call(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride, const uint8_t* keep,
             int64_t keep_bytes, bool masked, const float* stats, int64_t stats_bytes, const float* matrices,
             int64_t matrices_bytes, double* alpha, int64_t alpha_bytes, void* stream) {
-  constexpr int64_t kLimit = (int64_t)1 << 31;
-  if (cgnn_check_cohort_upto(S, n, CGNN_PARTIAL_MAX_NODES) != CGNN_OK || T < 2) return CGNN_EINVAL;
-  if (window != 0 && (window < 2 || window > T || stride < 1)) return CGNN_EINVAL;
-  const int L = window ? window : T;
-  const int st = window ? stride : T;
-  const int64_t W = (T - L) / st + 1;
-  const int64_t U = S * W;
-  if (U * n >= kLimit || keep_bytes < 0 || stats_bytes < 0 || matrices_bytes < 0 || alpha_bytes < 0) return CGNN_EINVAL;
+  cgnn_units un;
+  if (cgnn_check_cohort_upto(S, n, CGNN_PARTIAL_MAX_NODES) != CGNN_OK) return CGNN_EINVAL;
+  if (cgnn_check_units(S, T, n, window, stride, &un) != CGNN_OK) return CGNN_EINVAL;
+  if (keep_bytes < 0 || stats_bytes < 0 || matrices_bytes < 0 || alpha_bytes < 0) return CGNN_EINVAL;
+  const int64_t U = un.U;
   if (S == 0) return CGNN_OK;
-  const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
   if (!ts || !stats || !matrices || !alpha || (masked && !keep)) return CGNN_EINVAL;
-  if (((bits(ts) | bits(stats) | bits(matrices)) & 3) || (bits(alpha) & 7)) return CGNN_EINVAL;
+  if (cgnn_misaligned({ts, stats, matrices}, 3) || cgnn_misaligned({alpha}, 7)) return CGNN_EINVAL;
   CGNN_NEED_BYTES(alpha, alpha_bytes, U * (int64_t)sizeof(double));
   const int grid = cgnn_grid_for(U, CGNN_LW_PER_CU);
   hipStream_t hs = cgnn_stream(stream);
@@ -204,9 +196,9 @@ int lw_call(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, in
     CGNN_NEED_BYTES(keep, keep_bytes, S * (int64_t)T);
     CGNN_NEED_BYTES(stats, stats_bytes, U * n * 2 * (int64_t)sizeof(float));
     CGNN_NEED_BYTES(matrices, matrices_bytes, U * n * (int64_t)n * (int64_t)sizeof(float));
-    k_lw<true><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, matrices, alpha, keep);
+    k_lw<true><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)un.W, un.L, un.st, stats, matrices, alpha, keep);
   } else {
-    k_lw<false><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, matrices, alpha, nullptr);
+    k_lw<false><<<grid, kLwThreads, 0, hs>>>(ts, U, T, n, (int)un.W, un.L, un.st, stats, matrices, alpha, nullptr);
   }
   CGNN_CHECK_LAUNCH();
   return CGNN_OK;

@@ -6,13 +6,12 @@
 // r[i,j] = sum_t z[t,i] z[t,j] with z[t,i] = (x[t,i] - m_i) / sqrt(q_i), centred and scaled in fp32 as the
 // operands are staged; 1/sqrt(0) is taken as 0, so a constant column gives a zero row and column.
 //
-//   k_corr_stats   a workgroup of 4 waves per (unit, 64 columns), grid stride: lane = column (a wave reads 256
-//                  consecutive bytes of a frame), wave = frame phase.  A thread centres 8 frames at a time in
-//                  registers (their mean, then their centred squares, fp64) and merges the block into its
-//                  running (count, mean, centred sum) by the pairwise update of Chan et al.; the four waves'
-//                  moments merge the same way through LDS, in wave order.  One read of every frame, no
-//                  E[x^2] - E[x]^2 anywhere; a constant column gives q = 0 exactly.  Writes stats[u, i] =
-//                  (m_i, 1/sqrt(q_i)) as floats.
+//   k_corr_stats   the stream of frame_mask.h: a workgroup of 4 waves per (unit, 64 columns), lane = column, wave =
+//                  frame phase.  A thread centres 8 frames at a time in registers (their mean, then their centred
+//                  squares, fp64) and merges the block into its running (count, mean, centred sum) by the pairwise
+//                  update of Chan et al.; the four waves' moments merge the same way through LDS, in wave order.  One
+//                  read of every frame, no E[x^2] - E[x]^2 anywhere; a constant column gives q = 0 exactly.  Writes
+//                  stats[u, i] = (m_i, 1/sqrt(q_i)) as floats.
 //   k_corr<vec>    r = Z^T Z on the tile walk of gram_tile.h (96 x 96 outputs per item, the frames 32 at a time on
 //                  v_mfma_f32_16x16x4_f32; the design is told there).  Stage: the column statistics of the
 //                  item's two tiles wait in LDS, an entry is centred and scaled in fp32 on its way into the
@@ -22,26 +21,23 @@
 //                  1 (0 for a constant column) -- so the matrix is bit-symmetric by construction.
 //
 // cgnn_ingest_corr_masked is the same with a frame mask keep [S, T]: a unit's frames are its window's
-// kept ones.  The mask is a template argument of both kernels: in k_corr_stats a block's count is its kept frames and the
-// waves' counts go through LDS; in k_corr a censored frame is staged as a zero row (the 32 flags of a step are one ballot,
-// fetched a step ahead).  The unmasked instantiations keep their code.
+// kept ones.  The mask is a template argument of both kernels and the predicate of frame_mask.h: in k_corr_stats a
+// block's count is its kept frames and the waves' counts go through LDS; in k_corr a censored frame is staged as a zero
+// row (the 32 flags of a step are one ballot, fetched a step ahead).  The unmasked instantiations keep their code.
 //
 // Accumulation is fp32 over the frames in ascending order, no atomics: the same bits on every run and for every
 // grid.  Frames past L and columns past n are zeros in LDS and are never read from memory.  Element offsets
 // into `ts` and `out` are 64-bit.
 #include <math.h>
 
-#include "common.h"
+#include "frame_mask.h"
 #include "gram_tile.h"
+#include "series_request.h"
 
 namespace {
 
 using namespace gram;
 static_assert(kKS == 32, "k_corr<., true> keeps the flags of a step in one 32-bit ballot");
-
-constexpr int kStatCols = 64;                 // k_corr_stats: columns per workgroup
-constexpr int kStatThreads = 256;
-constexpr int kStatBlock = 8;                 // frames a thread centres in registers before it merges them
 
 // (count, mean, centred sum of squares) of two disjoint sets of samples -> of their union (Chan et al.)
 __device__ __forceinline__ void merge_moments(int& cnt, double& mean, double& m2, int cb, double mb, double m2b) {
@@ -53,93 +49,62 @@ __device__ __forceinline__ void merge_moments(int& cnt, double& mean, double& m2
   cnt = tot;
 }
 
-// kMask: `keep` [S, T] selects the frames.  A unit's frames are its window's kept ones: a censored
-// frame's value is loaded beside its flag (no load waits for another) and left out by selection; it is in no count, and
-// the waves' counts go through LDS instead of being derived from L.
+// The column statistics, on the stream of frame_mask.h: a block of frames is centred in registers and merged into the
+// thread's running moments, then the four waves' moments in wave order.  kMask: `keep` [S, T] selects
+// the frames.  A unit's frames are its window's kept ones: a censored frame is in no count, and the waves' counts go
+// through LDS instead of being derived from L.
+struct Moments {
+  int cnt = 0;
+  double mean = 0.0, m2 = 0.0;
+};
+
 template <bool kMask>
-__global__ __launch_bounds__(kStatThreads) void k_corr_stats(const float* __restrict__ ts, int64_t U, int T, int n,
+__global__ __launch_bounds__(kStreamThreads) void k_corr_stats(const float* __restrict__ ts, int64_t U, int T, int n,
                                                              int W, int L, int stride, float* __restrict__ stats,
                                                              const uint8_t* __restrict__ keep) {
-  __shared__ double part[2][kStatThreads / 64][kStatCols];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int chunks = (n + kStatCols - 1) / kStatCols;
-  const int64_t items = U * chunks;
-  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-    const int64_t u = item / chunks;
-    const int col = (int)(item - u * chunks) * kStatCols + lane;
-    const int64_t s = u / W;
-    const int w = (int)(u - s * W);
-    const bool act = col < n;
-    const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n + (act ? col : 0);
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
-    auto frame = [&](int t) {                 // frame t of the window counts
-      if constexpr (kMask) return t < L && kp[t] != 0;
-      else return t < L;
-    };
-    // this wave's frames are wave, wave + 4, ...: blocks of kStatBlock of them are centred in registers
-    // and merged into the running moments, so every frame is read once
-    // kMask: the flags of a block of frames tb, tb + 4, .. are one load, lane i's of frame tb + 4 i, and a ballot (every
-    // lane takes part, so the lanes past n walk column 0 along and write nothing)
-    auto flags = [&](int tb) {
-      if constexpr (kMask) return (unsigned)__ballot(lane < kStatBlock && frame(tb + 4 * lane));
-      else return 0u;
-    };
-    int cnt = 0;
-    double mean = 0.0, m2 = 0.0;
-    if (act || kMask) {
-      float v[kStatBlock], nx[kStatBlock];
-#pragma unroll
-      for (int i = 0; i < kStatBlock; ++i) nx[i] = wave + 4 * i < L ? x[(int64_t)(wave + 4 * i) * n] : 0.0f;
-      unsigned vk = 0, nk = flags(wave);        // kMask: bit i says that v[i] / nx[i] is a kept frame
-      for (int t0 = wave; t0 < L; t0 += 4 * kStatBlock) {
-        vk = nk;
-        nk = flags(t0 + 4 * kStatBlock);
-#pragma unroll
-        for (int i = 0; i < kStatBlock; ++i) {          // the next block's loads fly while this one is reduced
-          const int t = t0 + 4 * (kStatBlock + i);
-          v[i] = nx[i];
-          nx[i] = t < L ? x[(int64_t)t * n] : 0.0f;
-        }
-        const int left = (L - t0 + 3) / 4;
-        const int cb = kMask ? __builtin_popcount(vk) : (left < kStatBlock ? left : kStatBlock);
+  __shared__ double part[2][kStreamWaves][kStreamCols];
+  cgnn_stream_columns<kMask, Moments>(
+      ts, keep, U, T, n, W, L, stride,
+      [](Moments& a, const float (&v)[kStreamBlock], unsigned bits, int frames) {
+        const int cb = kMask ? __builtin_popcount(bits) : frames;
         double sum = 0.0;
 #pragma unroll
-        for (int i = 0; i < kStatBlock; ++i)             // (the padding adds zeros; a censored frame is left out)
-          sum += !kMask || ((vk >> i) & 1) ? (double)v[i] : 0.0;
+        for (int i = 0; i < kStreamBlock; ++i)          // (the padding adds zeros; a censored frame is left out)
+          sum += !kMask || ((bits >> i) & 1) ? (double)v[i] : 0.0;
         const double mb = sum / (double)cb;     // (cb == 0: nothing of this block is merged)
         double m2b = 0.0;
 #pragma unroll
-        for (int i = 0; i < kStatBlock; ++i) {
+        for (int i = 0; i < kStreamBlock; ++i) {
           const double d = (double)v[i] - mb;
-          if (kMask ? (vk >> i) & 1 : i < cb) m2b += d * d;
+          if (kMask ? (bits >> i) & 1 : i < cb) m2b += d * d;
         }
-        merge_moments(cnt, mean, m2, cb, mb, m2b);
-      }
-    }
-    part[0][wave][lane] = mean;
-    part[1][wave][lane] = m2;
-    if constexpr (kMask) {
-      __shared__ int counts[kStatThreads / 64][kStatCols];
-      counts[wave][lane] = cnt;
-      __syncthreads();
-      if (wave == 0 && act)
-        for (int k = 1; k < kStatThreads / 64; ++k)
-          merge_moments(cnt, mean, m2, counts[k][lane], part[0][k][lane], part[1][k][lane]);
-    } else {
-      __syncthreads();
-      if (wave == 0 && act)                    // the four waves' moments, in wave order
-        for (int k = 1; k < kStatThreads / 64; ++k) {
-          const int ck = k < L ? (L - k + 3) / 4 : 0;
-          merge_moments(cnt, mean, m2, ck, part[0][k][lane], part[1][k][lane]);
+        merge_moments(a.cnt, a.mean, a.m2, cb, mb, m2b);
+      },
+      [&](Moments a, int64_t u, int col, bool act, int lane, int wave) {
+        part[0][wave][lane] = a.mean;
+        part[1][wave][lane] = a.m2;
+        if constexpr (kMask) {
+          __shared__ int counts[kStreamWaves][kStreamCols];
+          counts[wave][lane] = a.cnt;
+          __syncthreads();
+          if (wave == 0 && act)
+            for (int k = 1; k < kStreamWaves; ++k)
+              merge_moments(a.cnt, a.mean, a.m2, counts[k][lane], part[0][k][lane], part[1][k][lane]);
+        } else {
+          __syncthreads();
+          if (wave == 0 && act)                    // the four waves' moments, in wave order
+            for (int k = 1; k < kStreamWaves; ++k) {
+              const int ck = k < L ? (L - k + 3) / 4 : 0;
+              merge_moments(a.cnt, a.mean, a.m2, ck, part[0][k][lane], part[1][k][lane]);
+            }
         }
-    }
-    if (wave == 0 && act) {
-      float* __restrict__ o = stats + (u * n + col) * 2;
-      o[0] = (float)mean;
-      o[1] = m2 == 0.0 ? 0.0f : (float)(1.0 / sqrt(m2));   // (a NaN stays a NaN)
-    }
-    __syncthreads();
-  }
+        if (wave == 0 && act) {
+          float* __restrict__ o = stats + (u * n + col) * 2;
+          o[0] = (float)a.mean;
+          o[1] = a.m2 == 0.0 ? 0.0f : (float)(1.0 / sqrt(a.m2));   // (a NaN stays a NaN)
+        }
+        __syncthreads();
+      });
 }
 
 struct alignas(16) CorrShared {
@@ -160,10 +125,9 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
 
   for (int64_t item = first_item(); item < items; item += gridDim.x) {
     const Item it(item, nt, th.wave);
-    const int64_t u = it.unit, s = u / W;
-    const int w = (int)(u - s * W);
-    const float* __restrict__ x = ts + (s * T + (int64_t)w * stride) * n;
-    const uint8_t* __restrict__ kp = kMask ? keep + s * T + (int64_t)w * stride : nullptr;
+    const int64_t u = it.unit, first = cgnn_first_frame(u, W, T, stride);
+    const float* __restrict__ x = ts + first * n;
+    const cgnn_frame_mask<kMask> mask(keep, first, L);
 
     __syncthreads();                          // the previous item's epilogue still reads sh.rstd
     if (th.tid < 2 * kTile) {
@@ -186,10 +150,7 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
     bool flag = false;
     uint64_t bits = 0;
     int bits_k0 = -1;
-    auto fetch = [&](int k0) {
-      const int t = k0 + (th.tid & 31);
-      flag = t < L && kp[t] != 0;
-    };
+    auto fetch = [&](int k0) { flag = mask.kept(k0 + (th.tid & 31)); };
     if constexpr (kMask) fetch(0);
     __syncthreads();
 
@@ -249,52 +210,36 @@ __global__ __launch_bounds__(kThreads) void k_corr(const float* __restrict__ ts,
 #define CGNN_CORR_STATS_PER_CU 4
 #endif
 
-}  // namespace
-
-namespace {
+template <bool kMask>
+int launch(const float* ts, const cgnn_units& un, int32_t T, int32_t n, int32_t absolute, const uint8_t* keep, float* stats,
+           float* out, hipStream_t hs) {
+  const int64_t chunks = (n + kStreamCols - 1) / kStreamCols;
+  k_corr_stats<kMask><<<cgnn_grid_for(un.U * chunks, CGNN_CORR_STATS_PER_CU), kStreamThreads, 0, hs>>>(
+      ts, un.U, T, n, (int)un.W, un.L, un.st, stats, keep);
+  CGNN_CHECK_LAUNCH();
+  const int grid = cgnn_grid_for(un.U * pairs_of(tiles_of(n)), CGNN_CORR_WG_PER_CU);
+  if (n % 4 == 0 && !cgnn_misaligned({ts, out}, 15))
+    k_corr<true, kMask><<<grid, kThreads, 0, hs>>>(ts, un.U, T, n, (int)un.W, un.L, un.st, absolute, stats, out, keep);
+  else
+    k_corr<false, kMask><<<grid, kThreads, 0, hs>>>(ts, un.U, T, n, (int)un.W, un.L, un.st, absolute, stats, out, keep);
+  CGNN_CHECK_LAUNCH();
+  return CGNN_OK;
+}
 
 // what both entry points check and do; masked: keep [S, T] selects the frames
 int corr_call(const float* ts, int64_t S, int32_t T, int32_t n, int32_t window, int32_t stride, int32_t absolute,
               const uint8_t* keep, int64_t keep_bytes, bool masked, float* stats, int64_t stats_bytes, float* out,
               int64_t out_bytes, void* stream) {
-  constexpr int64_t kLimit = (int64_t)1 << 31;
-  if (cgnn_check_cohort(S, n) != CGNN_OK || T < 2) return CGNN_EINVAL;
-  if (window != 0 && (window < 2 || window > T || stride < 1)) return CGNN_EINVAL;
-  const int L = window ? window : T;
-  const int st = window ? stride : T;
-  const int64_t W = (T - L) / st + 1;
-  const int64_t U = S * W;
-  if (U * n >= kLimit || keep_bytes < 0) return CGNN_EINVAL;
+  cgnn_units un;
+  if (cgnn_check_cohort(S, n) != CGNN_OK || cgnn_check_units(S, T, n, window, stride, &un) != CGNN_OK) return CGNN_EINVAL;
+  if (keep_bytes < 0) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
-  if (!ts || !stats || !out || (reinterpret_cast<uintptr_t>(ts) & 3)) return CGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(stats) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return CGNN_EINVAL;
-  if (masked && !keep) return CGNN_EINVAL;
+  if (!ts || !stats || !out || cgnn_misaligned({ts, stats, out}, 3) || (masked && !keep)) return CGNN_EINVAL;
   CGNN_NEED_BYTES(keep, keep_bytes, S * (int64_t)T);
-  CGNN_NEED_BYTES(stats, stats_bytes, U * n * 2 * (int64_t)sizeof(float));
-  CGNN_NEED_BYTES(out, out_bytes, U * n * (int64_t)n * (int64_t)sizeof(float));
-  hipStream_t hs = cgnn_stream(stream);
-  const int64_t chunks = (n + kStatCols - 1) / kStatCols;
-  const int stat_grid = cgnn_grid_for(U * chunks, CGNN_CORR_STATS_PER_CU);
-  if (masked)
-    k_corr_stats<true><<<stat_grid, kStatThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, keep);
-  else
-    k_corr_stats<false><<<stat_grid, kStatThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, stats, nullptr);
-  CGNN_CHECK_LAUNCH();
-  const int grid = cgnn_grid_for(U * pairs_of(tiles_of(n)), CGNN_CORR_WG_PER_CU);
-  const bool vec = n % 4 == 0 && !(reinterpret_cast<uintptr_t>(ts) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15);
-  if (masked) {
-    if (vec)
-      k_corr<true, true><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, keep);
-    else
-      k_corr<false, true><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, keep);
-  } else {
-    if (vec)
-      k_corr<true, false><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, nullptr);
-    else
-      k_corr<false, false><<<grid, kThreads, 0, hs>>>(ts, U, T, n, (int)W, L, st, absolute, stats, out, nullptr);
-  }
-  CGNN_CHECK_LAUNCH();
-  return CGNN_OK;
+  CGNN_NEED_BYTES(stats, stats_bytes, un.U * n * 2 * (int64_t)sizeof(float));
+  CGNN_NEED_BYTES(out, out_bytes, un.U * n * (int64_t)n * (int64_t)sizeof(float));
+  return masked ? launch<true>(ts, un, T, n, absolute, keep, stats, out, cgnn_stream(stream))
+                : launch<false>(ts, un, T, n, absolute, nullptr, stats, out, cgnn_stream(stream));
 }
 
 }  // namespace

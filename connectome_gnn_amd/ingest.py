@@ -342,6 +342,7 @@ orthogonal DCT projection centred over all ``T`` frames; then, with ``confounds=
 from __future__ import annotations
 
 import ctypes
+import itertools
 import math
 from typing import NamedTuple, Optional
 
@@ -431,13 +432,44 @@ def _threshold_choice(n: int, units: int, unit_name: str, keep, num_edges, min_w
     return 0, min_weight
 
 
-def _require_resident(matrices: torch.Tensor) -> None:
-    if not matrices.is_contiguous():
-        raise ValueError("matrices must be contiguous")
-    if not matrices.is_cuda:
+_MATRICES = ("matrices", "thresholds connectivity matrices")         # _require_resident's noun and verb phrase
+_SERIES = ("timeseries", "correlates ROI time series")
+_CONFOUNDS = ("confounds", "orthonormalises confounds")
+
+
+def _require_resident(data: torch.Tensor, noun: str, does: str) -> None:
+    if not data.is_contiguous():
+        raise ValueError(f"{noun} must be contiguous")
+    if not data.is_cuda:
         raise RuntimeError(
-            f"matrices are on {matrices.device}: connectome_gnn_amd thresholds connectivity matrices on a "
-            "ROCm device only (there is no CPU fallback; move them with .to('cuda')).")
+            f"{noun} are on {data.device}: connectome_gnn_amd {does} on a ROCm "
+            "device only (there is no CPU fallback; move them with .to('cuda')).")
+
+
+_WORK = object()                                      # among _call's arguments: where the workspace goes
+
+
+def _buf(t) -> tuple:
+    """A buffer as the library takes it: the pointer, then the byte count."""
+    return _lib.ptr(t), _lib.nbytes(t)
+
+
+def _call(dev, name: str, *args, workspace=None) -> None:
+    """``name(*args, stream)`` on ``dev`` under its device guard, with the stream torch is enqueuing on, checked under
+    the call's name.  ``workspace=(call, *arguments)``: ``call + "_workspace_bytes"`` is asked first (its answer may
+    depend on the device's grid), a negative answer is refused, and ``_WORK`` among ``args`` becomes the pointer and
+    the byte count of a uint8 buffer of that size (no buffer for 0 bytes)."""
+    lib = _lib.load()
+    with _lib.device_guard(dev):
+        if workspace is not None:
+            query = workspace[0] + "_workspace_bytes"
+            need = getattr(lib, query)(*workspace[1:])
+            if need < 0:                              # (the message names the sizes: the integers in front)
+                sizes = itertools.takewhile(lambda a: isinstance(a, int), workspace[1:])
+                raise _lib.CgnnError(f"{query}({', '.join(map(str, sizes))}) refused its arguments")
+            at = args.index(_WORK)
+            args = args[:at] + _buf(torch.empty(need, dtype=torch.uint8, device=dev) if need else None) + args[at + 1:]
+        _lib.check(getattr(lib, name)(*args, _lib.stream_ptr(dev)), name)
 
 
 def _thresholds(matrices: torch.Tensor, S: int, keep, num_edges, min_weight) -> torch.Tensor:
@@ -449,8 +481,27 @@ def _thresholds(matrices: torch.Tensor, S: int, keep, num_edges, min_weight) -> 
     return torch.full((S,), min_weight, dtype=torch.float32, device=matrices.device)
 
 
-def _check_timeseries(timeseries, window, stride) -> tuple:
-    """(S, T, n, L, st, W) of a valid request: L frames per unit, st frames between units, W units a subject."""
+class _Series(NamedTuple):
+    """A valid request: S subjects of T frames and n ROIs; L frames per unit, st frames between units, W units a
+    subject."""
+    S: int
+    T: int
+    n: int
+    L: int
+    st: int
+    W: int
+
+    def window(self, windowed: bool) -> tuple:
+        """(window, stride) as the C calls take them: zeros for whole runs."""
+        return (self.L, self.st) if windowed else (0, 0)
+
+
+def _check_frames(T: int) -> None:
+    if T > _FILTER_MAX_FRAMES:
+        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+
+
+def _check_timeseries(timeseries, window, stride) -> _Series:
     if not isinstance(timeseries, torch.Tensor):
         raise TypeError(f"timeseries must be a torch.Tensor, got {type(timeseries).__name__}")
     if timeseries.dtype != torch.float32:
@@ -479,16 +530,14 @@ def _check_timeseries(timeseries, window, stride) -> tuple:
         raise ValueError(f"units * n = {S * W * n} >= 2^31: ingest the cohort in slices of subjects")
     if n * n >= _LIMIT:
         raise ValueError(f"n * n = {n * n} >= 2^31: matrices this large are not supported")
-    return S, T, n, L, st, W
+    return _Series(S, T, n, L, st, W)
 
 
-def _require_resident_timeseries(timeseries: torch.Tensor) -> None:
-    if not timeseries.is_contiguous():
-        raise ValueError("timeseries must be contiguous")
-    if not timeseries.is_cuda:
-        raise RuntimeError(
-            f"timeseries are on {timeseries.device}: connectome_gnn_amd correlates ROI time series on a ROCm "
-            "device only (there is no CPU fallback; move them with .to('cuda')).")
+def _check_run(timeseries) -> _Series:
+    """``_check_timeseries`` of whole runs that the filter's kernels take: at most 2^30 frames."""
+    series = _check_timeseries(timeseries, None, None)
+    _check_frames(series.T)
+    return series
 
 
 def _finite_number(name: str, v) -> float:
@@ -543,6 +592,12 @@ def _check_out(out, timeseries: torch.Tensor) -> None:
         raise ValueError("out must be contiguous")
 
 
+def _resident_out(timeseries: torch.Tensor, out) -> torch.Tensor:
+    """Where the result of resident time series goes: ``out`` (``_check_out``'s), or a new tensor."""
+    _require_resident(timeseries, *_SERIES)
+    return torch.empty_like(timeseries) if out is None else out
+
+
 def _check_confounds(confounds, S=None, T=None, device=None) -> tuple:
     """(S, T, q) of valid confounds; with S, T and device given, of confounds that go with those time series."""
     if not isinstance(confounds, torch.Tensor):
@@ -559,8 +614,7 @@ def _check_confounds(confounds, S=None, T=None, device=None) -> tuple:
         raise ValueError(f"confounds hold q = {q} columns: 1 <= q <= CONFOUND_MAX = {CONFOUND_MAX}")
     if ct < 2:
         raise ValueError(f"confounds need T >= 2 frames, got T = {ct}")
-    if ct > _FILTER_MAX_FRAMES:
-        raise ValueError(f"T = {ct} > 2^30 frames: runs this long are not supported")
+    _check_frames(ct)
     if cs >= _LIMIT:
         raise ValueError(f"S = {cs} >= 2^31: ingest the cohort in slices of subjects")
     if device is not None and confounds.device != device:
@@ -587,30 +641,19 @@ def _check_sample_mask(sample_mask, S: int, T: int, device):
     return sample_mask
 
 
-def _require_resident_confounds(confounds: torch.Tensor) -> None:
-    if not confounds.is_cuda:
-        raise RuntimeError(
-            f"confounds are on {confounds.device}: connectome_gnn_amd orthonormalises confounds on a ROCm device only "
-            "(there is no CPU fallback; move them with .to('cuda')).")
+def _masked(name: str, keep) -> tuple:
+    """(the entry point of ``name`` that goes with ``keep``, what it takes for the mask)"""
+    return (name, ()) if keep is None else (name + "_masked", _buf(keep))
 
 
-def _confound_basis(confounds: torch.Tensor, S: int, T: int, q: int, keep=None) -> tuple:
+def _confound_basis(confounds: torch.Tensor, keep=None) -> tuple:
     dev = confounds.device
-    qpad = (q + 31) // 32 * 32
-    basis = torch.empty(S, T, qpad, dtype=torch.float32, device=dev)
+    S, T, q = confounds.shape
+    basis = torch.empty(S, T, (q + 31) // 32 * 32, dtype=torch.float32, device=dev)
     rank = torch.empty(S, dtype=torch.int32, device=dev)
     if S:
-        lib = _lib.load()
-        with _lib.device_guard(dev):
-            if keep is None:
-                _lib.check(lib.cgnn_ingest_confound_basis(_lib.ptr(confounds), S, T, q, _lib.ptr(basis),
-                                                          _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank),
-                                                          _lib.stream_ptr(dev)), "cgnn_ingest_confound_basis")
-            else:
-                _lib.check(lib.cgnn_ingest_confound_basis_masked(
-                    _lib.ptr(confounds), S, T, q, _lib.ptr(keep), _lib.nbytes(keep), _lib.ptr(basis),
-                    _lib.nbytes(basis), _lib.ptr(rank), _lib.nbytes(rank), _lib.stream_ptr(dev)),
-                    "cgnn_ingest_confound_basis_masked")
+        name, mask = _masked("cgnn_ingest_confound_basis", keep)
+        _call(dev, name, _lib.ptr(confounds), S, T, q, *mask, *_buf(basis), *_buf(rank))
     return basis, rank
 
 
@@ -624,28 +667,16 @@ def confound_basis(confounds: torch.Tensor, *, sample_mask=None) -> tuple:
     frames are exactly zero, and a non-finite confound counts only in a kept frame."""
     S, T, q = _check_confounds(confounds)
     keep = _check_sample_mask(sample_mask, S, T, confounds.device)
-    _require_resident_confounds(confounds)
-    return _confound_basis(confounds, S, T, q, keep)
+    _require_resident(confounds, *_CONFOUNDS)
+    return _confound_basis(confounds, keep)
 
 
-def _regress(timeseries: torch.Tensor, S: int, T: int, n: int, basis, out: torch.Tensor, keep=None) -> None:
+def _regress(timeseries: torch.Tensor, basis, out: torch.Tensor, keep=None) -> None:
     """``basis`` None (with ``keep``): masked centring alone."""
-    dev = timeseries.device
-    lib = _lib.load()
-    with _lib.device_guard(dev):
-        need = lib.cgnn_ingest_regress_workspace_bytes(S, T, n)
-        if need < 0:
-            raise _lib.CgnnError(f"cgnn_ingest_regress_workspace_bytes({S}, {T}, {n}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
-        if keep is None:
-            _lib.check(lib.cgnn_ingest_regress(_lib.ptr(timeseries), S, T, n, _lib.ptr(basis), _lib.nbytes(basis),
-                                               int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
-                                               _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress")
-        else:
-            _lib.check(lib.cgnn_ingest_regress_masked(
-                _lib.ptr(timeseries), S, T, n, _lib.ptr(keep), _lib.nbytes(keep), _lib.ptr(basis), _lib.nbytes(basis),
-                0 if basis is None else int(basis.shape[2]), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
-                _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_regress_masked")
+    S, T, n = timeseries.shape
+    name, mask = _masked("cgnn_ingest_regress", keep)
+    _call(timeseries.device, name, _lib.ptr(timeseries), S, T, n, *mask, *_buf(basis),
+          0 if basis is None else int(basis.shape[2]), _WORK, *_buf(out), workspace=("cgnn_ingest_regress", S, T, n))
 
 
 def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, sample_mask=None, out=None) -> torch.Tensor:
@@ -656,65 +687,59 @@ def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, samp
     launches on resident data; the temporaries are the basis ``[S, T, qpad]`` and the means ``[S, n]``.  No read-back.
     ``sample_mask`` (bool ``[S, T]``, True: kept): the regression runs on the subject's kept frames alone -- the fp64
     least-squares residual of ``x[K]`` on ``[1 | c[K]]`` -- and the censored frames of the result are exactly ``0.0``."""
-    S, T, n = _check_timeseries(timeseries, None, None)[:3]
-    if T > _FILTER_MAX_FRAMES:
-        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
-    q = _check_confounds(confounds, S, T, timeseries.device)[2]
+    S, T = _check_run(timeseries)[:2]
+    _check_confounds(confounds, S, T, timeseries.device)
     keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _check_out(out, timeseries)
-    _require_resident_timeseries(timeseries)
-    if out is None:
-        out = torch.empty_like(timeseries)
-    if S == 0:
-        return out
-    basis, _ = _confound_basis(confounds, S, T, q, keep)
-    _regress(timeseries, S, T, n, basis, out, keep)
+    out = _resident_out(timeseries, out)
+    if S:
+        _regress(timeseries, _confound_basis(confounds, keep)[0], out, keep)
     return out
 
 
-def _filter_censored(timeseries: torch.Tensor, S: int, T: int, n: int, k_lo: int, k_hi: int, confounds, q, keep,
-                     out) -> torch.Tensor:
+def _dropped_components(T: int, k_lo: int, k_hi: int) -> list:
+    """What the band ``k_lo .. k_hi`` drops of a ``T``-frame run, ascending."""
+    return list(range(1, k_lo)) + list(range(k_hi + 1, T))
+
+
+def _smaller_set(T: int, k_lo: int, k_hi: int) -> tuple:
+    """``(complement, comps)``: whether the set that is multiplied, the smaller one, is what the band drops, and its
+    components; refused beyond ``FILTER_MAX_COMPONENTS``."""
+    kept = k_hi - k_lo + 1
+    dropped = T - 1 - kept
+    if min(kept, dropped) > FILTER_MAX_COMPONENTS:
+        raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
+                         f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
+    if kept > dropped:
+        return True, _dropped_components(T, k_lo, k_hi)
+    return False, list(range(k_lo, k_hi + 1))
+
+
+def _filter_censored(timeseries: torch.Tensor, k_lo: int, k_hi: int, confounds, keep, out) -> torch.Tensor:
     """``filter_timeseries`` under a mask: the band removed by regression on ``[dropped cosines | confounds]`` at the
     kept frames (module docstring).  The design and its basis are the only temporaries besides the means."""
-    comps = list(range(1, k_lo)) + list(range(k_hi + 1, T))           # what the band drops, ascending
-    K, nq = len(comps), q or 0
+    S, T, _ = timeseries.shape
+    comps = _dropped_components(T, k_lo, k_hi)
+    K, nq = len(comps), 0 if confounds is None else int(confounds.shape[2])
     if K + nq > CONFOUND_MAX:
         raise ValueError(f"under a sample_mask the band is removed by regression: it drops {K} components, and with "
                          f"{nq} confound columns that is more than CONFOUND_MAX = {CONFOUND_MAX} regressors (a low_pass "
                          "under censoring would need the censored frames interpolated, which is not built)")
-    _require_resident_timeseries(timeseries)
-    if out is None:
-        out = torch.empty_like(timeseries)
+    out = _resident_out(timeseries, out)
     if S == 0:
         return out
     if K + nq == 0:                                   # masked centring: no product launched
-        _regress(timeseries, S, T, n, None, out, keep)
+        _regress(timeseries, None, out, keep)
         return out
     design = confounds
     if K:
-        dev = timeseries.device
-        design = torch.empty(S, T, K + nq, dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            _lib.check(_lib.load().cgnn_ingest_design(_lib.ptr(confounds), S, T, nq, (ctypes.c_int32 * K)(*comps), K,
-                                                      _lib.ptr(design), _lib.nbytes(design), _lib.stream_ptr(dev)),
-                       "cgnn_ingest_design")
-    basis, _ = _confound_basis(design, S, T, K + nq, keep)
+        design = torch.empty(S, T, K + nq, dtype=torch.float32, device=timeseries.device)
+        _call(timeseries.device, "cgnn_ingest_design", _lib.ptr(confounds), S, T, nq, (ctypes.c_int32 * K)(*comps), K,
+              *_buf(design))
+    basis, _ = _confound_basis(design, keep)
     del design
-    _regress(timeseries, S, T, n, basis, out, keep)
+    _regress(timeseries, basis, out, keep)
     return out
-
-
-def _interpolate(timeseries: torch.Tensor, S: int, T: int, n: int, keep: torch.Tensor, out: torch.Tensor) -> None:
-    dev = timeseries.device
-    lib = _lib.load()
-    with _lib.device_guard(dev):
-        need = lib.cgnn_ingest_interpolate_workspace_bytes(S, T, n)
-        if need < 0:
-            raise _lib.CgnnError(f"cgnn_ingest_interpolate_workspace_bytes({S}, {T}, {n}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cgnn_ingest_interpolate(_lib.ptr(timeseries), S, T, n, _lib.ptr(keep), _lib.nbytes(keep),
-                                               _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out), _lib.nbytes(out),
-                                               _lib.stream_ptr(dev)), "cgnn_ingest_interpolate")
 
 
 def interpolate_censored(timeseries: torch.Tensor, sample_mask: torch.Tensor, *, out=None) -> torch.Tensor:
@@ -729,25 +754,21 @@ def interpolate_censored(timeseries: torch.Tensor, sample_mask: torch.Tensor, *,
     ``timeseries`` itself, with the same bits as out of place.  Three launches on resident data; the temporary is the
     workspace of the solve (44 bytes per frame and subject, and a slab that depends on the device alone).  No
     read-back, no atomics; every run and every grid gives the same bits."""
-    S, T, n = _check_timeseries(timeseries, None, None)[:3]
-    if T > _FILTER_MAX_FRAMES:
-        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+    S, T, n = _check_run(timeseries)[:3]
     if sample_mask is None:
         raise TypeError("sample_mask must be a torch.Tensor, got None: interpolate_censored needs the frames to replace")
     keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _check_out(out, timeseries)
-    _require_resident_timeseries(timeseries)
-    if out is None:
-        out = torch.empty_like(timeseries)
-    if S == 0:
-        return out
-    _interpolate(timeseries, S, T, n, keep, out)
+    out = _resident_out(timeseries, out)
+    if S:
+        _call(timeseries.device, "cgnn_ingest_interpolate", _lib.ptr(timeseries), S, T, n, *_buf(keep), _WORK,
+              *_buf(out), workspace=("cgnn_ingest_interpolate", S, T, n))
     return out
 
 
 def _filter_interpolated(timeseries: torch.Tensor, band: dict, confounds, keep, out) -> torch.Tensor:
     """``filter_timeseries(..., sample_mask=, interpolate=True)``: the sequence of public calls of the module docstring."""
-    _require_resident_timeseries(timeseries)
+    _require_resident(timeseries, *_SERIES)
     out = interpolate_censored(timeseries, keep, out=out)
     filter_timeseries(out, out=out, **band)
     if confounds is None:
@@ -785,104 +806,57 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
         raise TypeError(f"interpolate must be a bool, got {type(interpolate).__name__}")
     if interpolate and sample_mask is None:
         raise ValueError("interpolate=True replaces the censored frames: give sample_mask= with it")
-    S, T, n = _check_timeseries(timeseries, None, None)[:3]
-    if T > _FILTER_MAX_FRAMES:
-        raise ValueError(f"T = {T} > 2^30 frames: runs this long are not supported")
+    S, T, n = _check_run(timeseries)[:3]
     k_lo, k_hi = filter_components(T, t_r, high_pass, low_pass)
     if k_lo > k_hi:
         raise ValueError(f"the band high_pass={high_pass}, low_pass={low_pass} at t_r={t_r} holds no component of a "
                          f"{T}-frame run (components {k_lo} .. {k_hi}; component k has k / (2 T t_r) Hz)")
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+    if keep is None or interpolate:
+        complement, comps = _smaller_set(T, k_lo, k_hi)
+    _check_out(out, timeseries)
+    if confounds is not None:
+        _check_confounds(confounds, S, T, timeseries.device)
     if interpolate:
-        keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
-        kept = k_hi - k_lo + 1
-        dropped = T - 1 - kept
-        if min(kept, dropped) > FILTER_MAX_COMPONENTS:
-            raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
-                             f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
-        _check_out(out, timeseries)
-        if confounds is not None:
-            _check_confounds(confounds, S, T, timeseries.device)
         band = dict(t_r=t_r, high_pass=high_pass, low_pass=low_pass)
         return _filter_interpolated(timeseries, band, confounds, keep, out)
-    if sample_mask is not None:
-        keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
-        _check_out(out, timeseries)
-        q = None if confounds is None else _check_confounds(confounds, S, T, timeseries.device)[2]
-        return _filter_censored(timeseries, S, T, n, k_lo, k_hi, confounds, q, keep, out)
-    kept = k_hi - k_lo + 1
-    dropped = T - 1 - kept
-    complement = kept > dropped                       # the smaller set is the one that is multiplied
-    K = dropped if complement else kept
-    if K > FILTER_MAX_COMPONENTS:
-        raise ValueError(f"the band keeps {kept} components and drops {dropped}: the smaller set must hold at most "
-                         f"FILTER_MAX_COMPONENTS = {FILTER_MAX_COMPONENTS} (narrow the band, or the part it removes)")
-    _check_out(out, timeseries)
-    q = None if confounds is None else _check_confounds(confounds, S, T, timeseries.device)[2]
-    _require_resident_timeseries(timeseries)
-    if out is None:
-        out = torch.empty_like(timeseries)
+    if keep is not None:
+        return _filter_censored(timeseries, k_lo, k_hi, confounds, keep, out)
+    out = _resident_out(timeseries, out)
     if S == 0:
         return out
-    if complement:
-        comps = list(range(1, k_lo)) + list(range(k_hi + 1, T))
-    else:
-        comps = list(range(k_lo, k_hi + 1))
-    dev = timeseries.device
-    lib = _lib.load()
-    with _lib.device_guard(dev):
-        need = lib.cgnn_ingest_filter_workspace_bytes(S, T, n, K)
-        if need < 0:
-            raise _lib.CgnnError(f"cgnn_ingest_filter_workspace_bytes({S}, {T}, {n}, {K}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cgnn_ingest_filter(_lib.ptr(timeseries), S, T, n, (ctypes.c_int32 * K)(*comps), K,
-                                          int(complement), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
-                                          _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_filter")
+    K = len(comps)                                    # the smaller set is the one that is multiplied
+    _call(timeseries.device, "cgnn_ingest_filter", _lib.ptr(timeseries), S, T, n, (ctypes.c_int32 * K)(*comps), K,
+          int(complement), _WORK, *_buf(out), workspace=("cgnn_ingest_filter", S, T, n, K))
     if confounds is not None:                         # the same band on the confounds, then out -= Q (Q^T out) in place
         clean = filter_timeseries(confounds, t_r=t_r, high_pass=high_pass, low_pass=low_pass)
-        basis, _ = _confound_basis(clean, S, T, q)
+        basis, _ = _confound_basis(clean)
         del clean
-        _regress(out, S, T, n, basis, out)
+        _regress(out, basis, out)
     return out
 
 
-def _correlate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, keep=None) -> tuple:
+def _correlate(timeseries: torch.Tensor, series: _Series, windowed: bool, absolute: bool, keep=None) -> tuple:
     """(the correlations [U, n, n], the statistics [U, n, 2] they were built with)"""
     dev = timeseries.device
-    U = S * W
-    out = torch.empty(U, n, n, dtype=torch.float32, device=dev)
-    stats = torch.empty(U, n, 2, dtype=torch.float32, device=dev)      # (mean, 1 / sqrt(q)) per unit and ROI
-    lib = _lib.load()
-    with _lib.device_guard(dev):
-        if keep is None:
-            _lib.check(lib.cgnn_ingest_corr(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
-                                            st if windowed else 0, int(bool(absolute)), _lib.ptr(stats),
-                                            _lib.nbytes(stats), _lib.ptr(out), _lib.nbytes(out),
-                                            _lib.stream_ptr(dev)), "cgnn_ingest_corr")
-        else:
-            _lib.check(lib.cgnn_ingest_corr_masked(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
-                                                   st if windowed else 0, int(bool(absolute)), _lib.ptr(keep),
-                                                   _lib.nbytes(keep), _lib.ptr(stats), _lib.nbytes(stats), _lib.ptr(out),
-                                                   _lib.nbytes(out), _lib.stream_ptr(dev)), "cgnn_ingest_corr_masked")
+    S, T, n = series[:3]
+    out = torch.empty(S * series.W, n, n, dtype=torch.float32, device=dev)
+    stats = torch.empty(S * series.W, n, 2, dtype=torch.float32, device=dev)      # (mean, 1 / sqrt(q)) per unit and ROI
+    name, mask = _masked("cgnn_ingest_corr", keep)
+    _call(dev, name, _lib.ptr(timeseries), S, T, n, *series.window(windowed), int(bool(absolute)), *mask, *_buf(stats),
+          *_buf(out))
     return out, stats
 
 
-def _estimate(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, stats: torch.Tensor,
-              matrices: torch.Tensor, keep=None) -> torch.Tensor:
+def _estimate(timeseries: torch.Tensor, series: _Series, windowed: bool, stats: torch.Tensor, matrices: torch.Tensor,
+              keep=None) -> torch.Tensor:
     """cgnn_ingest_shrinkage: float64 [U], for the signed correlations and the statistics ``_correlate`` returned."""
     dev = timeseries.device
-    alpha = torch.empty(S * W, dtype=torch.float64, device=dev)
-    lib = _lib.load()
-    with _lib.device_guard(dev):
-        if keep is None:
-            _lib.check(lib.cgnn_ingest_shrinkage(_lib.ptr(timeseries), S, T, n, L if windowed else 0,
-                                                 st if windowed else 0, _lib.ptr(stats), _lib.ptr(matrices),
-                                                 _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)),
-                       "cgnn_ingest_shrinkage")
-        else:
-            _lib.check(lib.cgnn_ingest_shrinkage_masked(
-                _lib.ptr(timeseries), S, T, n, L if windowed else 0, st if windowed else 0, _lib.ptr(keep),
-                _lib.nbytes(keep), _lib.ptr(stats), _lib.nbytes(stats), _lib.ptr(matrices), _lib.nbytes(matrices),
-                _lib.ptr(alpha), _lib.nbytes(alpha), _lib.stream_ptr(dev)), "cgnn_ingest_shrinkage_masked")
+    S, T, n = series[:3]
+    alpha = torch.empty(S * series.W, dtype=torch.float64, device=dev)
+    name, mask = _masked("cgnn_ingest_shrinkage", keep)
+    inputs = (_lib.ptr(stats), _lib.ptr(matrices)) if keep is None else _buf(stats) + _buf(matrices)
+    _call(dev, name, _lib.ptr(timeseries), S, T, n, *series.window(windowed), *mask, *inputs, *_buf(alpha))
     return alpha
 
 
@@ -940,20 +914,11 @@ def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage, absolute: bool, 
     """cgnn_ingest_partial of resident matrices into ``out``, which may be ``matrices``; cgnn_ingest_partial_each if
     ``shrinkage`` is a float64 ``[U]`` tensor.  The workspace is what the query asks for: one slab per workgroup of the
     launch."""
-    if U == 0:
-        return out
-    dev = matrices.device
-    lib = _lib.load()
-    with _lib.device_guard(dev):                      # (the byte count depends on the device's grid)
-        need = lib.cgnn_ingest_partial_workspace_bytes(U, n)
-        if need < 0:
-            raise _lib.CgnnError(f"cgnn_ingest_partial_workspace_bytes({U}, {n}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    if U:
         each = isinstance(shrinkage, torch.Tensor)
-        call = "cgnn_ingest_partial_each" if each else "cgnn_ingest_partial"
-        _lib.check(getattr(lib, call)(_lib.ptr(matrices), U, n, _lib.ptr(shrinkage) if each else shrinkage,
-                                      int(bool(absolute)), _lib.ptr(work), _lib.nbytes(work), _lib.ptr(out),
-                                      _lib.nbytes(out), _lib.stream_ptr(dev)), call)
+        _call(matrices.device, "cgnn_ingest_partial_each" if each else "cgnn_ingest_partial", _lib.ptr(matrices), U, n,
+              _lib.ptr(shrinkage) if each else shrinkage, int(bool(absolute)), _WORK, *_buf(out),
+              workspace=("cgnn_ingest_partial", U, n))
     return out
 
 
@@ -965,22 +930,32 @@ def partial_correlation(matrices: torch.Tensor, *, shrinkage=0.0, absolute=False
     U, n = _check_matrices(matrices)
     shrinkage = _check_shrinkage(shrinkage, U, matrices, False)
     _check_partial_size(n)
-    _require_resident(matrices)
+    _require_resident(matrices, *_MATRICES)
     return _partial(matrices, U, n, shrinkage, absolute, torch.empty_like(matrices))
 
 
-def _connectivity(timeseries: torch.Tensor, S, T, n, L, W, st, windowed: bool, absolute: bool, kind: str,
-                  shrinkage, keep=None) -> torch.Tensor:
+def _connectivity(timeseries: torch.Tensor, series: _Series, windowed: bool, absolute: bool, kind: str, shrinkage,
+                  keep=None) -> torch.Tensor:
     """The matrices of a valid request: the correlations, or the partial correlations of the signed correlations
     written over them (no second cohort-sized tensor).  A shrinkage named in SHRINKAGES is estimated in between, from
     the frames, the statistics and the signed correlations."""
     if kind == "correlation":
-        return _correlate(timeseries, S, T, n, L, W, st, windowed, absolute, keep)[0]
-    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False, keep)
+        return _correlate(timeseries, series, windowed, absolute, keep)[0]
+    matrices, stats = _correlate(timeseries, series, windowed, False, keep)
     if isinstance(shrinkage, str):
-        shrinkage = _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices, keep)
+        shrinkage = _estimate(timeseries, series, windowed, stats, matrices, keep)
     del stats
-    return _partial(matrices, S * W, n, shrinkage, absolute, matrices)
+    return _partial(matrices, series.S * series.W, series.n, shrinkage, absolute, matrices)
+
+
+def _check_labels_and_features(labels, S: int, node_features, letter: str, units: int, n: int) -> None:
+    """``labels`` int64 ``[S]``; ``node_features`` None or float32 ``[units, n, F]``, ``letter`` naming the units."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
+        raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
+    if node_features is not None:
+        if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
+                or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (units, n):
+            raise ValueError(f"node_features must be a float32 tensor [{letter}, n, F] = [{units}, {n}, F]")
 
 
 def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None) -> torch.Tensor:
@@ -989,13 +964,13 @@ def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None,
     launches on resident data (the two of ``correlation_matrices``, then the estimate); the matrices and the statistics
     are temporaries.  ``n <= PARTIAL_MAX_NODES``.  No read-back.  ``sample_mask`` (bool ``[S, T]``, True: kept): a
     unit's frames are its window's kept ones, ``L_u`` of them, and ``L_u`` stands wherever ``L`` does."""
-    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
-    _check_partial_size(n)
-    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
-    _require_resident_timeseries(timeseries)
+    series = _check_timeseries(timeseries, window, stride)
+    _check_partial_size(series.n)
+    keep = _check_sample_mask(sample_mask, series.S, series.T, timeseries.device)
+    _require_resident(timeseries, *_SERIES)
     windowed = window is not None
-    matrices, stats = _correlate(timeseries, S, T, n, L, W, st, windowed, False, keep)
-    return _estimate(timeseries, S, T, n, L, W, st, windowed, stats, matrices, keep)
+    matrices, stats = _correlate(timeseries, series, windowed, False, keep)
+    return _estimate(timeseries, series, windowed, stats, matrices, keep)
 
 
 def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
@@ -1008,11 +983,12 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
     ``sample_mask`` (bool ``[S, T]``, True: kept): a unit's frames are its window's kept ones; a unit with fewer than
     two is an all-zero matrix.  The ``n + 2`` frames that ``shrinkage == 0`` asks for are still counted on the window:
     kept counts stay on the device, and a unit that its kept frames leave singular is all NaN."""
-    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    series = _check_timeseries(timeseries, window, stride)
+    S, T, n, L, _, W = series
     shrinkage = _check_kind(kind, shrinkage, n, L, S * W, timeseries)
     keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
-    _require_resident_timeseries(timeseries)
-    return _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage, keep)
+    _require_resident(timeseries, *_SERIES)
+    return _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, keep)
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
@@ -1023,20 +999,16 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
     ``shrinkage`` and ``sample_mask`` are ``correlation_matrices``'s (a unit with fewer than two kept frames is a graph
     without edges).  The one read-back is ``from_matrices``'s."""
-    S, T, n, L, st, W = _check_timeseries(timeseries, window, stride)
+    series = _check_timeseries(timeseries, window, stride)
+    S, T, n, L, _, W = series
     U = S * W
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
     _check_path_size(_check_measures_argument(measures, node_features), n)
     _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
-        raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
-    if node_features is not None:
-        if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
-                or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (U, n):
-            raise ValueError(f"node_features must be a float32 tensor [U, n, F] = [{U}, {n}, F]")
+    _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
-    _require_resident_timeseries(timeseries)
-    matrices = _connectivity(timeseries, S, T, n, L, W, st, window is not None, absolute, kind, shrinkage, sample_mask)
+    _require_resident(timeseries, *_SERIES)
+    matrices = _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, sample_mask)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
                          num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
 
@@ -1086,22 +1058,15 @@ def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch
     per workgroup for the weighted paths.  Returns ``x``."""
     if S == 0:
         return x
-    dev = matrices.device
-    lib = _lib.load()
     num = len(ids)
     arr = (ctypes.c_int32 * num)(*ids)
     args = [_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num]
     if fam.cols:
         args += [(ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1]
-    with _lib.device_guard(dev):                      # (the weighted paths' byte count depends on the device's grid)
-        need = getattr(lib, fam.call + "_workspace_bytes")(S, n, arr, num)
-        if need < 0:
-            raise _lib.CgnnError(f"{fam.call}_workspace_bytes({S}, {n}) refused its arguments")
-        work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        args += [_lib.ptr(work), _lib.nbytes(work), _lib.ptr(x), _lib.nbytes(x)]
-        if fam.dist:
-            args += [_lib.ptr(dist), _lib.nbytes(dist)]
-        _lib.check(getattr(lib, fam.call)(*args, _lib.stream_ptr(dev)), fam.call)
+    args += [_WORK, *_buf(x)]
+    if fam.dist:
+        args += _buf(dist)
+    _call(matrices.device, fam.call, *args, workspace=(fam.call, S, n, arr, num))
     return x
 
 
@@ -1134,7 +1099,7 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
-    _require_resident(matrices)
+    _require_resident(matrices, *_MATRICES)
     return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids)
 
 
@@ -1147,7 +1112,7 @@ def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weigh
     S, n = _check_matrices(matrices)
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_size(_WEIGHTED, n, "path_lengths takes")
-    _require_resident(matrices)
+    _require_resident(matrices, *_MATRICES)
     thr = _thresholds(matrices, S, keep, num_edges, min_weight)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
     _run_family(_WEIGHTED, matrices, S, n, thr, [], [], None, dist)
@@ -1159,12 +1124,9 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
     device): the threshold that ``from_matrices`` applies for the same ``keep`` / ``num_edges``."""
     S, n = _check_matrices(matrices)
     k = _rank(n, keep, num_edges)
-    _require_resident(matrices)
-    dev = matrices.device
-    thr = torch.empty(S, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        _lib.check(_lib.load().cgnn_ingest_select(_lib.ptr(matrices), S, n, k, _lib.ptr(thr), _lib.nbytes(thr),
-                                                  _lib.stream_ptr(dev)), "cgnn_ingest_select")
+    _require_resident(matrices, *_MATRICES)
+    thr = torch.empty(S, dtype=torch.float32, device=matrices.device)
+    _call(matrices.device, "cgnn_ingest_select", _lib.ptr(matrices), S, n, k, *_buf(thr))
     return thr
 
 
@@ -1178,17 +1140,12 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
     S, n = _check_matrices(matrices)
     k, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
-        raise ValueError(f"labels must be an int64 tensor [S] = [{S}]")
-    if node_features is not None:
-        if not isinstance(node_features, torch.Tensor) or node_features.dtype != torch.float32 \
-                or node_features.dim() != 3 or tuple(node_features.shape[:2]) != (S, n):
-            raise ValueError(f"node_features must be a float32 tensor [S, n, F] = [{S}, {n}, F]")
-        if node_features.device != matrices.device:
-            raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
+    _check_labels_and_features(labels, S, node_features, "S", S, n)
+    if node_features is not None and node_features.device != matrices.device:
+        raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
-    _require_resident(matrices)
+    _require_resident(matrices, *_MATRICES)
     dev = matrices.device
     lib = _lib.load()
     if min_weight is None:
@@ -1203,9 +1160,8 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     row_off = torch.zeros(S * n + 1, dtype=torch.long, device=dev)
     with _lib.device_guard(dev):
         sp = _lib.stream_ptr(dev)
-        _lib.check(lib.cgnn_ingest_count(_lib.ptr(matrices), S, n, int(min_weight is None), k, _lib.ptr(thr),
-                                         _lib.nbytes(thr), _lib.ptr(row_count), _lib.nbytes(row_count),
-                                         _lib.ptr(strength), _lib.nbytes(strength), sp), "cgnn_ingest_count")
+        _lib.check(lib.cgnn_ingest_count(_lib.ptr(matrices), S, n, int(min_weight is None), k, *_buf(thr),
+                                         *_buf(row_count), *_buf(strength), sp), "cgnn_ingest_count")
         torch.cumsum(row_count, 0, dtype=torch.long, out=row_off[1:])
         edge_ptr_dev = row_off[::n].contiguous()          # [S + 1]: every subject's first row
         edge_ptr = edge_ptr_dev.cpu()                     # the one read-back
@@ -1213,8 +1169,7 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
         edge_local = torch.empty(2, E, dtype=torch.long, device=dev)
         edge_weight = torch.empty(E, dtype=torch.float32, device=dev)
         _lib.check(lib.cgnn_ingest_fill(_lib.ptr(matrices), S, n, _lib.ptr(thr), _lib.ptr(row_off), E,
-                                        _lib.ptr(edge_local), _lib.nbytes(edge_local), _lib.ptr(edge_weight),
-                                        _lib.nbytes(edge_weight), sp), "cgnn_ingest_fill")
+                                        *_buf(edge_local), *_buf(edge_weight), sp), "cgnn_ingest_fill")
     if ids is not None:
         x = _measures(matrices, S, n, thr, ids)       # at the thresholds cgnn_ingest_count selected
     return RaggedPackedDataset(x, edge_local, edge_weight, labels.to(dev), edge_ptr, edge_ptr_dev)

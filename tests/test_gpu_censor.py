@@ -412,3 +412,65 @@ def test_censoring_removes_an_artefact_that_no_confound_carries():
     none = torch.zeros_like(md)
     empty = ingest.from_timeseries(dev, y, keep=0.25, sample_mask=none)
     assert int(empty.edge_ptr[-1]) == 0, "no kept frame: graphs without edges"
+
+
+# ---- the masked and the unmasked entry point of a pair check alike ------------------------------------------------------------
+def test_pairs_refuse_alike():
+    """Each pair shares one host body: a bad argument is CGNN_EINVAL from both entry points, before any launch, and
+    the good arguments are CGNN_OK from both (an all-True mask on the masked side)."""
+    lib = _lib.load()
+    S_, T, n, q, qpad = 2, 8, 5, 3, 32
+    gen = torch.Generator().manual_seed(5)
+    ts = torch.randn(S_, T, n, generator=gen).to(DEV)
+    conf = torch.randn(S_, T, q, generator=gen).to(DEV)
+    keep = torch.ones(S_, T, dtype=torch.bool, device=DEV)
+
+    def fresh(*shape, dtype=torch.float32):
+        return torch.full(shape, -7, dtype=dtype, device=DEV)
+
+    stats, mats, alpha = fresh(S_, n, 2), fresh(S_, n, n), fresh(S_, dtype=torch.float64)
+    basis, rank, out = fresh(S_, T, qpad), fresh(S_, dtype=torch.int32), fresh(S_, T, n)
+    work = torch.empty(lib.cgnn_ingest_regress_workspace_bytes(S_, T, n), dtype=torch.uint8, device=DEV)
+    shape = dict(S=S_, T=T, n=n, window=0, stride=0, keep=_lib.ptr(keep), keep_bytes=S_ * T, sp=_lib.stream_ptr())
+
+    def buf(name, t):
+        return {name: _lib.ptr(t), name + "_bytes": _lib.nbytes(t)}
+
+    # name: (the masked entry's arguments in order, those the unmasked one does not take, input, output, what the call
+    # writes, the good arguments)
+    pairs = {
+        "cgnn_ingest_corr": ("ts S T n window stride absolute keep keep_bytes stats stats_bytes out out_bytes sp",
+                             "keep keep_bytes", "ts", "out", (stats, mats),
+                             dict(shape, ts=_lib.ptr(ts), absolute=0, **buf("stats", stats), **buf("out", mats))),
+        "cgnn_ingest_shrinkage": ("ts S T n window stride keep keep_bytes stats stats_bytes matrices matrices_bytes "
+                                  "alpha alpha_bytes sp", "keep keep_bytes stats_bytes matrices_bytes", "ts", "alpha",
+                                  (alpha,),
+                                  dict(shape, ts=_lib.ptr(ts), **buf("stats", stats), **buf("matrices", mats),
+                                       **buf("alpha", alpha))),
+        "cgnn_ingest_confound_basis": ("ts S T n keep keep_bytes basis basis_bytes rank rank_bytes sp",
+                                       "keep keep_bytes", "ts", "basis", (basis, rank),
+                                       dict(shape, ts=_lib.ptr(conf), n=q, **buf("basis", basis), **buf("rank", rank))),
+        "cgnn_ingest_regress": ("ts S T n keep keep_bytes basis basis_bytes qpad work work_bytes out out_bytes sp",
+                                "keep keep_bytes", "ts", "out", (out,),
+                                dict(shape, ts=_lib.ptr(ts), qpad=qpad, **buf("basis", basis), **buf("work", work),
+                                     **buf("out", out))),
+    }
+    for name, (order, masked_only, src, dst, outs, good) in pairs.items():
+        def both(change):
+            args = dict(good, **change)
+            masked = [args[k] for k in order.split()]
+            plain = [args[k] for k in order.split() if k not in masked_only.split()]
+            return getattr(lib, name)(*plain), getattr(lib, name + "_masked")(*masked)
+
+        bad = {"T = 1": dict(T=1), "a null input": {src: None}, "a null output": {dst: None},
+               "a negative byte count": {dst + "_bytes": -1}, "an input offset by one byte": {src: good[src] + 1},
+               "an output one float short": {dst + "_bytes": good[dst + "_bytes"] - 4}}
+        if "window" in order.split():
+            bad.update({"window > T": dict(window=T + 1, stride=1), "stride = 0": dict(window=4, stride=0)})
+        if name == "cgnn_ingest_regress":
+            bad["qpad = 48"] = dict(qpad=48)
+        for what, change in bad.items():
+            assert both(change) == (_lib.CGNN_EINVAL, _lib.CGNN_EINVAL), (name, what)
+        torch.cuda.synchronize()
+        assert all(bool((t == -7).all()) for t in outs), (name, "a refused call wrote")
+        assert both({}) == (_lib.CGNN_OK, _lib.CGNN_OK), name

@@ -90,7 +90,7 @@ def main():
         basis, _ = ingest.confound_basis(conf)
         mbasis, _ = ingest.confound_basis(conf, sample_mask=keep)
         pairs = {"basis": lambda m: ingest.confound_basis(conf, sample_mask=m),
-                 "regress": lambda m: ingest._regress(ts, S, T, n, basis if m is None else mbasis, work, m),
+                 "regress": lambda m: ingest._regress(ts, basis if m is None else mbasis, work, m),
                  "whole": lambda m: ingest.regress_confounds(ts, conf, sample_mask=m, out=work),
                  "centre": lambda m: ingest.filter_timeseries(ts, t_r=args.t_r, sample_mask=m, out=work),
                  "corr": lambda m: ingest.correlation_matrices(ts, sample_mask=m),

@@ -81,7 +81,7 @@ def main():
         basis, rank = ingest.confound_basis(conf)
         qpad = int(basis.shape[2])
         variants = {"basis": lambda: ingest.confound_basis(conf),
-                    "regress": lambda: ingest._regress(ts, S, T, n, basis, work),
+                    "regress": lambda: ingest._regress(ts, basis, work),
                     "whole": lambda: ingest.regress_confounds(ts, conf, out=work),
                     "filter": lambda: ingest.filter_timeseries(ts, out=work, **kw),
                     "cleaned": lambda: ingest.filter_timeseries(ts, confounds=conf, out=work, **kw)}
