@@ -20,19 +20,27 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, bn_stage, ops
-from .structure import BatchStructure
 
 HID = 64
 MAX_ROWS = 384
 MAX_F0 = 16
 
 
-def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
-    """None if the fused path covers this (model, batch); else the reason it does not."""
-    if model.convs[0].linear.weight.shape[0] != HID:
+def widths_ineligible(model) -> Optional[str]:
+    """The part of eligible() that the layer widths decide (Trainer asks it before building a subject cache)."""
+    hid, fin = model.convs[0].linear.weight.shape
+    if hid != HID:
         return f"hidden_dim != {HID}"
-    if model.convs[0].linear.weight.shape[1] > MAX_F0:
+    if fin > MAX_F0:
         return f"in_channels > {MAX_F0}"
+    return None
+
+
+def eligible(model, batch, structure) -> Optional[str]:
+    """None if the fused path covers this (model, batch); else the reason it does not."""
+    why = widths_ineligible(model)
+    if why is not None:
+        return why
     if not structure.block_diagonal:
         return "edges cross graph boundaries"
     if structure.max_nodes_per_graph > MAX_ROWS:
@@ -44,13 +52,15 @@ def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
         # dX0 = A_hat^T (dY0 W0) exists for the factored layer 0 only (cgnn_gcn_l0_bwd_dx, cgnn_gcn_l0_dx)
         return ("node_features require grad: the fused path returns the input gradient from its narrow layer 0 "
                 "only (in_channels <= 8 and num_layers >= 2)")
+    # looser than bn_stage.bn_modules_ok (no type test); merging them would move a GCN with a BatchNorm1d subclass
+    # off the per-tile kernels
     for bn in model.batch_norms:
         if not (bn.affine and bn.track_running_stats) or bn.momentum is None:
             return "BatchNorm without affine/running stats/momentum"
     return None
 
 
-def _tiles_struct(s: BatchStructure, meta, dis: torch.Tensor):
+def _tiles_struct(s, meta, dis: torch.Tensor):
     return s.tiles_struct(meta, dis)
 
 
@@ -76,26 +86,26 @@ def _l0_center(lib, s, x0: torch.Tensor, tiles_ref, stream) -> torch.Tensor:
     gives the same result up to rounding), so it is computed once per (batch, feature tensor)
     and cached on the structure -- one tiny launch at a batch's first use -- or once per DATASET for
     batches assembled from a per-subject structure cache."""
-    cache = getattr(s, "cache", None)
+    cache = s.cache
     if cache is not None and torch.cuda.is_current_stream_capturing():
         # a captured step that assembles another batch of a per-subject structure cache on every replay:
         # ONE set of constants per dataset -- those of the batch the step's eager warm-up ran on, stored
         # below -- instead of a launch per replay (6.4 us of a 0.2 ms step at 512 x 84-ROI).  Any value is
         # correct; eager steps keep their per-batch constants (and with them bit-identity to the
         # per-batch build of the same subjects).
-        const = cache.__dict__.get("_l0_center")
+        const = cache._l0_center
         if const is not None and const[0] == int(x0.shape[1]):
             return const[1]
     key = (x0.data_ptr(), x0._version, tuple(x0.shape))
-    hit = s.__dict__.get("_l0_center")
+    hit = s._l0_center
     if hit is None or hit[0] != key:
         center = torch.empty(8, dtype=torch.float32, device=x0.device)
         _lib.check(lib.cgnn_gcn_l0_center(tiles_ref, _lib.ptr(x0), x0.shape[1], _lib.ptr(center), stream),
                    "cgnn_gcn_l0_center")
         hit = (key, center)
-        s.__dict__["_l0_center"] = hit
-        if cache is not None and not torch.cuda.is_current_stream_capturing() and cache.__dict__.get("_l0_center") is None:
-            cache.__dict__["_l0_center"] = (int(x0.shape[1]), center)
+        s._l0_center = hit
+        if cache is not None and not torch.cuda.is_current_stream_capturing() and cache._l0_center is None:
+            cache._l0_center = (int(x0.shape[1]), center)
     return hit[1]
 
 
@@ -107,7 +117,7 @@ _NO_L0_CACHE = bool(os.environ.get("CGNN_DIAG_NO_L0_CACHE"))
 def _kept(s) -> bool:
     """`s` belongs to a batch that is trained on repeatedly (prepare_batch(reuse=True) -> keep_batch): what
     layer 0 derives from the batch alone -- dis, P0 and the moments of its rows -- is kept with it."""
-    return not _NO_L0_CACHE and isinstance(s, BatchStructure) and bool(s.__dict__.get("_kept"))
+    return not _NO_L0_CACHE and bool(s._kept)
 
 
 def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, stream):
@@ -117,7 +127,7 @@ def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, 
     again (cgnn_gcn_l0_agg) -- except while a stream is capturing, where nothing may be allocated into the
     graph's pool and kept: the step then runs cgnn_gcn_l0_fwd."""
     key = (x0.data_ptr(), x0._version, tuple(x0.shape), None if center is None else center.data_ptr(), sets)
-    hit = s.__dict__.get("_l0_batch")
+    hit = s._l0_batch
     if hit is not None and hit[0] == key:
         return hit[3], hit[4]
     if torch.cuda.is_current_stream_capturing():
@@ -128,16 +138,16 @@ def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, 
         _lib.check(lib.cgnn_gcn_l0_agg(tiles_ref, _lib.ptr(x0), x0.shape[1], _lib.ptr(center), _lib.ptr(p0),
                                        _lib.ptr(moments), _lib.nbytes(moments), stream), "cgnn_gcn_l0_agg")
     # (x0 and the centre are held so that their addresses stay theirs while the entry lives)
-    s.__dict__["_l0_batch"] = (key, x0, center, p0, moments)
+    s._l0_batch = (key, x0, center, p0, moments)
     return p0, moments
 
 
 def keep_batch(model, s, x0: torch.Tensor) -> None:
     """prepare_batch(reuse=True): mark the structure the encoder will run on as kept and, when the narrow
     layer 0 applies, fill its batch constants now -- eagerly, outside any capture."""
-    if not isinstance(s, BatchStructure) or s.num_nodes == 0:
+    if not s.has_csr or s.num_nodes == 0:     # (a cached structure lives for one shuffle)
         return
-    s.__dict__["_kept"] = True
+    s._kept = True
     if _NO_L0_CACHE or x0.requires_grad or not x0.is_cuda:
         return
     lib = _lib.load()
@@ -205,7 +215,7 @@ class FusedGCNEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, meta, *params):
         lib = _lib.load()
-        s: BatchStructure = meta["structure"]
+        s = meta["structure"]
         bns_mod = meta["batch_norms"]
         training: bool = meta["training"]
         p: float = meta["dropout"] if training else 0.0
@@ -217,7 +227,7 @@ class FusedGCNEncode(torch.autograd.Function):
         grid = lib.cgnn_fused_grid()
         fmeta = s.fused_meta(MAX_ROWS, grid)      # static per batch (cached on the structure)
         # the normalisation itself: every forward -- on a kept batch a batch constant, like the CSR
-        dis = s.gcn_dis(fmeta, fresh=True) if (_NO_L0_CACHE and isinstance(s, BatchStructure)) else s.gcn_dis(fmeta)
+        dis = s.gcn_dis(fmeta, fresh=_NO_L0_CACHE)
         tiles = _tiles_struct(s, fmeta, dis)
         tp = ctypes.byref(tiles)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -536,5 +546,5 @@ class FusedGCNEncode(torch.autograd.Function):
         return (dx0, None, *ops.undelivered(grads, dst))
 
 
-def encode(model, batch, structure: BatchStructure) -> torch.Tensor:
+def encode(model, batch, structure) -> torch.Tensor:
     return bn_stage.encode(FusedGCNEncode, model, batch, structure)

@@ -79,12 +79,10 @@ def _operator(s: BatchStructure, coef, selfc, transposed: bool):
 
 def dense_operators(s: BatchStructure):
     """(Mf, Mb): normalised operator and its transpose, built once per batch structure."""
-    cached = s.__dict__.get("_dense_f16")
-    if cached is None:
+    if s._dense_f16 is None:
         norm = s.gcn_norm()
-        cached = (_operator(s, norm.coef_dst, norm.selfc, False), _operator(s, norm.coef_src, norm.selfc, True))
-        s.__dict__["_dense_f16"] = cached
-    return cached
+        s._dense_f16 = (_operator(s, norm.coef_dst, norm.selfc, False), _operator(s, norm.coef_src, norm.selfc, True))
+    return s._dense_f16
 
 
 P0_COLS = 64             # layer 0's input features ride in one 64-column half panel

@@ -28,19 +28,25 @@ import torch
 
 from . import _lib, ops
 from .bn_stage import PAD_K, PAD_MIN_ROWS, BnStage, encode as _encode, f32, ineligible, linear_fwd_stats
-from .structure import TILED_MAX_ROWS, BatchStructure
+from .structure import TILED_MAX_ROWS
 
 
-def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
-    """None if this path covers (model, batch); else the reason it does not."""
-    hid = model.convs[0].linear.weight.shape[0]
+def widths_ineligible(model) -> Optional[str]:
+    """The part of eligible() that the layer widths decide."""
+    hid, fin = model.convs[0].linear.weight.shape
     if hid % 64 or not bool(_lib.load().cgnn_bn_act_width_ok(hid)):
         return "hidden_dim is not 64, 128, 256, ..."
-    if model.convs[0].linear.weight.shape[1] >= hid:
+    if fin >= hid:
         return "input features are not narrower than hidden_dim"
-    if not structure.tiled_ok(hid) and not isinstance(structure, BatchStructure):
-        return "graphs do not fit an LDS tile and the structure has no CSR form"
-    return ineligible(batch, structure, model)
+    return None
+
+
+def eligible(model, batch, structure) -> Optional[str]:
+    """None if this path covers (model, batch); else the reason it does not."""
+    why = widths_ineligible(model)
+    if why is None and not structure.has_csr and not structure.tiled_ok(model.convs[0].linear.weight.shape[0]):
+        why = "graphs do not fit an LDS tile and the structure has no CSR form"
+    return why or ineligible(batch, structure, model)
 
 
 class _Saved:
@@ -53,7 +59,7 @@ class GcnWideEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, cfg, *params):
         lib = _lib.load()
-        s: BatchStructure = cfg["structure"]
+        s = cfg["structure"]
         L = len(params) // 4
         dev = x0.device
         x = x0.contiguous()
@@ -141,5 +147,5 @@ class GcnWideEncode(torch.autograd.Function):
         return (None, None, *grads)
 
 
-def encode(model, batch, structure: BatchStructure) -> torch.Tensor:
+def encode(model, batch, structure) -> torch.Tensor:
     return _encode(GcnWideEncode, model, batch, structure)

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, encoder_choice, fused, gcn_half_path, ops
 from .graph import ConnectomeBatch
 from .structure import BatchStructure, GcnNorm, SageNorm, _require_device
 
@@ -35,7 +35,6 @@ _TILE_ROWS = 384
 
 
 def _grid() -> int:
-    from . import _lib
     return int(_lib.load().cgnn_fused_grid())
 
 
@@ -69,7 +68,7 @@ class GCNLayer(nn.Module):
         if norm is None:
             norm = structure.gcn_norm()
         s = structure
-        bf, bb = s.band_ops("gcn", norm) if hasattr(s, "band_ops") else (None, None)
+        bf, bb = s.band_ops("gcn", norm) if s.has_csr else (None, None)
         fwd = (s.rowptr_dst, s.col_dst, norm.coef_dst, norm.selfc, None, bf)
         bwd = (s.rowptr_src, s.col_src, norm.coef_src, bb)
         # edge_weight.requires_grad: every aggregate also returns its dL/dw (ops.edge_weight_grad)
@@ -108,7 +107,7 @@ class SAGELayer(nn.Module):
             meta = s.fused_meta(_TILE_ROWS, _grid(), 0.0)
             agg = ops.aggregate_tiled(x, None, s, meta, post=norm.den, post_div=True, **eg)
         else:
-            bf, bb = s.band_ops("sage", norm) if hasattr(s, "band_ops") else (None, None)
+            bf, bb = s.band_ops("sage", norm) if s.has_csr else (None, None)
             agg = ops.aggregate(x, None, (s.rowptr_dst, s.col_dst, norm.w_dst, None, norm.den, bf),
                                 (s.rowptr_src, s.col_src, norm.coef_src_bwd, bb), **eg)
         # the [x || agg] concat is never materialised: two K-panels of one GEMM, ReLU epilogue
@@ -123,6 +122,7 @@ def _head(hidden_dim: int, num_classes: int, dropout: float) -> nn.Sequential:
 class _ConnectomeModel(nn.Module):
     _layer_cls = None
     _relu_after_bn = False
+    _family = None                    # "gcn" | "sage": whose encoders (encoder_choice.py) and ELL
 
     def __init__(self, in_channels: int, hidden_dim: int = 64, num_classes: int = 2,
                  num_layers: int = 3, dropout: float = 0.3, *, impl: str = "auto", storage: str = "fp32"):
@@ -156,11 +156,13 @@ class _ConnectomeModel(nn.Module):
         self.batch_norms = nn.ModuleList(nn.BatchNorm1d(hidden_dim) for _ in range(num_layers))
         self.classifier = _head(hidden_dim, num_classes, dropout)
 
-    def _norm(self, structure: BatchStructure):
-        raise NotImplementedError
+    def _norm(self, structure):
+        return structure.gcn_norm() if self._family == "gcn" else structure.sage_norm()
 
-    def _post(self, x):
-        raise NotImplementedError
+    def _rng_word(self, i: int) -> Optional[int]:
+        """Address of a captured step's dropout word `i` (the layers', then the classifier's); None when eager."""
+        rng = self.rng_device_state
+        return None if rng is None else rng.data_ptr() + 4 * i
 
     def _dropout_record(self):
         """Fresh record dict for this forward when ``record_dropout`` is on, else None."""
@@ -192,15 +194,17 @@ class _ConnectomeModel(nn.Module):
         """Graph embeddings [B, hidden] (reference models.py:203-211 / 256-262)."""
         self._validate(batch)
         s = batch.structure()
-        if self._agreed_fused(batch, s):
-            self.impl_used = "fused"
-            return self._fused_encode(batch, s)
-        self.impl_used = "layered"
+        choice = encoder_choice.agreed(self, batch, s, encoder_choice.choose(self, batch, s))
+        # the records of what ran: written here only, read back by nothing in the package
+        self.impl_used = "layered" if choice.kind is None else "fused"
+        if choice.record is not None:
+            self._fused_kind = choice.record
+        if choice.kind is not None:
+            return encoder_choice.ENCODERS[choice.kind].encode(self, batch, s)
         norm = self._norm(s)                  # once per forward pass, shared by all layers
         x = batch.node_features
-        rng = getattr(self, "rng_device_state", None)     # set by graphed.GraphedTrainStep
+        rng = self.rng_device_state           # set by graphed.GraphedTrainStep
         if rng is not None and self.training and self.dropout > 0:
-            from . import _lib
             _lib.check(_lib.load().cgnn_rng_advance(_lib.ptr(rng), len(self.convs) + 1,
                                                     _lib.stream_ptr()), "cgnn_rng_advance")
         rec = self._dropout_record()
@@ -209,9 +213,9 @@ class _ConnectomeModel(nn.Module):
             if ops.bn_act_drop_supported(bn, x.shape[1]):
                 # BatchNorm (+ReLU) + dropout in two streaming HIP passes each way
                 x = ops.bn_act_drop(x, bn, self._relu_after_bn, self.dropout, self.training,
-                                    None if rng is None else rng.data_ptr() + 4 * li, rec)
+                                    self._rng_word(li), rec)
             else:                     # SyncBatchNorm / odd widths: torch ops
-                x = self._post(bn(x))
+                x = F.relu(bn(x)) if self._relu_after_bn else bn(x)
                 x = F.dropout(x, p=self.dropout, training=self.training)
         return ops.pool_mean(x, s.gptr, batch.num_graphs)
 
@@ -223,20 +227,16 @@ class _ConnectomeModel(nn.Module):
                 and ops.head_loss_supported(self.classifier)):
             return None
         pooled = self.encode(batch)
-        rng = getattr(self, "rng_device_state", None)
-        word = None if rng is None else rng.data_ptr() + 4 * len(self.convs)
         rec = self.last_dropout if self.record_dropout else None
-        return ops.head_loss(self.classifier, pooled, batch.labels, True, word, rec)
+        return ops.head_loss(self.classifier, pooled, batch.labels, True, self._rng_word(len(self.convs)), rec)
 
     def forward(self, batch: ConnectomeBatch) -> torch.Tensor:
         """Class logits [B, num_classes]."""
         pooled = self.encode(batch)
         if ops.head_supported(self.classifier):
             # Linear -> ReLU -> Dropout -> Linear on [B, hidden] in one HIP kernel each way
-            rng = getattr(self, "rng_device_state", None)
-            word = None if rng is None else rng.data_ptr() + 4 * len(self.convs)
             rec = self.last_dropout if (self.record_dropout and self.training) else None
-            return ops.head(self.classifier, pooled, self.training, word, rec)
+            return ops.head(self.classifier, pooled, self.training, self._rng_word(len(self.convs)), rec)
         if self.record_dropout and self.training and self.last_dropout is not None \
                 and self.dropout > 0 and len(self.classifier) == 4:
             # parity hook for heads outside head.hip's widths (torch modules): same record format
@@ -252,82 +252,35 @@ class _ConnectomeModel(nn.Module):
         blocked-ELL of the fused path) now -- these builds read sizes back to the host, so they
         must not happen inside a HIP-graph capture or a timed region.  reuse=True says the batch
         will be trained on repeatedly (cached batches, captured steps): structure work that only
-        pays when amortised is then done too (the per-tile GCN path's degree-ordered twin)."""
+        pays when amortised is then done too -- the one-node encoders over LDS tiles run on the batch's
+        degree-ordered twin (structure.degree_ordered_twin: 19 % -> 3 % of blocked-ELL padding on small-world
+        connectomes) and the per-tile GCN path keeps its per-batch constants (fused.keep_batch)."""
         s = batch.structure()
+        hid = self.convs[-1].linear.weight.shape[0]
+        self_loop = 1.0 if self._family == "gcn" else 0.0      # GCN's ELL carries it, GraphSAGE's does not
+        # (fp16 storage: no twin, nothing kept; whether it covers the batch is encode's to say)
+        kind = None if self.storage == "fp16" else encoder_choice.choose(self, batch, s).kind
         if reuse:
-            self._prepare_reused(batch, s)
-            twin = getattr(s, "__dict__", {}).get("_degree_twin")
-            if twin is not None:
-                self._keep_batch(twin, twin.permuted_features(batch.node_features))
-                return                                  # the encoder runs on the twin's metadata
+            # (no twin under cross-rank BatchNorm, where the ranks agree on paths, or for cached structures)
+            if kind is not None and s.has_csr and s.tiled_ok(hid) \
+                    and not any(isinstance(bn, nn.SyncBatchNorm) for bn in self.batch_norms):
+                s.degree_ordered_twin().fused_meta(_TILE_ROWS, _grid(), self_loop)
+            twin = s._degree_twin
+            if twin is not None:                            # the encoder runs on the twin's metadata
+                xt = twin.permuted_features(batch.node_features)
+                if kind == "tile":
+                    fused.keep_batch(self, twin, xt)
+                return
         if self.storage == "fp16":
-            from . import gcn_half_path
             gcn_half_path.dense_operators(s)
             return
-        hid = self.convs[-1].linear.weight.shape[0]
         if s.tiled_ok(hid):
-            # GCN's ELL carries the self-loop (weight 1), GraphSAGE's does not (weight 0)
-            s.fused_meta(_TILE_ROWS, _grid(), 1.0 if self._relu_after_bn else 0.0)
-        elif hasattr(s, "band_ops"):
+            s.fused_meta(_TILE_ROWS, _grid(), self_loop)
+        elif s.has_csr:
             # large graphs: the dense fragments of the operator as matrix-core operands (band_aggregate.hip)
-            s.band_ops("gcn" if self._relu_after_bn else "sage", self._norm(s))
-        if self._try_fused(batch, s) and reuse:
-            self._keep_batch(s, batch.node_features)
-
-    def _try_fused(self, batch, structure) -> bool:
-        return False
-
-    def _keep_batch(self, structure, x0) -> None:
-        """prepare_batch(reuse=True): `structure` (the twin when there is one) and the node features in its
-        order are what the one-node encoder will run on, again and again; an encoder that keeps per-batch
-        constants fills them here (the per-tile GCN path: fused.keep_batch)."""
-
-    def _prepare_reused(self, batch, structure) -> None:
-        """prepare_batch(reuse=True): the one-node encoders over LDS tiles (per-tile GCN, wide GCN,
-        GraphSAGE) run on the batch's degree-ordered twin (structure.degree_ordered_twin: 19 % -> 3 % of
-        blocked-ELL padding on small-world connectomes).  Not under cross-rank BatchNorm (the ranks
-        agree on paths there), not for cached subject structures, not for the dense fp16 operator."""
-        from .structure import BatchStructure
-        if not isinstance(structure, BatchStructure) or self.impl == "layered" or self.storage == "fp16" \
-                or any(isinstance(bn, nn.SyncBatchNorm) for bn in self.batch_norms) \
-                or not self._try_fused(batch, structure) \
-                or not structure.tiled_ok(self.convs[-1].linear.weight.shape[0]):
-            return
-        twin = structure.degree_ordered_twin()
-        twin.fused_meta(_TILE_ROWS, _grid(), 1.0 if self._relu_after_bn else 0.0)
-        twin.permuted_features(batch.node_features)
-
-    def _agreed_fused(self, batch, structure) -> bool:
-        """``_try_fused`` -- and, while training with SyncBatchNorm across ranks, the same answer
-        on every rank: the choice depends on the local shard (graph sizes, block-diagonality),
-        and the fused encoders exchange their BatchNorm sums with a different collective than
-        torch's SyncBatchNorm on the layered path, so mixed paths would hang.  One tiny
-        all-reduce(MIN) per batch, cached on the batch's structure."""
-        ok = self._try_fused(batch, structure)
-        import torch.distributed as dist
-        if not (self.training and dist.is_initialized() and dist.get_world_size() > 1
-                and any(isinstance(bn, nn.SyncBatchNorm) for bn in self.batch_norms)):
-            return ok
-        key = (type(self).__name__, self.impl, id(self))
-        cache = structure.__dict__.setdefault("_path_agreement", {})
-        if key not in cache:
-            from . import dist as cdist
-            code = 0 if not ok else (2 if getattr(self, "_fused_kind", "tile") == "tile" else 1)
-            cache[key] = cdist.agree_min(code, batch.node_features.device)
-        agreed = cache[key]
-        if ok and agreed == 0:
-            return False
-        if ok and agreed == 1:
-            self._fused_kind = "wide"
-        return ok
-
-    def _fused_encode(self, batch, structure) -> torch.Tensor:
-        raise NotImplementedError
-
-    def _decide(self, why: Optional[str]) -> bool:
-        if why is not None and self.impl == "fused":
-            raise RuntimeError(f"impl='fused' requested but not applicable: {why}")
-        return why is None
+            s.band_ops(self._family, self._norm(s))
+        if reuse and kind == "tile":
+            fused.keep_batch(self, s, batch.node_features)
 
 
 class GCNConnectome(_ConnectomeModel):
@@ -335,62 +288,11 @@ class GCNConnectome(_ConnectomeModel):
     (reference models.py:159-216)."""
     _layer_cls = GCNLayer
     _relu_after_bn = True
+    _family = "gcn"
 
-    def _norm(self, structure):
-        return structure.gcn_norm()
-
-    def _post(self, x):
-        return F.relu(x)
-
-    def _try_fused(self, batch, structure) -> bool:
-        """Fused per-tile kernels (fused.py) when the shape is covered: hidden 64, <= 16 input
-        features, graphs of <= 384 nodes, block-diagonal edges; else the one-node wide encoder
-        (gcn_wide_path.py) for hidden 64/128/256 on such graphs; else the op-by-op path."""
-        if self.storage == "fp16":
-            from . import gcn_half_path
-            why = gcn_half_path.eligible(self, batch, structure)
-            if why is not None:
-                raise RuntimeError(f"storage='fp16' requested but not applicable: {why}")
-            self._fused_kind = "half"
-            return True
-        if self.impl == "layered":
-            return False
-        from . import fused, gcn_wide_path
-        why = fused.eligible(self, batch, structure)
-        self._fused_kind = "tile"
-        if why is not None and gcn_wide_path.eligible(self, batch, structure) is None:
-            self._fused_kind, why = "wide", None
-        return self._decide(why)
-
-    def _keep_batch(self, structure, x0) -> None:
-        if getattr(self, "_fused_kind", None) == "tile" and self.impl != "layered" and self.storage != "fp16":
-            from . import fused
-            fused.keep_batch(self, structure, x0)
-
-    def _fused_encode(self, batch, structure):
-        from . import fused, gcn_half_path, gcn_wide_path
-        path = {"tile": fused, "wide": gcn_wide_path, "half": gcn_half_path}[self._fused_kind]
-        return path.encode(self, batch, structure)
 
 class GraphSAGEConnectome(_ConnectomeModel):
     """conv (ReLU inside) -> BatchNorm1d -> dropout per layer -- no ReLU after BN
     (reference models.py:219-266)."""
     _layer_cls = SAGELayer
-
-    def _norm(self, structure):
-        return structure.sage_norm()
-
-    def _post(self, x):
-        return x
-
-    def _try_fused(self, batch, structure) -> bool:
-        """One-node encoder with hand-written backward (sage_path.py) when hidden is a multiple
-        of 64 and every graph fits an LDS tile (<= 384 nodes, block-diagonal edges)."""
-        if self.impl == "layered":
-            return False
-        from . import sage_path
-        return self._decide(sage_path.eligible(self, batch, structure))
-
-    def _fused_encode(self, batch, structure):
-        from . import sage_path
-        return sage_path.encode(self, batch, structure)
+    _family = "sage"

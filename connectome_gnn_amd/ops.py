@@ -208,13 +208,12 @@ def edge_weight_grad(kind: str, structure, norm, dy, xp, y=None) -> torch.Tensor
 
 
 def _edge_grad_check(edge_weight, edge_grad):
-    from .structure import BatchStructure
     if edge_weight is None:
         return
     if edge_grad is None or edge_grad[0] not in ("gcn", "sage"):
         raise ValueError("edge_weight needs edge_grad=(kind 'gcn' | 'sage', structure, norm)")
     s = edge_grad[1]
-    if not isinstance(s, BatchStructure):
+    if not s.has_csr:
         raise RuntimeError("edge-weight gradients need the batch's own CSR structure (BatchStructure), got "
                            f"{type(s).__name__}")
     if edge_weight.numel() != s.num_edges:

@@ -25,21 +25,28 @@ import torch
 
 from . import _lib, ops
 from .bn_stage import PAD_K, PAD_MIN_ROWS, BnStage, encode as _encode, f32, ineligible, linear_fwd_stats
-from .structure import TILED_MAX_ROWS, BatchStructure
+from .structure import TILED_MAX_ROWS
 
 
-def eligible(model, batch, structure: BatchStructure) -> Optional[str]:
-    """None if this path covers (model, batch); else the reason it does not."""
+def widths_ineligible(model, tiled: bool = True) -> Optional[str]:
+    """The part of eligible() that the layer widths decide.  tiled=False: off the tiled aggregate -- and what
+    Trainer asks before building a subject cache, which it does for these widths only."""
     hid = model.convs[0].linear.weight.shape[0]
     if hid % 64 or not bool(_lib.load().cgnn_bn_act_width_ok(hid)):
         return "hidden_dim is not 64, 128, 256, ..."
-    if not structure.tiled_ok(hid) and not isinstance(structure, BatchStructure):
-        return "graphs do not fit an LDS tile and the structure has no CSR form"
-    if not structure.tiled_ok(hid) and hid not in (64, 128, 256):
+    if not tiled and hid not in (64, 128, 256):
         # off the tiled aggregate the backward adds dX1 inside the gather kernel (ops.aggregate_raw(yadd=...)),
         # which covers widths 64 / 128 / 256 only: wider layers on large graphs take the layered path
         return "graphs do not fit an LDS tile and hidden_dim is not 64, 128 or 256"
-    return ineligible(batch, structure, model)
+    return None
+
+
+def eligible(model, batch, structure) -> Optional[str]:
+    """None if this path covers (model, batch); else the reason it does not."""
+    tiled = structure.tiled_ok(model.convs[0].linear.weight.shape[0])
+    if not tiled and not structure.has_csr:
+        return widths_ineligible(model) or "graphs do not fit an LDS tile and the structure has no CSR form"
+    return widths_ineligible(model, tiled) or ineligible(batch, structure, model)
 
 
 class _Saved:
@@ -58,11 +65,11 @@ def _agg_narrow_tiled(s, ell, norm, x, out=None):
     return out
 
 
-def _agg_fwd(s: BatchStructure, ell, norm, x, band=None):
+def _agg_fwd(s, ell, norm, x, band=None):
     """weighted mean of in-neighbours, models.py:146-149"""
     if ell is not None and s.tiled_ok(x.shape[1]):
         return ops.aggregate_tiled_raw(s, ell, ops.AGG_POST_DIV, x, None, norm.den, None)
-    if getattr(s, "cached_subjects", False):
+    if not s.has_csr:
         return _agg_narrow_tiled(s, ell, norm, x)
     return ops.aggregate_raw(s.rowptr_dst, s.col_dst, norm.w_dst, None, norm.den, None, x, band=band)
 
@@ -73,7 +80,7 @@ class SageEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, cfg, *params):
         lib = _lib.load()
-        s: BatchStructure = cfg["structure"]
+        s = cfg["structure"]
         L = len(params) // 4
         dev = x0.device
         x = x0.contiguous()
@@ -114,7 +121,7 @@ class SageEncode(torch.autograd.Function):
                     # 32-wide panels so that the tall weight-stationary GEMMs apply (K = 10 would
                     # otherwise run the per-tile kernels at a few % of the matrix-core rate)
                     xa = torch.nn.functional.pad(x, (0, PAD_K - fin))        # one pass: [x0 | 0]
-                    if getattr(s, "cached_subjects", False):
+                    if not s.has_csr:
                         agg = _agg_narrow_tiled(s, sv.ell, sv.norm, x, out=xa[:, fin:2 * fin])
                     else:
                         agg = ops.aggregate_raw(s.rowptr_dst, s.col_dst, sv.norm.w_dst, None, sv.norm.den,
@@ -174,5 +181,5 @@ class SageEncode(torch.autograd.Function):
         return (None, None, *grads)
 
 
-def encode(model, batch, structure: BatchStructure) -> torch.Tensor:
+def encode(model, batch, structure) -> torch.Tensor:
     return _encode(SageEncode, model, batch, structure)

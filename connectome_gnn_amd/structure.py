@@ -51,7 +51,7 @@ def edge_grad_requested(structure) -> bool:
     for the layered path, whose aggregates return dL/dw (ops.edge_weight_grad).  Read from the weights the
     structure was built from (the batch's own tensor, or its contiguous copy in the autograd graph), so a
     batch whose COO fields are assembled lazily is not made to assemble them."""
-    ew = getattr(structure, "__dict__", {}).get("_edge_weight")
+    ew = structure._edge_weight
     return ew is not None and ew.requires_grad and torch.is_grad_enabled()
 
 
@@ -60,7 +60,7 @@ def twin_view(structure, x: torch.Tensor):
     one has been prepared (``BatchStructure.degree_ordered_twin`` via ``model.prepare_batch(batch,
     reuse=True)``), else the inputs and None.  The one-node encoders call this on entry: all their
     per-node arrays are internal, so they run on the twin unchanged."""
-    twin = getattr(structure, "__dict__", {}).get("_degree_twin")
+    twin = structure._degree_twin
     if twin is None:
         return structure, x, None
     if x.requires_grad and torch.is_grad_enabled():
@@ -111,7 +111,13 @@ class FusedMeta:
 
 
 class BatchStructure:
-    """dst-/src-sorted CSR (+ per-graph node ranges) of one batch, on its device."""
+    """dst-/src-sorted CSR (+ per-graph node ranges) of one batch, on its device.  Generic code asks either
+    structure class (this, structure_cache.CachedStructure) for has_csr, cache, _edge_weight, _degree_twin, _kept."""
+    has_csr = True    # CSR arrays, band_ops, gcn_norm and a degree-ordered twin exist
+    cache = None      # the SubjectStructureCache of a CachedStructure
+    # (two slots on the class: test_gpu_l0_cache.py reads "not in __dict__" as "never filled")
+    _dis = None       # gcn_dis, kept batch
+    _l0_batch = None  # fused._l0_batch_constants
 
     def __init__(self):
         self.num_nodes = 0
@@ -129,6 +135,17 @@ class BatchStructure:
         self._edge_weight = None
         self._ptr_host = None
         self._tiles = {}
+        # per-batch state, empty until the named owner fills it
+        self._eptr_host = None     # build
+        self.perm = None           # degree_ordered_twin, on the twin
+        self._is_twin = False      # degree_ordered_twin, on the twin
+        self._degree_twin = None   # degree_ordered_twin
+        self._xperm = None         # permuted_features
+        self._band_ops = {}        # band_ops
+        self._kept = None          # fused.keep_batch
+        self._l0_center = None     # fused._l0_center
+        self._dense_f16 = None     # gcn_half_path.dense_operators
+        self._path_agreement = {}  # encoder_choice.agreed
 
     @staticmethod
     def build(batch, force_generic: bool = False) -> "BatchStructure":
@@ -163,7 +180,7 @@ class BatchStructure:
                             else torch.zeros(nn_, dtype=torch.int32, device=dev))
             f = None
             eptr = getattr(batch, "_eptr", None)
-            s.__dict__["_eptr_host"] = eptr
+            s._eptr_host = eptr
             if (not force_generic and eptr is not None and eptr.numel() == batch.num_graphs + 1
                     and int(eptr[-1]) == ne and batch.num_graphs > 0):
                 # COO grouped by graph: whole graphs are built in LDS by one workgroup each
@@ -209,7 +226,7 @@ class BatchStructure:
         (node features gathered through ``perm`` on entry) while the batch's public arrays stay as
         they are.  Built once per batch on request (`model.prepare_batch(batch, reuse=True)`): it
         costs a second CSR / blocked-ELL build, which pays for batches that are trained on repeatedly."""
-        twin = self.__dict__.get("_degree_twin")
+        twin = self._degree_twin
         if twin is not None:
             return twin
         ei = self._edge_index
@@ -232,20 +249,20 @@ class BatchStructure:
         shim.num_nodes, shim.num_graphs = nn_, self.num_graphs
         shim.batch = gid
         shim.ptr = self.gptr.to(torch.long)
-        shim._eptr = self.__dict__.get("_eptr_host")
+        shim._eptr = self._eptr_host
         twin = BatchStructure.build(shim)
         twin.perm = perm
-        twin.__dict__["_is_twin"] = True
-        self.__dict__["_degree_twin"] = twin
+        twin._is_twin = True
+        self._degree_twin = twin
         return twin
 
     def permuted_features(self, x: torch.Tensor) -> torch.Tensor:
         """Node features in this (twin) structure's node order; cached per feature tensor version."""
         key = (x.data_ptr(), x._version, tuple(x.shape))
-        hit = self.__dict__.get("_xperm")
+        hit = self._xperm
         if hit is None or hit[0] != key:
             hit = (key, x.detach().index_select(0, self.perm).contiguous())
-            self.__dict__["_xperm"] = hit
+            self._xperm = hit
         return hit[1]
 
     # -- dense fragments of the operators of large graphs (band_aggregate.hip) -----------------
@@ -253,7 +270,7 @@ class BatchStructure:
         """(fwd, bwd) `(self, ops.BandOp)` pairs -- or (None, None) -- of the GCN / GraphSAGE operator:
         built once per batch from the first normalisation computed for it (the coefficients are a
         function of the batch's edge weights only), like the CSR and the blocked-ELL."""
-        hit = self.__dict__.setdefault("_band_ops", {})
+        hit = self._band_ops
         if kind not in hit:
             from . import ops
             if kind == "gcn":
@@ -406,9 +423,9 @@ class BatchStructure:
         structure marked kept (``model.prepare_batch(batch, reuse=True)``), where it is a batch constant like
         the CSR: a function of ``meta.w_src``, which is itself built once per batch.  Computed at the first
         request outside a stream capture and returned from then on; fresh=True recomputes regardless."""
-        kept = not fresh and self.__dict__.get("_kept")
+        kept = not fresh and self._kept
         if kept:
-            hit = self.__dict__.get("_dis")
+            hit = self._dis
             if hit is not None and hit[0] is meta:
                 return hit[1]
         lib = _lib.load()
@@ -419,5 +436,5 @@ class BatchStructure:
                                         self.num_nodes, _lib.ptr(dis), _lib.stream_ptr()),
                        "cgnn_gcn_dis")
         if kept and not torch.cuda.is_current_stream_capturing():
-            self.__dict__["_dis"] = (meta, dis)       # (never a tensor from a graph's pool)
+            self._dis = (meta, dis)       # (never a tensor from a graph's pool)
         return dis

@@ -39,7 +39,7 @@ import torch
 
 from . import _lib
 from .graph import ConnectomeBatch
-from .structure import FusedMeta
+from .structure import BatchStructure, FusedMeta
 
 MAX_ROWS = 384
 
@@ -68,6 +68,7 @@ class SubjectStructureCache:
         self.nb = (n + 15) // 16                                     # 16-row blocks per graph
         self._fam = {}
         self._static = {}
+        self._l0_center = None       # fused._l0_center: a captured step's constants
         self.family("gcn")
 
     def family(self, kind: str) -> _Family:
@@ -137,12 +138,14 @@ class CachedStructure:
     assembled from the cache.  `family(kind)` -- (block offsets dst, src, per-node normaliser) of the
     batch -- comes from the batch's own single assembly launch when its owner provides one
     (ResidentBatch), else from three gathers."""
-    cached_subjects = True
+    has_csr = False                               # (what generic code reads on either structure class)
+    _edge_weight = _degree_twin = _kept = None    # never filled here
 
     def __init__(self, cache: SubjectStructureCache, ids, b: int, assembled=None):
         """ids: the subject ids on the cache's device, or a callable that returns them.
         assembled(kind): callable returning (blk_off_dst, blk_off_src, norm) of the batch."""
         self.cache, self._ids_src, self._assembled = cache, ids, assembled
+        self._l0_center, self._path_agreement = None, {}      # as on a BatchStructure
         self.num_graphs, self.num_nodes = b, b * cache.n
         self.max_nodes_per_graph = cache.n
         self.block_diagonal = True
@@ -177,7 +180,7 @@ class CachedStructure:
             raise ValueError("cached structure: tiles of 384 rows, GCN (self-loop 1) or GraphSAGE (none) metadata")
         return self._family(kind)[0]
 
-    def gcn_dis(self, meta: FusedMeta) -> torch.Tensor:
+    def gcn_dis(self, meta: FusedMeta, fresh: bool = False) -> torch.Tensor:
         """Per-subject `dis`, gathered (a function of the subject's edge weights only)."""
         return self._family("gcn")[1]
 
@@ -187,16 +190,7 @@ class CachedStructure:
         from .structure import SageNorm
         return SageNorm(self._family("sage")[1], None, None)
 
-    def tiles_struct(self, meta: FusedMeta, dis: Optional[torch.Tensor] = None):
-        t = _lib.CgnnTiles()
-        t.num_nodes = self.num_nodes
-        t.num_tiles = self.num_graphs
-        t.max_tile_rows = meta.max_tile_rows
-        t.tile_ptr, t.tile_blk = meta.tile_ptr.data_ptr(), meta.tile_blk.data_ptr()
-        t.blk_off_dst, t.ent_dst = meta.blk_off_dst.data_ptr(), meta.ent_dst.data_ptr()
-        t.blk_off_src, t.ent_src = meta.blk_off_src.data_ptr(), meta.ent_src.data_ptr()
-        t.dis = dis.data_ptr() if dis is not None else None
-        return t
+    tiles_struct = BatchStructure.tiles_struct       # (one tile per graph: tile_ptr has num_graphs + 1 entries)
 
     def tiled_ok(self, width: int) -> bool:
         return width % 64 == 0 and self.num_nodes > 0

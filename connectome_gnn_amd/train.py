@@ -204,7 +204,7 @@ class Trainer:
     def _subject_cache_serves(self, ds, batch_size: int) -> bool:
         """The per-subject structure cache (structure_cache.py) carries what the per-tile GCN encoder and the
         GraphSAGE encoder index with, and nothing else (no CSR)."""
-        from . import bn_stage, fused
+        from . import bn_stage, fused, sage_path
         from .models import GCNConnectome, GraphSAGEConnectome
         from .structure_cache import MAX_ROWS
         m = self.model
@@ -212,11 +212,10 @@ class Trainer:
         if not (0 < n <= MAX_ROWS) or getattr(m, "impl", None) == "layered" or getattr(m, "storage", "fp32") != "fp32" \
                 or any(isinstance(mod, nn.SyncBatchNorm) for mod in m.modules()) or not bn_stage.bn_modules_ok(m):
             return False
-        hid, fin = m.convs[0].linear.weight.shape
-        if type(m) is GCNConnectome:                       # the per-tile kernels (fused.eligible)
-            return hid == fused.HID and fin <= fused.MAX_F0
-        if type(m) is GraphSAGEConnectome:                 # sage_path.eligible over LDS tiles
-            return hid in (64, 128, 256)
+        if type(m) is GCNConnectome:                       # the per-tile kernels
+            return fused.widths_ineligible(m) is None
+        if type(m) is GraphSAGEConnectome:                 # narrower than sage_path.eligible over LDS tiles: 64 / 128 / 256
+            return sage_path.widths_ineligible(m, tiled=False) is None
         return False
 
     def _make_capturable(self) -> bool:

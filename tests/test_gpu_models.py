@@ -1194,6 +1194,38 @@ def test_degree_ordered_twin_is_the_same_model_on_ragged_batches():
         assert float((g1 - g0).abs().max()) <= 2e-5 * float(g0.abs().max()) + 2e-6, k
 
 
+def test_encoder_choice_is_per_call_not_per_model():
+    """One GCN (hidden 64, 4 input features, 2 layers, eval) prepared for two kept batches -- A on the per-tile
+    kernels, B (a 400-node graph) on the wide encoder -- and run on A, B, A: each call runs and records its own
+    encoder, and A's logits are bit-equal both times and to those of a model that only ever saw A."""
+    import connectome_gnn_amd as C
+
+    def cut(graphs):                                   # the generator makes 5 features: keep 4
+        return [C.ConnectomeGraph(g.node_features[:, :4].contiguous(), g.edge_index, g.edge_weight, g.label)
+                for g in graphs]
+    ga = cut(C.generate_dataset(3, 20, 4, seed=3))
+    gb = cut([C.generate_connectome(400, 6, seed=2), C.generate_connectome(20, 4, seed=4)])
+    a, b = C.collate_graphs(ga).to(DEV), C.collate_graphs(gb).to(DEV)
+    torch.manual_seed(6)
+    m = C.GCNConnectome(4, 64, num_layers=2).to(DEV).eval()
+    m.prepare_batch(a, reuse=True)
+    m.prepare_batch(b, reuse=True)
+    outs, kinds = [], []
+    with torch.no_grad():
+        for batch in (a, b, a):
+            outs.append(m(batch).clone())
+            kinds.append((m.impl_used, m._fused_kind))
+    assert kinds == [("fused", "tile"), ("fused", "wide"), ("fused", "tile")]
+    assert torch.equal(outs[0], outs[2])
+    only_a = C.GCNConnectome(4, 64, num_layers=2).to(DEV).eval()
+    only_a.load_state_dict(m.state_dict())
+    a2 = C.collate_graphs(ga).to(DEV)
+    only_a.prepare_batch(a2, reuse=True)
+    with torch.no_grad():
+        assert torch.equal(only_a(a2), outs[0])
+    assert only_a._fused_kind == "tile" and torch.isfinite(outs[1]).all()
+
+
 @pytest.mark.parametrize("mode", ["keep", "drop"])
 def test_capture_with_a_live_earlier_autograd_graph_raises_instead_of_crashing(mode):
     """building a captured step while a non-detached `loss` of an earlier eager step is alive used to
