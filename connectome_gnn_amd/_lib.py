@@ -21,7 +21,28 @@ CGNN_OK, CGNN_EINVAL, CGNN_ELAUNCH, CGNN_EUNSUPPORTED = 0, -1, -2, -3
 _ERR = {CGNN_EINVAL: "CGNN_EINVAL (bad argument)", CGNN_ELAUNCH: "CGNN_ELAUNCH (kernel launch failed)",
         CGNN_EUNSUPPORTED: "CGNN_EUNSUPPORTED (shape not covered by this build)"}
 
-P, I32, I64, U64, F32, F64 = c_void_p, c_int32, c_int64, c_uint64, c_float, c_double
+
+class DevPtr:
+    """A pointer argument (``argtypes``): a tensor (anything with ``data_ptr()``), an address as an int, or None
+    for NULL -- and a ctypes array, for the few host-side id lists of the ingest calls.  Addresses are handed on as
+    c_void_p: ctypes would pass a bare int as a 32-bit C int.  Which tensors may be passed is the call site's
+    business: no device, dtype or contiguity check happens here.  Anything else raises (ctypes names the position)."""
+    _NULL = c_void_p()
+
+    @classmethod
+    def from_param(cls, o):
+        if o is None:
+            return cls._NULL
+        if isinstance(o, int):
+            return c_void_p(o)
+        if hasattr(o, "data_ptr"):
+            return c_void_p(o.data_ptr())
+        if isinstance(o, ctypes.Array):
+            return o
+        raise TypeError(f"expected a tensor, an address or None, got {type(o).__name__}")
+
+
+P, I32, I64, U64, F32, F64 = DevPtr, c_int32, c_int64, c_uint64, c_float, c_double
 
 
 class CgnnTiles(ctypes.Structure):
@@ -111,14 +132,13 @@ class DeferredReduce:
         self.items.append((slab, int(rows), int(width), out))
 
     def flush(self, stream_ptr) -> None:
-        lib = load()
         for lo in range(0, len(self.items), REDUCE_MAX_JOBS):
             chunk = self.items[lo:lo + REDUCE_MAX_JOBS]
             jobs = CgnnReduceJobs()
             jobs.n = len(chunk)
             for i, (slab, rows, width, out) in enumerate(chunk):
                 jobs.slab[i], jobs.rows[i], jobs.width[i], jobs.out[i] = slab.data_ptr(), rows, width, out.data_ptr()
-            check(lib.cgnn_slab_reduce_f64_multi(jobs, stream_ptr), "cgnn_slab_reduce_f64_multi")
+            call("cgnn_slab_reduce_f64_multi", jobs, stream=stream_ptr)
         self.items = []
 
 
@@ -303,6 +323,11 @@ def nbytes(t) -> int:
     return 0 if t is None else t.numel() * t.element_size()
 
 
+def buf(t) -> tuple:
+    """A buffer as ABI 2 takes it: the pointer argument, then the byte count."""
+    return t, nbytes(t)
+
+
 class _NullCtx:
     def __enter__(self):
         return None
@@ -329,6 +354,26 @@ def stream_ptr(device=None) -> int:
     kernels join torch's ordering."""
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(name: str, *args, device=None, stream=None, key=None, accept=()) -> int:
+    """``name(*args, stream)`` of the library: THE way a kernel is launched.  Under ``device``'s guard when one is
+    given; on ``stream``, else on the stream torch is enqueuing on for ``device``; between a HIP-event pair when the
+    installed KernelTimer names ``key`` (default: ``name``).  A return code other than CGNN_OK or one listed in
+    ``accept`` raises CgnnError under ``name``; the code is returned.  With ``stream`` given and no timer naming the
+    key, torch.cuda is not touched (the once-per-pass stream lookup of the fused paths stays the only one)."""
+    fn = getattr(load(), name)
+    with _NULL if device is None else device_guard(device):
+        if stream is None:
+            stream = stream_ptr(device)
+        if TIMER is None:
+            rc = fn(*args, stream)
+        else:
+            with timed(key or name):
+                rc = fn(*args, stream)
+    if rc != CGNN_OK and rc not in accept:
+        check(rc, name)
+    return rc
 
 
 # ---------------------------------------------------------------------------------------------

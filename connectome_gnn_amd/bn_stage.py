@@ -86,7 +86,7 @@ def encode(fn, model, batch, structure, half: bool = False) -> torch.Tensor:
     return out
 
 
-def linear_fwd_stats(lib, x1, x2, w, b, grid, relu: bool = True):
+def linear_fwd_stats(x1, x2, w, b, grid, relu: bool = True):
     """act([x1 | x2] W^T + b) and the per-workgroup (sum | sum of squares) slab of the result, or
     (None, None) when the shape is outside the weight-stationary kernel."""
     m, k1 = x1.shape
@@ -94,14 +94,9 @@ def linear_fwd_stats(lib, x1, x2, w, b, grid, relu: bool = True):
     n = w.shape[0]
     y = torch.empty(m, n, dtype=torch.float32, device=x1.device)
     slab = torch.empty(grid, 2 * n, dtype=torch.float64, device=x1.device)
-    rc = lib.cgnn_linear_fwd_stats_f32(
-        _lib.ptr(x1), x1.stride(0), k1, _lib.ptr(x2), 0 if x2 is None else x2.stride(0), k2,
-        _lib.ptr(w), _lib.ptr(b), int(relu), _lib.ptr(y), y.stride(0), m, n, _lib.ptr(slab), _lib.nbytes(slab),
-        _lib.stream_ptr())
-    if rc == _lib.CGNN_EUNSUPPORTED:
-        return None, None
-    _lib.check(rc, "cgnn_linear_fwd_stats_f32")
-    return y, slab
+    rc = _lib.call("cgnn_linear_fwd_stats_f32", x1, x1.stride(0), k1, x2, 0 if x2 is None else x2.stride(0), k2,
+                   w, b, int(relu), y, y.stride(0), m, n, *_lib.buf(slab), accept=(_lib.CGNN_EUNSUPPORTED,))
+    return (None, None) if rc == _lib.CGNN_EUNSUPPORTED else (y, slab)
 
 
 class BnStage:
@@ -124,14 +119,14 @@ class BnStage:
         self.fsum = None
         self._begin()
         if self.rng is not None and self.p > 0:
-            self._launch("cgnn_rng_advance", _lib.ptr(self.rng), num_layers + 1)
+            self._launch("cgnn_rng_advance", self.rng, num_layers + 1)
 
     def _begin(self):
         self.sp = _lib.stream_ptr(self.dev)      # one lookup per pass (torch.cuda.current_stream is ~10 us)
         self.rows = int(self.lib.cgnn_bn_act_slab_rows(self.n))
 
     def _launch(self, name, *args):
-        _lib.check(getattr(self.lib, name)(*args, self.sp), name)
+        _lib.call(name, *args, stream=self.sp)
 
     # ---- forward
 
@@ -144,7 +139,7 @@ class BnStage:
         srows = self.rows if slab is None else slab.shape[0]
         if self.training and slab is None:
             slab = torch.empty(self.rows, 2 * hid, dtype=torch.float64, device=dev)
-            self._launch("cgnn_bn_act_fwd_stats" + self.sfx, _lib.ptr(y), n, hid, _lib.ptr(slab), _lib.nbytes(slab))
+            self._launch("cgnn_bn_act_fwd_stats" + self.sfx, y, n, hid, *_lib.buf(slab))
         coef = f32(dev, 4 * hid)
         count_dev = None
         if self.training and self.sync_group is not None:
@@ -154,10 +149,9 @@ class BnStage:
             dist.all_reduce(block, op=dist.ReduceOp.SUM, group=self.sync_group)
             slab, srows, count_dev = block, 1, block.data_ptr() + 8 * 2 * hid
             self.count_block = block
-        self._launch("cgnn_bn_act_finalize", _lib.ptr(slab), srows, hid, float(max(n, 1)), count_dev,
-                     int(self.training), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(bn.running_mean),
-                     _lib.ptr(bn.running_var), float(bn.momentum), float(bn.eps),
-                     _lib.ptr(bn.num_batches_tracked) if self.training else None, _lib.ptr(coef))
+        self._launch("cgnn_bn_act_finalize", slab, srows, hid, float(max(n, 1)), count_dev, int(self.training),
+                     gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps),
+                     bn.num_batches_tracked if self.training else None, coef)
         p = self.p
         self.ys.append(y)
         self.coefs.append(coef)
@@ -169,8 +163,8 @@ class BnStage:
         """X' of layer li (cgnn_bn_act_fwd_apply)."""
         y = self.ys[li]
         x = torch.empty_like(y)
-        self._launch("cgnn_bn_act_fwd_apply" + self.sfx, _lib.ptr(y), _lib.ptr(self.coefs[li]), self.relu, self.p,
-                     self.seeds[li], self.rws[li], _lib.ptr(self.masks[li]), _lib.ptr(x), self.n, y.shape[1])
+        self._launch("cgnn_bn_act_fwd_apply" + self.sfx, y, self.coefs[li], self.relu, self.p, self.seeds[li],
+                     self.rws[li], self.masks[li], x, self.n, y.shape[1])
         return x
 
     def pool(self, needs_grad: bool) -> torch.Tensor:
@@ -180,9 +174,8 @@ class BnStage:
         y, s, hid = self.ys[-1], self.s, self.ys[-1].shape[1]
         pooled = f32(self.dev, s.num_graphs, hid)
         self.fsum = f32(self.dev, 2, s.num_graphs, hid) if (self.sync_group is None and needs_grad) else None
-        self._launch("cgnn_bn_act_pool_fwd" + self.sfx, _lib.ptr(y), _lib.ptr(self.coefs[-1]), self.relu, self.p,
-                     self.seeds[-1], self.rws[-1], _lib.ptr(self.masks[-1]), _lib.ptr(s.gptr), s.num_graphs,
-                     _lib.ptr(pooled), hid, _lib.ptr(self.fsum))
+        self._launch("cgnn_bn_act_pool_fwd" + self.sfx, y, self.coefs[-1], self.relu, self.p, self.seeds[-1],
+                     self.rws[-1], self.masks[-1], s.gptr, s.num_graphs, pooled, hid, self.fsum)
         if self.record is not None:
             self.record["layers"] = list(self.masks)
         return pooled
@@ -208,23 +201,21 @@ class BnStage:
                          for d in self.grad_dst[4 * li + 2:4 * li + 4])
         bwc = f32(dev, 2 * hid)
         if li == self.L - 1 and self.fsum is not None:
-            self._launch("cgnn_bn_act_pool_bwd_finalize", _lib.ptr(self.dP), _lib.ptr(self.fsum), _lib.ptr(s.gptr),
-                         s.num_graphs, hid, float(max(n, 1)), int(not self.training), _lib.ptr(dgamma),
-                         _lib.ptr(dbeta), _lib.ptr(bwc))
+            self._launch("cgnn_bn_act_pool_bwd_finalize", self.dP, self.fsum, s.gptr, s.num_graphs, hid,
+                         float(max(n, 1)), int(not self.training), dgamma, dbeta, bwc)
         else:
             slab = torch.empty(self.rows, 2 * hid, dtype=torch.float64, device=dev)
-            self._launch("cgnn_bn_act_bwd_stats" + self.sfx, _lib.ptr(dx), _lib.ptr(y), _lib.ptr(self.masks[li]),
-                         _lib.ptr(coef), self.relu, self.p, n, hid, _lib.ptr(slab), _lib.nbytes(slab), *self._pool(li))
+            self._launch("cgnn_bn_act_bwd_stats" + self.sfx, dx, y, self.masks[li], coef, self.relu, self.p, n, hid,
+                         *_lib.buf(slab), *self._pool(li))
             if direct:
-                self._launch("cgnn_bn_act_bwd_finalize", _lib.ptr(slab), self.rows, hid, float(max(n, 1)), None,
-                             int(not self.training), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(bwc))
+                self._launch("cgnn_bn_act_bwd_finalize", slab, self.rows, hid, float(max(n, 1)), None,
+                             int(not self.training), dgamma, dbeta, bwc)
             else:
                 sums = torch.sum(slab, dim=0)                          # fp64 [2H] = sum dZ | sum dZ*xhat
                 local_dbeta, local_dgamma = sums[:hid].float(), sums[hid:].float()
                 dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.sync_group)
-                self._launch("cgnn_bn_act_bwd_finalize", _lib.ptr(sums), 1, hid, 0.0,
-                             self.count_block.data_ptr() + 8 * 2 * hid, int(not self.training), _lib.ptr(dgamma),
-                             _lib.ptr(dbeta), _lib.ptr(bwc))
+                self._launch("cgnn_bn_act_bwd_finalize", sums, 1, hid, 0.0, self.count_block.data_ptr() + 8 * 2 * hid,
+                             int(not self.training), dgamma, dbeta, bwc)
                 dgamma, dbeta = local_dgamma, local_dbeta
         self.grads[4 * li + 2], self.grads[4 * li + 3] = dgamma, dbeta
         return bwc
@@ -236,9 +227,8 @@ class BnStage:
         cs_rows = int(self.lib.cgnn_bn_act_apply_blocks(n, hid))
         cs_slab = torch.empty(cs_rows, hid, dtype=torch.float64, device=self.dev)
         dy = torch.empty_like(y)
-        self._launch("cgnn_bn_act_bwd_apply" + self.sfx, _lib.ptr(dx), _lib.ptr(y), _lib.ptr(self.masks[li]),
-                     _lib.ptr(self.coefs[li]), _lib.ptr(bwc), self.relu, self.p, 1 - self.relu, _lib.ptr(cs_slab),
-                     _lib.nbytes(cs_slab), _lib.ptr(dy), n, hid, *self._pool(li))
+        self._launch("cgnn_bn_act_bwd_apply" + self.sfx, dx, y, self.masks[li], self.coefs[li], bwc, self.relu, self.p,
+                     1 - self.relu, *_lib.buf(cs_slab), dy, n, hid, *self._pool(li))
         self.add_db(li, cs_slab, cs_rows)
         return dy
 
@@ -247,8 +237,7 @@ class BnStage:
         return self.bwd_apply(li, dx, self.bwd_coefs(li, dx))
 
     def _pool(self, li: int):
-        return (_lib.ptr(self.dP), _lib.ptr(self.s.node_graph), _lib.ptr(self.s.gptr)) if li == self.L - 1 \
-            else (None, None, None)
+        return (self.dP, self.s.node_graph, self.s.gptr) if li == self.L - 1 else (None, None, None)
 
     def add_db(self, li: int, cs_slab, rows: int) -> None:
         """db of layer li from a slab of its column sums: all layers' in one launch at the end (finish)."""

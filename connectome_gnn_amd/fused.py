@@ -12,7 +12,6 @@ one dropout keep-byte per (node, 4-column chunk); activations are rebuilt in LDS
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import List, Optional
 
@@ -80,7 +79,7 @@ def _zeros(dev) -> torch.Tensor:
     return z
 
 
-def _l0_center(lib, s, x0: torch.Tensor, tiles_ref, stream) -> torch.Tensor:
+def _l0_center(s, x0: torch.Tensor, tiles, stream) -> torch.Tensor:
     """The centring constants of the factored layer 0 (cgnn_gcn_l0_center): column means of X0 and
     the mean row sum of the normalised operator over the batch's first tile.  It is a conditioning hint, not part of the arithmetic (any value
     gives the same result up to rounding), so it is computed once per (batch, feature tensor)
@@ -100,8 +99,7 @@ def _l0_center(lib, s, x0: torch.Tensor, tiles_ref, stream) -> torch.Tensor:
     hit = s._l0_center
     if hit is None or hit[0] != key:
         center = torch.empty(8, dtype=torch.float32, device=x0.device)
-        _lib.check(lib.cgnn_gcn_l0_center(tiles_ref, _lib.ptr(x0), x0.shape[1], _lib.ptr(center), stream),
-                   "cgnn_gcn_l0_center")
+        _lib.call("cgnn_gcn_l0_center", tiles, x0, x0.shape[1], center, stream=stream)
         hit = (key, center)
         s._l0_center = hit
         if cache is not None and not torch.cuda.is_current_stream_capturing() and cache._l0_center is None:
@@ -120,7 +118,7 @@ def _kept(s) -> bool:
     return not _NO_L0_CACHE and bool(s._kept)
 
 
-def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, stream):
+def _l0_batch_constants(s, x0: torch.Tensor, center, tiles, sets: int, stream):
     """(P0, moments) of the factored layer 0 on a kept structure, or None = run the full kernel.  Cached as
     `_l0_center` / `permuted_features` are: per (feature tensor, its version, shape), per centre tensor (None
     for the raw form) and per cgnn_l0_grid (the cgnn_set_fused_grid test hook changes it).  A miss aggregates
@@ -134,9 +132,7 @@ def _l0_batch_constants(lib, s, x0: torch.Tensor, center, tiles_ref, sets: int, 
         return None
     p0 = torch.empty(s.num_nodes, 8, dtype=torch.float32, device=x0.device)
     moments = torch.empty(sets, 81, dtype=torch.float64, device=x0.device)
-    with _lib.timed("cgnn_gcn_l0_agg"):
-        _lib.check(lib.cgnn_gcn_l0_agg(tiles_ref, _lib.ptr(x0), x0.shape[1], _lib.ptr(center), _lib.ptr(p0),
-                                       _lib.ptr(moments), _lib.nbytes(moments), stream), "cgnn_gcn_l0_agg")
+    _lib.call("cgnn_gcn_l0_agg", tiles, x0, x0.shape[1], center, p0, *_lib.buf(moments), stream=stream)
     # (x0 and the centre are held so that their addresses stay theirs while the entry lives)
     s._l0_batch = (key, x0, center, p0, moments)
     return p0, moments
@@ -157,10 +153,10 @@ def keep_batch(model, s, x0: torch.Tensor) -> None:
         if not _narrow0(len(model.convs), x0.shape[1]):
             return
         x0 = x0.detach().contiguous()
-        tp = ctypes.byref(_tiles_struct(s, fmeta, dis))
+        tiles = _tiles_struct(s, fmeta, dis)
         sp = _lib.stream_ptr(x0.device)
-        center = _l0_center(lib, s, x0, tp, sp) if (x0.shape[1] < 8 and bn_stage.sync_group_of(model) is None) else None
-        _l0_batch_constants(lib, s, x0, center, tp, lib.cgnn_l0_grid(s.num_nodes), sp)
+        center = _l0_center(s, x0, tiles, sp) if (x0.shape[1] < 8 and bn_stage.sync_group_of(model) is None) else None
+        _l0_batch_constants(s, x0, center, tiles, lib.cgnn_l0_grid(s.num_nodes), sp)
 
 
 class _Ctx:
@@ -229,7 +225,6 @@ class FusedGCNEncode(torch.autograd.Function):
         # the normalisation itself: every forward -- on a kept batch a batch constant, like the CSR
         dis = s.gcn_dis(fmeta, fresh=_NO_L0_CACHE)
         tiles = _tiles_struct(s, fmeta, dis)
-        tp = ctypes.byref(tiles)
         f32 = dict(dtype=torch.float32, device=dev)
         stat_slab = torch.empty(grid, 128, dtype=torch.float64, device=dev) if training else None
         # [sum(64) | sumsq(64) | rows]: the 129th word carries this rank's row count through the
@@ -245,8 +240,7 @@ class FusedGCNEncode(torch.autograd.Function):
             raise RuntimeError("FusedGCNEncode: the input gradient exists for the narrow layer 0 only "
                                "(in_channels <= 8, num_layers >= 2)")
         p0 = l0src = l0keep = None
-        _sp = _lib.stream_ptr(dev)          # one lookup per pass (torch.cuda.current_stream is ~10 us)
-        st = lambda: _sp
+        sp = _lib.stream_ptr(dev)           # one lookup per pass (torch.cuda.current_stream is ~10 us)
         rng = meta.get("rng_state")       # device uint32 words: set when the step is graph-captured
 
         def rng_ptr(i: int):
@@ -257,7 +251,7 @@ class FusedGCNEncode(torch.autograd.Function):
         rng_in_finalize = rng is not None and p > 0 and training and sync_group is None
         with _lib.device_guard(dev):
             if rng is not None and p > 0 and not rng_in_finalize:
-                _lib.check(lib.cgnn_rng_advance(_lib.ptr(rng), L + 1, st()), "cgnn_rng_advance")
+                _lib.call("cgnn_rng_advance", rng, L + 1, stream=sp)
             # per-rank BatchNorm in training: the layer's statistics are finalised by the LAST WORKGROUP of the
             # kernel that produces them (csrc/bn_tail.h) -- no slab, no finalisation launch; with a sync group the
             # sums have to cross the ranks between the two, so the slab protocol stays
@@ -283,14 +277,14 @@ class FusedGCNEncode(torch.autograd.Function):
                     # (Under sync-BN the ranks' constants would differ: raw form there.)
                     y = None
                     f0 = int(x0.shape[1])
-                    center = _l0_center(lib, s, x0, tp, st()) if (f0 < 8 and sync_group is None) else None
+                    center = _l0_center(s, x0, tiles, sp) if (f0 < 8 and sync_group is None) else None
                     slab_rows = lib.cgnn_l0_grid(nn_)
                     # kept batch: P0 and the per-workgroup moments of its rows are batch constants (aggregated
                     # once, cgnn_gcn_l0_agg); the step only turns the moments into this step's sums
                     # (cgnn_gcn_l0_stats).  Never for a differentiable x0 (a fresh gather per pass).
                     const = None
                     if _kept(s) and not ctx.needs_input_grad[0] and not x0.requires_grad:
-                        const = _l0_batch_constants(lib, s, x0, center, tp, slab_rows, st())
+                        const = _l0_batch_constants(s, x0, center, tiles, slab_rows, sp)
                     p0 = const[0] if const is not None else torch.empty(nn_, 8, **f32)
                     if center is not None:
                         w_eff, mean_off = torch.empty(HID, f0 + 1, **f32), torch.empty(HID, **f32)
@@ -302,33 +296,20 @@ class FusedGCNEncode(torch.autograd.Function):
                         l0keep = (w, b, None, None)
                     slab = torch.empty(slab_rows, 128, dtype=torch.float64, device=dev) if (training and tail is None) else None
                     if const is not None:
-                        with _lib.timed("cgnn_gcn_l0_stats"):
-                            _lib.check(lib.cgnn_gcn_l0_stats(
-                                _lib.ptr(const[1]), slab_rows, f0, _lib.ptr(w), _lib.ptr(b), _lib.ptr(center),
-                                _lib.ptr(w_eff), _lib.ptr(mean_off), _lib.ptr(slab), _lib.nbytes(slab),
-                                ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_l0_stats")
+                        _lib.call("cgnn_gcn_l0_stats", const[1], slab_rows, f0, w, b, center, w_eff, mean_off,
+                                  *_lib.buf(slab), tail, stream=sp)
                     else:
-                        with _lib.timed("cgnn_gcn_l0_fwd"):
-                            _lib.check(lib.cgnn_gcn_l0_fwd(
-                                tp, _lib.ptr(x0), f0, _lib.ptr(w), _lib.ptr(b), _lib.ptr(p0), None, _lib.ptr(slab), _lib.nbytes(slab),
-                                _lib.ptr(center), _lib.ptr(w_eff), _lib.ptr(mean_off),
-                                ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_l0_fwd")
+                        _lib.call("cgnn_gcn_l0_fwd", tiles, x0, f0, w, b, p0, None, *_lib.buf(slab), center, w_eff,
+                                  mean_off, tail, stream=sp)
                 elif l == 0:
-                    with _lib.timed("cgnn_gcn_fused_fwd_first"):
-                        _lib.check(lib.cgnn_gcn_fused_fwd_first(
-                            tp, _lib.ptr(x0), x0.shape[1], _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
-                            _lib.ptr(stat_slab), _lib.nbytes(stat_slab), st()), "cgnn_gcn_fused_fwd_first")
+                    _lib.call("cgnn_gcn_fused_fwd_first", tiles, x0, x0.shape[1], w, b, y, *_lib.buf(stat_slab),
+                              stream=sp)
                 else:
                     mask = torch.empty(nn_ * 16, dtype=torch.uint8, device=dev) if p > 0 else None
                     seed = _lib.next_seed(dev) if p > 0 else 0
-                    with _lib.timed("cgnn_gcn_fused_fwd"):
-                        _lib.check(lib.cgnn_gcn_fused_fwd(
-                            tp, _lib.ptr(ys[-1]), ctypes.byref(l0src) if ys[-1] is None else None,
-                            _lib.ptr(bns[-1]), p, seed, rng_ptr(l), _lib.ptr(mask),
-                            _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
-                            None if tail is not None else _lib.ptr(stat_slab), _lib.nbytes(stat_slab),
-                            ctypes.byref(tail) if tail is not None else None, st()),
-                            "cgnn_gcn_fused_fwd")
+                    _lib.call("cgnn_gcn_fused_fwd", tiles, ys[-1], l0src if ys[-1] is None else None, bns[-1], p, seed,
+                              rng_ptr(l), mask, w, b, y, None if tail is not None else stat_slab,
+                              _lib.nbytes(stat_slab), tail, stream=sp)
                     masks.append(mask)
                 cnt = count
                 if tail is not None:
@@ -336,31 +317,23 @@ class FusedGCNEncode(torch.autograd.Function):
                 elif training and sync_group is None:
                     # one launch: reduce partials, finalise, update running stats and the counter
                     adv = rng_in_finalize and l == 0
-                    _lib.check(lib.cgnn_bn_stats_finalize_rng(
-                        _lib.ptr(slab), slab_rows, cnt, _lib.ptr(gamma), _lib.ptr(beta),
-                        _lib.ptr(bn_mod.running_mean), _lib.ptr(bn_mod.running_var),
-                        float(bn_mod.momentum), float(bn_mod.eps),
-                        _lib.ptr(bn_mod.num_batches_tracked), _lib.ptr(bn),
-                        _lib.ptr(rng) if adv else None, L + 1 if adv else 0,
-                        _lib.ptr(l0keep[3]) if (l == 0 and l0keep is not None) else None, st()),
-                        "cgnn_bn_stats_finalize_rng")
+                    _lib.call("cgnn_bn_stats_finalize_rng", slab, slab_rows, cnt, gamma, beta, bn_mod.running_mean,
+                              bn_mod.running_var, float(bn_mod.momentum), float(bn_mod.eps), bn_mod.num_batches_tracked,
+                              bn, rng if adv else None, L + 1 if adv else 0,
+                              l0keep[3] if (l == 0 and l0keep is not None) else None, stream=sp)
                 else:
                     cnt_dev = None
                     if training:
-                        _lib.check(lib.cgnn_bn_reduce(_lib.ptr(slab), slab_rows, 128, _lib.ptr(sums), st()),
-                                   "cgnn_bn_reduce")
+                        _lib.call("cgnn_bn_reduce", slab, slab_rows, 128, sums, stream=sp)
                         sums[128] = local_count
                         _sync_sums(sums, sync_group)
                         cnt_dev = sums.data_ptr() + 128 * 8
                         if count_dev is None:
                             count_dev = sums[128:129].clone()     # global rows, for backward
                         bn_mod.num_batches_tracked.add_(1)
-                    _lib.check(lib.cgnn_bn_finalize(
-                        _lib.ptr(sums), cnt, cnt_dev, _lib.ptr(gamma), _lib.ptr(beta),
-                        _lib.ptr(bn_mod.running_mean), _lib.ptr(bn_mod.running_var),
-                        float(bn_mod.momentum), float(bn_mod.eps), int(training), _lib.ptr(bn),
-                        _lib.ptr(l0keep[3]) if (l == 0 and l0keep is not None) else None, st()),
-                        "cgnn_bn_finalize")
+                    _lib.call("cgnn_bn_finalize", sums, cnt, cnt_dev, gamma, beta, bn_mod.running_mean,
+                              bn_mod.running_var, float(bn_mod.momentum), float(bn_mod.eps), int(training), bn,
+                              l0keep[3] if (l == 0 and l0keep is not None) else None, stream=sp)
                 ys.append(y)
                 bns.append(bn)
             mask = torch.empty(nn_ * 16, dtype=torch.uint8, device=dev) if p > 0 else None
@@ -369,11 +342,8 @@ class FusedGCNEncode(torch.autograd.Function):
             # per-graph factor sums: the readout backward needs no second pass over Y
             want_grad = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:])
             fsum = torch.empty(2, B, HID, **f32) if want_grad else None
-            with _lib.timed("cgnn_gcn_fused_pool_fwd"):
-                _lib.check(lib.cgnn_gcn_fused_pool_fwd(
-                    _lib.ptr(ys[-1]), _lib.ptr(bns[-1]), p, seed, rng_ptr(L), _lib.ptr(mask), _lib.ptr(s.gptr), B,
-                    _lib.ptr(pooled), _lib.ptr(fsum), None if fsum is None else fsum.data_ptr() + 4 * B * HID,
-                    st()), "cgnn_gcn_fused_pool_fwd")
+            _lib.call("cgnn_gcn_fused_pool_fwd", ys[-1], bns[-1], p, seed, rng_ptr(L), mask, s.gptr, B, pooled, fsum,
+                      None if fsum is None else fsum.data_ptr() + 4 * B * HID, stream=sp)
             masks.append(mask)
         c = _Ctx()
         c.s, c.meta, c.dis, c.tiles, c.grid = s, fmeta, dis, tiles, grid
@@ -400,9 +370,7 @@ class FusedGCNEncode(torch.autograd.Function):
         nn_, B = s.num_nodes, s.num_graphs
         f32 = dict(dtype=torch.float32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        tp = ctypes.byref(c.tiles)
-        _sp = _lib.stream_ptr(dev)          # one lookup per pass (torch.cuda.current_stream is ~10 us)
-        st = lambda: _sp
+        sp = _lib.stream_ptr(dev)           # one lookup per pass (torch.cuda.current_stream is ~10 us)
         d_pooled = d_pooled.contiguous()
         s_slab = torch.empty(grid, 128, **f64)
         sums = torch.empty(128, **f64)
@@ -426,47 +394,38 @@ class FusedGCNEncode(torch.autograd.Function):
             dbeta = out(4 * l + 3, HID) if direct else torch.empty(HID, **f32)
             bwc = torch.empty(2 * HID, **f32)
             if c.sync_group is None:
-                _lib.check(lib.cgnn_bn_bwd_stats_finalize(
-                    _lib.ptr(s_slab), grid, c.count, int(not c.training), _lib.ptr(dgamma),
-                    _lib.ptr(dbeta), _lib.ptr(bwc), st()), "cgnn_bn_bwd_stats_finalize")
+                _lib.call("cgnn_bn_bwd_stats_finalize", s_slab, grid, c.count, int(not c.training), dgamma, dbeta, bwc,
+                          stream=sp)
             else:
-                _lib.check(lib.cgnn_bn_reduce(_lib.ptr(s_slab), grid, 128, _lib.ptr(sums), st()),
-                           "cgnn_bn_reduce")
+                _lib.call("cgnn_bn_reduce", s_slab, grid, 128, sums, stream=sp)
                 # parameter gradients are the LOCAL sums (the gradient all-reduce averages them,
                 # exactly like torch's SyncBatchNorm); c1|c2 need the sums over all ranks
                 local_dbeta, local_dgamma = sums[:HID].float(), sums[HID:].float()
                 dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=c.sync_group)
-                _lib.check(lib.cgnn_bn_bwd_finalize(_lib.ptr(sums), c.count, _lib.ptr(c.count_dev),
-                                                    int(not c.training), _lib.ptr(dgamma),
-                                                    _lib.ptr(dbeta), _lib.ptr(bwc), st()),
-                           "cgnn_bn_bwd_finalize")
+                _lib.call("cgnn_bn_bwd_finalize", sums, c.count, c.count_dev, int(not c.training), dgamma, dbeta, bwc,
+                          stream=sp)
                 dgamma, dbeta = local_dgamma, local_dbeta
             grads[4 * l + 2], grads[4 * l + 3] = dgamma, dbeta
             return bwc
 
         # the last layer rebuilds its incoming gradient from dP (POOLIN); the readout backward
         # only supplies the BatchNorm-backward sums (dZ = NULL)
-        pool_args = (_lib.ptr(d_pooled), _lib.ptr(s.node_graph), _lib.ptr(s.gptr), _lib.ptr(c.masks[-1]))
+        pool_args = (d_pooled, s.node_graph, s.gptr, c.masks[-1])
         none_args = (None, None, None, None)
         with _lib.device_guard(dev):
             if c.fsum is not None and c.sync_group is None:
                 # per-rank BatchNorm: the sums over all graphs and the coefficients in one launch
                 dgamma, dbeta, bwc = out(4 * (L - 1) + 2, HID), out(4 * (L - 1) + 3, HID), torch.empty(2 * HID, **f32)
-                _lib.check(lib.cgnn_gcn_fused_pool_bwd_finalize(
-                    _lib.ptr(d_pooled), _lib.ptr(c.fsum), c.fsum.data_ptr() + 4 * B * HID, _lib.ptr(s.gptr), B,
-                    c.count, int(not c.training), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(bwc), st()),
-                    "cgnn_gcn_fused_pool_bwd_finalize")
+                _lib.call("cgnn_gcn_fused_pool_bwd_finalize", d_pooled, c.fsum, c.fsum.data_ptr() + 4 * B * HID, s.gptr,
+                          B, c.count, int(not c.training), dgamma, dbeta, bwc, stream=sp)
                 grads[4 * (L - 1) + 2], grads[4 * (L - 1) + 3] = dgamma, dbeta
             else:
                 if c.fsum is not None:
-                    _lib.check(lib.cgnn_gcn_fused_pool_bwd_sums(
-                        _lib.ptr(d_pooled), _lib.ptr(c.fsum), c.fsum.data_ptr() + 4 * B * HID, _lib.ptr(s.gptr), B,
-                        _lib.ptr(s_slab), _lib.nbytes(s_slab), st()), "cgnn_gcn_fused_pool_bwd_sums")
+                    _lib.call("cgnn_gcn_fused_pool_bwd_sums", d_pooled, c.fsum, c.fsum.data_ptr() + 4 * B * HID, s.gptr,
+                              B, *_lib.buf(s_slab), stream=sp)
                 else:
-                    _lib.check(lib.cgnn_gcn_fused_pool_bwd(
-                        _lib.ptr(d_pooled), _lib.ptr(c.ys[-1]), _lib.ptr(c.bns[-1]), c.p,
-                        _lib.ptr(c.masks[-1]), _lib.ptr(s.gptr), B, None, _lib.ptr(s_slab), _lib.nbytes(s_slab), st()),
-                        "cgnn_gcn_fused_pool_bwd")
+                    _lib.call("cgnn_gcn_fused_pool_bwd", d_pooled, c.ys[-1], c.bns[-1], c.p, c.masks[-1], s.gptr, B,
+                              None, *_lib.buf(s_slab), stream=sp)
                 bwc = bn_backward(L - 1)
             bns_mod = c.bn_modules
             for l in range(L - 1, 0, -1):
@@ -480,15 +439,10 @@ class FusedGCNEncode(torch.autograd.Function):
                 if c.sync_group is None and not _NO_TAILS:
                     nxt = (out(4 * (l - 1) + 2, HID), out(4 * (l - 1) + 3, HID), torch.empty(2 * HID, **f32))
                     tail = _tail_bwd(bns_mod[l - 1], dev, c.count, not c.training, *nxt)
-                with _lib.timed("cgnn_gcn_fused_bwd"):
-                    _lib.check(lib.cgnn_gcn_fused_bwd(
-                        tp, _lib.ptr(dz), _lib.ptr(c.ys[l]), _lib.ptr(c.bns[l]), _lib.ptr(bwc),
-                        _lib.ptr(c.ys[l - 1]), ctypes.byref(c.l0src) if c.ys[l - 1] is None else None,
-                        _lib.ptr(c.bns[l - 1]), c.p, _lib.ptr(c.masks[l - 1]),
-                        _lib.ptr(w), _lib.ptr(dz_prev), None if tail is not None else _lib.ptr(s_slab), _lib.nbytes(s_slab),
-                        _lib.ptr(dw_slab), _lib.nbytes(dw_slab),
-                        _lib.ptr(db_slab), _lib.nbytes(db_slab), *extra,
-                        ctypes.byref(tail) if tail is not None else None, st()), "cgnn_gcn_fused_bwd")
+                _lib.call("cgnn_gcn_fused_bwd", c.tiles, dz, c.ys[l], c.bns[l], bwc, c.ys[l - 1],
+                          c.l0src if c.ys[l - 1] is None else None, c.bns[l - 1], c.p, c.masks[l - 1], w, dz_prev,
+                          None if tail is not None else s_slab, _lib.nbytes(s_slab), *_lib.buf(dw_slab),
+                          *_lib.buf(db_slab), *extra, tail, stream=sp)
                 dw, db = out(4 * l, HID, HID), out(4 * l + 1, HID)
                 jobs.append((dw_slab, db_slab, grid, HID, HID, dw, db))
                 grads[4 * l], grads[4 * l + 1] = dw, db
@@ -504,33 +458,23 @@ class FusedGCNEncode(torch.autograd.Function):
                 g0 = lib.cgnn_l0_grid(nn_)
                 dw_slab0 = torch.empty(g0, HID * 8, **f32)
                 db_slab0 = torch.empty(g0, HID, **f64)
-                l0_args = (ctypes.byref(c.l0src), _lib.ptr(c.bns[0]), _lib.ptr(bwc), _lib.ptr(c.p0), nn_,
-                           _lib.ptr(dw_slab0), _lib.nbytes(dw_slab0), _lib.ptr(db_slab0), _lib.nbytes(db_slab0),
-                           _lib.ptr(c.l0keep[2]))
+                l0_args = (c.l0src, c.bns[0], bwc, c.p0, nn_, *_lib.buf(dw_slab0), *_lib.buf(db_slab0), c.l0keep[2])
                 if ctx.needs_input_grad[0]:
                     # ... and the node-feature gradient dX0 = A_hat^T G0 with G0 = dY0 W0 [Nn, 8]: the 64 -> F0
                     # narrowing rides in the same streaming pass, then one narrow transposed aggregate
                     gbuf = torch.empty(nn_, 8, **f32)
                     dx0 = torch.empty(nn_, c.f0, **f32)
-                    with _lib.timed("cgnn_gcn_l0_bwd_dx"):
-                        _lib.check(lib.cgnn_gcn_l0_bwd_dx(_lib.ptr(dz), *l0_args, _lib.ptr(gbuf), _lib.nbytes(gbuf), st()),
-                                   "cgnn_gcn_l0_bwd_dx")
-                    with _lib.timed("cgnn_gcn_l0_dx"):
-                        _lib.check(lib.cgnn_gcn_l0_dx(tp, _lib.ptr(gbuf), c.f0, _lib.ptr(dx0), _lib.nbytes(dx0), st()),
-                                   "cgnn_gcn_l0_dx")
+                    _lib.call("cgnn_gcn_l0_bwd_dx", dz, *l0_args, *_lib.buf(gbuf), stream=sp)
+                    _lib.call("cgnn_gcn_l0_dx", c.tiles, gbuf, c.f0, *_lib.buf(dx0), stream=sp)
                 else:
-                    with _lib.timed("cgnn_gcn_l0_bwd"):
-                        _lib.check(lib.cgnn_gcn_l0_bwd(_lib.ptr(dz), None, *l0_args, st()), "cgnn_gcn_l0_bwd")
+                    _lib.call("cgnn_gcn_l0_bwd", dz, None, *l0_args, stream=sp)
                 jobs.append((dw_slab0, db_slab0, g0, 8, c.f0, dw0, db0))
             else:
                 extra = pool_args if L == 1 else none_args
                 dw_slab = torch.empty(grid, HID * 16, **f32)
                 db_slab = torch.empty(grid, HID, **f64)
-                with _lib.timed("cgnn_gcn_fused_bwd_first"):
-                    _lib.check(lib.cgnn_gcn_fused_bwd_first(
-                        tp, _lib.ptr(dz), _lib.ptr(c.ys[0]), _lib.ptr(c.bns[0]), _lib.ptr(bwc),
-                        _lib.ptr(c.x0), c.f0, _lib.ptr(dw_slab), _lib.nbytes(dw_slab), _lib.ptr(db_slab), _lib.nbytes(db_slab), c.p, *extra, st()),
-                        "cgnn_gcn_fused_bwd_first")
+                _lib.call("cgnn_gcn_fused_bwd_first", c.tiles, dz, c.ys[0], c.bns[0], bwc, c.x0, c.f0,
+                          *_lib.buf(dw_slab), *_lib.buf(db_slab), c.p, *extra, stream=sp)
                 jobs.append((dw_slab, db_slab, grid, 16, c.f0, dw0, db0))
             grads[0], grads[1] = dw0, db0
             for i0 in range(0, len(jobs), _lib.DW_MAX_JOBS):
@@ -541,7 +485,7 @@ class FusedGCNEncode(torch.autograd.Function):
                     jb.dw_slab[i], jb.db_slab[i] = sw.data_ptr(), sb.data_ptr()
                     jb.rows[i], jb.out_cols[i], jb.take_cols[i] = rows, oc, tc
                     jb.dW[i], jb.db[i] = dw_o.data_ptr(), db_o.data_ptr()
-                _lib.check(lib.cgnn_dw_db_reduce_multi(ctypes.byref(jb), st()), "cgnn_dw_db_reduce_multi")
+                _lib.call("cgnn_dw_db_reduce_multi", jb, stream=sp)
         ctx.c = None
         return (dx0, None, *ops.undelivered(grads, dst))
 

@@ -94,7 +94,7 @@ class GcnWideEncode(torch.autograd.Function):
                         wq = torch.zeros(hid, PAD_K, dtype=torch.float32, device=dev)
                         wq[:, :fin].copy_(w)
                     if bn.training:
-                        y, slab = linear_fwd_stats(lib, p0, None, wq, b, grid, relu=False)
+                        y, slab = linear_fwd_stats(p0, None, wq, b, grid, relu=False)
                     if y is None:
                         y = ops.linear_fwd_raw(p0, None, wq, b, False)
                     sv.p0, sv.padded = p0, pad

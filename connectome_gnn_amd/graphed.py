@@ -317,11 +317,8 @@ class GraphedResidentStep(GraphedTrainStep):
         self.tally.zero_()
 
     def _end_of_step(self, loss: torch.Tensor) -> None:
-        lib = self._lib
-        dev = self.cursor.device
-        with lib.device_guard(dev):
-            lib.check(lib.load().cgnn_epoch_advance(lib.ptr(self.cursor), self._b, lib.ptr(loss), float(self._b),
-                                                    lib.ptr(self.tally), lib.stream_ptr(dev)), "cgnn_epoch_advance")
+        self._lib.call("cgnn_epoch_advance", self.cursor, self._b, loss, float(self._b), self.tally,
+                       device=self.cursor.device)
 
     def __call__(self, batch=None) -> torch.Tensor:
         if batch is not None:
@@ -404,9 +401,7 @@ class GraphedEvalStep:
             logits = model(batch)
             loss = loss_fn(logits, batch.labels)
             self.hits.add_((logits.argmax(dim=1) == batch.labels).sum())
-            with _lib.device_guard(dev):
-                _lib.check(_lib.load().cgnn_epoch_advance(_lib.ptr(self.cursor), b, _lib.ptr(loss), float(b),
-                                                          _lib.ptr(self.tally), _lib.stream_ptr(dev)), "cgnn_epoch_advance")
+            _lib.call("cgnn_epoch_advance", self.cursor, b, loss, float(b), self.tally, device=dev)
 
         self._body, self._dev, self._nodes = body, dev, b * int(cache.n)
         self._run_graph, self._run_failed = None, False

@@ -449,27 +449,21 @@ def _require_resident(data: torch.Tensor, noun: str, does: str) -> None:
 _WORK = object()                                      # among _call's arguments: where the workspace goes
 
 
-def _buf(t) -> tuple:
-    """A buffer as the library takes it: the pointer, then the byte count."""
-    return _lib.ptr(t), _lib.nbytes(t)
-
-
 def _call(dev, name: str, *args, workspace=None) -> None:
-    """``name(*args, stream)`` on ``dev`` under its device guard, with the stream torch is enqueuing on, checked under
-    the call's name.  ``workspace=(call, *arguments)``: ``call + "_workspace_bytes"`` is asked first (its answer may
-    depend on the device's grid), a negative answer is refused, and ``_WORK`` among ``args`` becomes the pointer and
-    the byte count of a uint8 buffer of that size (no buffer for 0 bytes)."""
-    lib = _lib.load()
+    """``_lib.call(name, *args)`` on ``dev``.  ``workspace=(call, *arguments)``: ``call + "_workspace_bytes"`` is asked
+    first (its answer may depend on the device's grid), a negative answer is refused, and ``_WORK`` among ``args``
+    becomes the pointer and the byte count of a uint8 buffer of that size (no buffer for 0 bytes)."""
     with _lib.device_guard(dev):
         if workspace is not None:
             query = workspace[0] + "_workspace_bytes"
-            need = getattr(lib, query)(*workspace[1:])
+            need = getattr(_lib.load(), query)(*workspace[1:])
             if need < 0:                              # (the message names the sizes: the integers in front)
                 sizes = itertools.takewhile(lambda a: isinstance(a, int), workspace[1:])
                 raise _lib.CgnnError(f"{query}({', '.join(map(str, sizes))}) refused its arguments")
-            at = args.index(_WORK)
-            args = args[:at] + _buf(torch.empty(need, dtype=torch.uint8, device=dev) if need else None) + args[at + 1:]
-        _lib.check(getattr(lib, name)(*args, _lib.stream_ptr(dev)), name)
+            at = next(i for i, a in enumerate(args) if a is _WORK)     # (by identity: tensors define ==)
+            work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+            args = args[:at] + _lib.buf(work) + args[at + 1:]
+        _lib.call(name, *args, device=dev)
 
 
 def _thresholds(matrices: torch.Tensor, S: int, keep, num_edges, min_weight) -> torch.Tensor:
@@ -643,7 +637,7 @@ def _check_sample_mask(sample_mask, S: int, T: int, device):
 
 def _masked(name: str, keep) -> tuple:
     """(the entry point of ``name`` that goes with ``keep``, what it takes for the mask)"""
-    return (name, ()) if keep is None else (name + "_masked", _buf(keep))
+    return (name, ()) if keep is None else (name + "_masked", _lib.buf(keep))
 
 
 def _confound_basis(confounds: torch.Tensor, keep=None) -> tuple:
@@ -653,7 +647,7 @@ def _confound_basis(confounds: torch.Tensor, keep=None) -> tuple:
     rank = torch.empty(S, dtype=torch.int32, device=dev)
     if S:
         name, mask = _masked("cgnn_ingest_confound_basis", keep)
-        _call(dev, name, _lib.ptr(confounds), S, T, q, *mask, *_buf(basis), *_buf(rank))
+        _call(dev, name, confounds, S, T, q, *mask, *_lib.buf(basis), *_lib.buf(rank))
     return basis, rank
 
 
@@ -675,8 +669,9 @@ def _regress(timeseries: torch.Tensor, basis, out: torch.Tensor, keep=None) -> N
     """``basis`` None (with ``keep``): masked centring alone."""
     S, T, n = timeseries.shape
     name, mask = _masked("cgnn_ingest_regress", keep)
-    _call(timeseries.device, name, _lib.ptr(timeseries), S, T, n, *mask, *_buf(basis),
-          0 if basis is None else int(basis.shape[2]), _WORK, *_buf(out), workspace=("cgnn_ingest_regress", S, T, n))
+    _call(timeseries.device, name, timeseries, S, T, n, *mask, *_lib.buf(basis),
+          0 if basis is None else int(basis.shape[2]), _WORK, *_lib.buf(out),
+          workspace=("cgnn_ingest_regress", S, T, n))
 
 
 def regress_confounds(timeseries: torch.Tensor, confounds: torch.Tensor, *, sample_mask=None, out=None) -> torch.Tensor:
@@ -734,8 +729,8 @@ def _filter_censored(timeseries: torch.Tensor, k_lo: int, k_hi: int, confounds, 
     design = confounds
     if K:
         design = torch.empty(S, T, K + nq, dtype=torch.float32, device=timeseries.device)
-        _call(timeseries.device, "cgnn_ingest_design", _lib.ptr(confounds), S, T, nq, (ctypes.c_int32 * K)(*comps), K,
-              *_buf(design))
+        _call(timeseries.device, "cgnn_ingest_design", confounds, S, T, nq, (ctypes.c_int32 * K)(*comps), K,
+              *_lib.buf(design))
     basis, _ = _confound_basis(design, keep)
     del design
     _regress(timeseries, basis, out, keep)
@@ -761,8 +756,8 @@ def interpolate_censored(timeseries: torch.Tensor, sample_mask: torch.Tensor, *,
     _check_out(out, timeseries)
     out = _resident_out(timeseries, out)
     if S:
-        _call(timeseries.device, "cgnn_ingest_interpolate", _lib.ptr(timeseries), S, T, n, *_buf(keep), _WORK,
-              *_buf(out), workspace=("cgnn_ingest_interpolate", S, T, n))
+        _call(timeseries.device, "cgnn_ingest_interpolate", timeseries, S, T, n, *_lib.buf(keep), _WORK,
+              *_lib.buf(out), workspace=("cgnn_ingest_interpolate", S, T, n))
     return out
 
 
@@ -826,8 +821,8 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     if S == 0:
         return out
     K = len(comps)                                    # the smaller set is the one that is multiplied
-    _call(timeseries.device, "cgnn_ingest_filter", _lib.ptr(timeseries), S, T, n, (ctypes.c_int32 * K)(*comps), K,
-          int(complement), _WORK, *_buf(out), workspace=("cgnn_ingest_filter", S, T, n, K))
+    _call(timeseries.device, "cgnn_ingest_filter", timeseries, S, T, n, (ctypes.c_int32 * K)(*comps), K,
+          int(complement), _WORK, *_lib.buf(out), workspace=("cgnn_ingest_filter", S, T, n, K))
     if confounds is not None:                         # the same band on the confounds, then out -= Q (Q^T out) in place
         clean = filter_timeseries(confounds, t_r=t_r, high_pass=high_pass, low_pass=low_pass)
         basis, _ = _confound_basis(clean)
@@ -843,8 +838,8 @@ def _correlate(timeseries: torch.Tensor, series: _Series, windowed: bool, absolu
     out = torch.empty(S * series.W, n, n, dtype=torch.float32, device=dev)
     stats = torch.empty(S * series.W, n, 2, dtype=torch.float32, device=dev)      # (mean, 1 / sqrt(q)) per unit and ROI
     name, mask = _masked("cgnn_ingest_corr", keep)
-    _call(dev, name, _lib.ptr(timeseries), S, T, n, *series.window(windowed), int(bool(absolute)), *mask, *_buf(stats),
-          *_buf(out))
+    _call(dev, name, timeseries, S, T, n, *series.window(windowed), int(bool(absolute)), *mask, *_lib.buf(stats),
+          *_lib.buf(out))
     return out, stats
 
 
@@ -855,8 +850,8 @@ def _estimate(timeseries: torch.Tensor, series: _Series, windowed: bool, stats: 
     S, T, n = series[:3]
     alpha = torch.empty(S * series.W, dtype=torch.float64, device=dev)
     name, mask = _masked("cgnn_ingest_shrinkage", keep)
-    inputs = (_lib.ptr(stats), _lib.ptr(matrices)) if keep is None else _buf(stats) + _buf(matrices)
-    _call(dev, name, _lib.ptr(timeseries), S, T, n, *series.window(windowed), *mask, *inputs, *_buf(alpha))
+    inputs = (stats, matrices) if keep is None else _lib.buf(stats) + _lib.buf(matrices)
+    _call(dev, name, timeseries, S, T, n, *series.window(windowed), *mask, *inputs, *_lib.buf(alpha))
     return alpha
 
 
@@ -916,8 +911,8 @@ def _partial(matrices: torch.Tensor, U: int, n: int, shrinkage, absolute: bool, 
     launch."""
     if U:
         each = isinstance(shrinkage, torch.Tensor)
-        _call(matrices.device, "cgnn_ingest_partial_each" if each else "cgnn_ingest_partial", _lib.ptr(matrices), U, n,
-              _lib.ptr(shrinkage) if each else shrinkage, int(bool(absolute)), _WORK, *_buf(out),
+        _call(matrices.device, "cgnn_ingest_partial_each" if each else "cgnn_ingest_partial", matrices, U, n,
+              shrinkage, int(bool(absolute)), _WORK, *_lib.buf(out),
               workspace=("cgnn_ingest_partial", U, n))
     return out
 
@@ -1060,12 +1055,12 @@ def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch
         return x
     num = len(ids)
     arr = (ctypes.c_int32 * num)(*ids)
-    args = [_lib.ptr(matrices), S, n, _lib.ptr(thr), arr, num]
+    args = [matrices, S, n, thr, arr, num]
     if fam.cols:
         args += [(ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1]
-    args += [_WORK, *_buf(x)]
+    args += [_WORK, *_lib.buf(x)]
     if fam.dist:
-        args += _buf(dist)
+        args += _lib.buf(dist)
     _call(matrices.device, fam.call, *args, workspace=(fam.call, S, n, arr, num))
     return x
 
@@ -1126,7 +1121,7 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
     k = _rank(n, keep, num_edges)
     _require_resident(matrices, *_MATRICES)
     thr = torch.empty(S, dtype=torch.float32, device=matrices.device)
-    _call(matrices.device, "cgnn_ingest_select", _lib.ptr(matrices), S, n, k, *_buf(thr))
+    _call(matrices.device, "cgnn_ingest_select", matrices, S, n, k, *_lib.buf(thr))
     return thr
 
 
@@ -1147,7 +1142,6 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     _check_path_size(ids, n)
     _require_resident(matrices, *_MATRICES)
     dev = matrices.device
-    lib = _lib.load()
     if min_weight is None:
         thr = torch.empty(S, dtype=torch.float32, device=dev)     # cgnn_ingest_count selects them: no launch of its own
     else:
@@ -1160,16 +1154,16 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     row_off = torch.zeros(S * n + 1, dtype=torch.long, device=dev)
     with _lib.device_guard(dev):
         sp = _lib.stream_ptr(dev)
-        _lib.check(lib.cgnn_ingest_count(_lib.ptr(matrices), S, n, int(min_weight is None), k, *_buf(thr),
-                                         *_buf(row_count), *_buf(strength), sp), "cgnn_ingest_count")
+        _lib.call("cgnn_ingest_count", matrices, S, n, int(min_weight is None), k, *_lib.buf(thr), *_lib.buf(row_count),
+                  *_lib.buf(strength), stream=sp)
         torch.cumsum(row_count, 0, dtype=torch.long, out=row_off[1:])
         edge_ptr_dev = row_off[::n].contiguous()          # [S + 1]: every subject's first row
         edge_ptr = edge_ptr_dev.cpu()                     # the one read-back
         E = int(edge_ptr[-1])
         edge_local = torch.empty(2, E, dtype=torch.long, device=dev)
         edge_weight = torch.empty(E, dtype=torch.float32, device=dev)
-        _lib.check(lib.cgnn_ingest_fill(_lib.ptr(matrices), S, n, _lib.ptr(thr), _lib.ptr(row_off), E,
-                                        *_buf(edge_local), *_buf(edge_weight), sp), "cgnn_ingest_fill")
+        _lib.call("cgnn_ingest_fill", matrices, S, n, thr, row_off, E, *_lib.buf(edge_local), *_lib.buf(edge_weight),
+                  stream=sp)
     if ids is not None:
         x = _measures(matrices, S, n, thr, ids)       # at the thresholds cgnn_ingest_count selected
     return RaggedPackedDataset(x, edge_local, edge_weight, labels.to(dev), edge_ptr, edge_ptr_dev)

@@ -205,8 +205,7 @@ class _ConnectomeModel(nn.Module):
         x = batch.node_features
         rng = self.rng_device_state           # set by graphed.GraphedTrainStep
         if rng is not None and self.training and self.dropout > 0:
-            _lib.check(_lib.load().cgnn_rng_advance(_lib.ptr(rng), len(self.convs) + 1,
-                                                    _lib.stream_ptr()), "cgnn_rng_advance")
+            _lib.call("cgnn_rng_advance", rng, len(self.convs) + 1)
         rec = self._dropout_record()
         for li, (conv, bn) in enumerate(zip(self.convs, self.batch_norms)):
             x = conv(x, batch.edge_index, batch.edge_weight, structure=s, norm=norm)

@@ -6,7 +6,6 @@ matching backward kernels.  No arithmetic of the message-passing path happens in
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
@@ -47,16 +46,13 @@ def band_operator_f32(structure, rowptr, col, coef) -> Optional[BandOp]:
     s = structure
     if not s.block_diagonal or s.max_nodes_per_graph <= 384 or s.max_nodes_per_graph > 1024 or s.num_edges == 0:
         return None
-    lib = _lib.load()
     dev = coef.device
     pitch = (s.max_nodes_per_graph + 63) // 64 * 64
     steps, nrb = pitch // 16, pitch // 32
     nrows = s.num_graphs * nrb
     counts = torch.empty(nrows * steps, dtype=torch.int32, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(lib.cgnn_dense_pack_count(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), None, _lib.ptr(s.gptr),
-                                             s.num_graphs, pitch, _lib.ptr(counts), _lib.stream_ptr()),
-                   "cgnn_dense_pack_count")
+        _lib.call("cgnn_dense_pack_count", rowptr, col, coef, None, s.gptr, s.num_graphs, pitch, counts)
         cnt = counts.view(nrows, steps).to(torch.int64)
         is_d = cnt > BAND_MIN_NNZ
         covered = float((cnt * is_d).sum()) / max(float(cnt.sum()), 1.0)      # host sync: collate-time
@@ -71,9 +67,7 @@ def band_operator_f32(structure, rowptr, col, coef) -> Optional[BandOp]:
         op = BandOp()
         op.bfrag = torch.empty(max(items, 1) * 3 * 64 * 4, dtype=torch.int32, device=dev)     # 3 KB per fragment
         op.bstep = torch.zeros(max(items, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.cgnn_band_pack_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), _lib.ptr(s.gptr), s.num_graphs,
-                                          pitch, _lib.ptr(fpos32), _lib.ptr(op.bfrag), _lib.ptr(op.bstep),
-                                          _lib.stream_ptr()), "cgnn_band_pack_f32")
+        _lib.call("cgnn_band_pack_f32", rowptr, col, coef, s.gptr, s.num_graphs, pitch, fpos32, op.bfrag, op.bstep)
         # the CSR of the edges outside the listed fragments (COO order inside a row is kept)
         nn_ = s.num_nodes
         deg = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
@@ -94,19 +88,16 @@ def band_operator_f32(structure, rowptr, col, coef) -> Optional[BandOp]:
 def band_aggregate_raw(structure, band: BandOp, selfc, rowdiv, bias, x, out=None, yadd=None) -> torch.Tensor:
     """The operator of ``band`` applied to x with the epilogue of aggregate_raw (+ yadd): the dense fragments'
     part written by cgnn_band_aggregate_f32, the remaining edges added by cgnn_aggregate_acc_f32."""
-    lib = _lib.load()
     n, f = x.shape
     y = torch.empty_like(x) if out is None else out
     # (one timed region: the two launches are one aggregation -- bench.py prices them together)
     with _lib.device_guard(x.device), _lib.timed("cgnn_band_aggregate_f32+cgnn_aggregate_acc_f32", f"F={f}"):
         sp = _lib.stream_ptr()
-        _lib.check(lib.cgnn_band_aggregate_f32(
-            _lib.ptr(band.bfrag), _lib.ptr(band.bstep), _lib.ptr(band.boff), band.pitch, _lib.ptr(structure.gptr),
-            structure.num_graphs, _lib.ptr(x), x.stride(0), f, _lib.ptr(rowdiv), _lib.ptr(yadd),
-            0 if yadd is None else yadd.stride(0), _lib.ptr(y), y.stride(0), sp), "cgnn_band_aggregate_f32")
-        _lib.check(lib.cgnn_aggregate_acc_f32(
-            _lib.ptr(band.rowptr), _lib.ptr(band.col), _lib.ptr(band.coef), _lib.ptr(selfc), _lib.ptr(rowdiv),
-            _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), n, f, sp), "cgnn_aggregate_acc_f32")
+        _lib.call("cgnn_band_aggregate_f32", band.bfrag, band.bstep, band.boff, band.pitch, structure.gptr,
+                  structure.num_graphs, x, x.stride(0), f, rowdiv, yadd, 0 if yadd is None else yadd.stride(0),
+                  y, y.stride(0), stream=sp)
+        _lib.call("cgnn_aggregate_acc_f32", band.rowptr, band.col, band.coef, selfc, rowdiv, bias, x, x.stride(0),
+                  y, y.stride(0), n, f, stream=sp)
     return y
 
 
@@ -123,65 +114,46 @@ def aggregate_raw(rowptr, col, coef, selfc, rowdiv, bias, x, out=None, band=None
     if yadd is not None:
         if not wide:
             raise ValueError("aggregate_raw(yadd=...) takes widths 64, 128, 256 (16-byte aligned rows)")
-        lib = _lib.load()
         y = torch.empty_like(x) if out is None else out
         y.copy_(yadd)                                  # the sum lands on top (cgnn_aggregate_acc_f32)
-        with _lib.device_guard(x.device), _lib.timed("cgnn_aggregate_acc_f32", f"F={f}"):
-            _lib.check(lib.cgnn_aggregate_acc_f32(
-                _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), _lib.ptr(selfc), _lib.ptr(rowdiv), _lib.ptr(bias),
-                _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), x.shape[0], f, _lib.stream_ptr()),
-                "cgnn_aggregate_acc_f32")
+        _lib.call("cgnn_aggregate_acc_f32", rowptr, col, coef, selfc, rowdiv, bias, x, x.stride(0), y, y.stride(0),
+                  x.shape[0], f, device=x.device, key=f"cgnn_aggregate_acc_f32[F={f}]")
         return y
-    lib = _lib.load()
     n, f = x.shape
     y = torch.empty_like(x) if out is None else out
-    with _lib.device_guard(x.device), _lib.timed("cgnn_aggregate_f32", f"F={f}"):
-        _lib.check(lib.cgnn_aggregate_f32(
-            _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), _lib.ptr(selfc), _lib.ptr(rowdiv),
-            _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), n, f,
-            _lib.stream_ptr()), "cgnn_aggregate_f32")
+    _lib.call("cgnn_aggregate_f32", rowptr, col, coef, selfc, rowdiv, bias, x, x.stride(0), y, y.stride(0), n, f,
+              device=x.device, key=f"cgnn_aggregate_f32[F={f}]")
     return y
 
 
 def colsum_raw(a: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     m, n = a.shape
     out = torch.empty(n, dtype=torch.float32, device=a.device)
-    slab = _scratch(lib.cgnn_colsum_workspace_bytes(m, n), a.device)
-    with _lib.device_guard(a.device):
-        _lib.check(lib.cgnn_colsum_f32(_lib.ptr(a), a.stride(0), _lib.ptr(out), m, n,
-                                       _lib.ptr(slab), _lib.nbytes(slab), _lib.stream_ptr()), "cgnn_colsum_f32")
+    slab = _scratch(_lib.load().cgnn_colsum_workspace_bytes(m, n), a.device)
+    _lib.call("cgnn_colsum_f32", a, a.stride(0), out, m, n, *_lib.buf(slab), device=a.device)
     return out
 
 
 def sddmm_raw(rowptr, col, eid, dy, x, xself=None, rowdiv=None, out=None, gself=None, num_slots=None) -> torch.Tensor:
     """out[eid[k] or k] = (<dy[r], x[col[k]]> - <dy[r], xself[r]>) / rowdiv[r] over the CSR (rowptr, col)
     (the subtraction and division only with rowdiv); gself[r] = <dy[r], xself[r]> (cgnn_sddmm_f32)."""
-    lib = _lib.load()
     n, f = dy.shape
     if out is None:
         out = torch.empty(int(col.numel()) if num_slots is None else num_slots, dtype=torch.float32,
                           device=dy.device)
-    with _lib.device_guard(dy.device), _lib.timed("cgnn_sddmm_f32", f"F={f}"):
-        _lib.check(lib.cgnn_sddmm_f32(
-            _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(dy), dy.stride(0), _lib.ptr(x), x.stride(0),
-            _lib.ptr(xself), 0 if xself is None else xself.stride(0), _lib.ptr(rowdiv), _lib.ptr(out),
-            _lib.ptr(gself), n, f, _lib.stream_ptr()), "cgnn_sddmm_f32")
+    _lib.call("cgnn_sddmm_f32", rowptr, col, eid, dy, dy.stride(0), x, x.stride(0), xself,
+              0 if xself is None else xself.stride(0), rowdiv, out, gself, n, f,
+              device=dy.device, key=f"cgnn_sddmm_f32[F={f}]")
     return out
 
 
 def gcn_norm_bwd_raw(structure, edge_weight, dis, g, gself) -> torch.Tensor:
     """dw [Ee] (COO order) of one GCN aggregate from g (COO order) and gself (cgnn_gcn_norm_bwd)."""
-    lib = _lib.load()
     s = structure
     dw = torch.empty(s.num_edges, dtype=torch.float32, device=g.device)
-    ws = _scratch(lib.cgnn_gcn_norm_bwd_workspace_bytes(s.num_nodes), g.device)
-    with _lib.device_guard(g.device):
-        _lib.check(lib.cgnn_gcn_norm_bwd(
-            _lib.ptr(s.rowptr_dst), _lib.ptr(s.col_dst), _lib.ptr(s.eid_dst), _lib.ptr(s.rowptr_src),
-            _lib.ptr(s.col_src), _lib.ptr(s.eid_src), _lib.ptr(edge_weight), _lib.ptr(dis), _lib.ptr(g),
-            _lib.ptr(gself), s.num_nodes, s.num_edges, _lib.ptr(dw), _lib.ptr(ws), _lib.nbytes(ws),
-            _lib.stream_ptr()), "cgnn_gcn_norm_bwd")
+    ws = _scratch(_lib.load().cgnn_gcn_norm_bwd_workspace_bytes(s.num_nodes), g.device)
+    _lib.call("cgnn_gcn_norm_bwd", s.rowptr_dst, s.col_dst, s.eid_dst, s.rowptr_src, s.col_src, s.eid_src,
+              edge_weight, dis, g, gself, s.num_nodes, s.num_edges, dw, *_lib.buf(ws), device=g.device)
     return dw
 
 
@@ -229,55 +201,41 @@ def _edge_grad_out(ctx, dy, xp, y):
 
 
 def linear_fwd_raw(x1, x2, w, bias, relu: bool) -> torch.Tensor:
-    lib = _lib.load()
     m, k1 = x1.shape
     k2 = 0 if x2 is None else x2.shape[1]
     n = w.shape[0]
     if w.shape[1] != k1 + k2:
         raise ValueError(f"weight is {tuple(w.shape)}, inputs give K = {k1}+{k2}")
     y = torch.empty(m, n, dtype=torch.float32, device=x1.device)
-    with _lib.device_guard(x1.device):
-        _lib.check(lib.cgnn_linear_fwd_f32(
-            _lib.ptr(x1), x1.stride(0), k1, _lib.ptr(x2), 0 if x2 is None else x2.stride(0), k2,
-            _lib.ptr(w), _lib.ptr(bias), int(relu), _lib.ptr(y), y.stride(0), m, n,
-            _lib.stream_ptr()), "cgnn_linear_fwd_f32")
+    _lib.call("cgnn_linear_fwd_f32", x1, x1.stride(0), k1, x2, 0 if x2 is None else x2.stride(0), k2, w, bias,
+              int(relu), y, y.stride(0), m, n, device=x1.device)
     return y
 
 
 def linear_bwd_input_raw(dy, w, k0: int, k: int) -> torch.Tensor:
-    lib = _lib.load()
     m, n = dy.shape
     dx = torch.empty(m, k, dtype=torch.float32, device=dy.device)
-    with _lib.device_guard(dy.device):
-        _lib.check(lib.cgnn_linear_bwd_input_f32(
-            _lib.ptr(dy), dy.stride(0), _lib.ptr(w), w.stride(0), k0, _lib.ptr(dx), dx.stride(0),
-            m, n, k, _lib.stream_ptr()), "cgnn_linear_bwd_input_f32")
+    _lib.call("cgnn_linear_bwd_input_f32", dy, dy.stride(0), w, w.stride(0), k0, dx, dx.stride(0), m, n, k,
+              device=dy.device)
     return dx
 
 
 def linear_bwd_weight_raw(dy, x, dw, k0: int) -> None:
-    lib = _lib.load()
     m, n = dy.shape
     k = x.shape[1]
-    slab = _scratch(lib.cgnn_linear_bwd_weight_workspace_bytes(m, n, k), dy.device)
-    with _lib.device_guard(dy.device):
-        _lib.check(lib.cgnn_linear_bwd_weight_f32(
-            _lib.ptr(dy), dy.stride(0), _lib.ptr(x), x.stride(0), _lib.ptr(dw), dw.stride(0), k0,
-            m, n, k, _lib.ptr(slab), _lib.nbytes(slab), _lib.stream_ptr()), "cgnn_linear_bwd_weight_f32")
+    slab = _scratch(_lib.load().cgnn_linear_bwd_weight_workspace_bytes(m, n, k), dy.device)
+    _lib.call("cgnn_linear_bwd_weight_f32", dy, dy.stride(0), x, x.stride(0), dw, dw.stride(0), k0, m, n, k,
+              *_lib.buf(slab), device=dy.device)
 
 
 def linear_bwd_weight2_raw(dy, x1, x2, dw) -> None:
     """dW [N, K1 + K2] = dY^T [X1 | X2] (cgnn_linear_bwd_weight2_f32: one pass over dY when the joint shape
     fits the weight-stationary kernel, else panel by panel); panels may differ in width."""
-    lib = _lib.load()
     m, n = dy.shape
     k1, k2 = x1.shape[1], x2.shape[1]
-    slab = _scratch(lib.cgnn_linear_bwd_weight2_workspace_bytes(m, n, k1, k2), dy.device)
-    with _lib.device_guard(dy.device):
-        _lib.check(lib.cgnn_linear_bwd_weight2_f32(
-            _lib.ptr(dy), dy.stride(0), _lib.ptr(x1), x1.stride(0), k1, _lib.ptr(x2), x2.stride(0), k2,
-            _lib.ptr(dw), dw.stride(0), m, n, _lib.ptr(slab), _lib.nbytes(slab), _lib.stream_ptr()),
-            "cgnn_linear_bwd_weight2_f32")
+    slab = _scratch(_lib.load().cgnn_linear_bwd_weight2_workspace_bytes(m, n, k1, k2), dy.device)
+    _lib.call("cgnn_linear_bwd_weight2_f32", dy, dy.stride(0), x1, x1.stride(0), k1, x2, x2.stride(0), k2,
+              dw, dw.stride(0), m, n, *_lib.buf(slab), device=dy.device)
 
 
 # ------------------------------------------------------------------------- autograd Functions
@@ -322,15 +280,11 @@ AGG_TRANSPOSED, AGG_PRE_DIV, AGG_POST_DIV = 1, 2, 4   # include/cgnn.h
 def aggregate_tiled_raw(structure, meta, flags: int, x, pre, post, bias, yadd=None) -> torch.Tensor:
     """Y = post * A(pre * X) (+bias) (+yadd) through cgnn_aggregate_tiled_f32 (LDS-staged tiles).
     x / yadd may be column slices of wider row-major buffers (their row stride is passed on)."""
-    lib = _lib.load()
     n, f = x.shape
     y = torch.empty(n, f, dtype=torch.float32, device=x.device)
-    tiles = structure.tiles_struct(meta)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_aggregate_tiled_f32", f"F={f}"):
-        _lib.check(lib.cgnn_aggregate_tiled_f32(
-            ctypes.byref(tiles), int(flags), _lib.ptr(x), x.stride(0), f, _lib.ptr(pre), _lib.ptr(post),
-            _lib.ptr(bias), _lib.ptr(yadd), 0 if yadd is None else yadd.stride(0), _lib.ptr(y),
-            y.stride(0), _lib.stream_ptr()), "cgnn_aggregate_tiled_f32")
+    _lib.call("cgnn_aggregate_tiled_f32", structure.tiles_struct(meta), int(flags), x, x.stride(0), f, pre, post,
+              bias, yadd, 0 if yadd is None else yadd.stride(0), y, y.stride(0),
+              device=x.device, key=f"cgnn_aggregate_tiled_f32[F={f}]")
     return y
 
 
@@ -338,62 +292,47 @@ def aggregate_tiled_bn_raw(structure, meta, flags: int, z, pre, post, bias, coef
                            seed: int, seed_dev, mask, xout) -> torch.Tensor:
     """Y = post * A(pre * X) (+bias) with X = drop(act(a z + b)) formed while the tiles are staged and
     also written to ``xout`` (keep bytes to ``mask``): cgnn_aggregate_tiled_bn_f32."""
-    lib = _lib.load()
     n, f = z.shape
     y = torch.empty(n, f, dtype=torch.float32, device=z.device)
-    tiles = structure.tiles_struct(meta)
-    with _lib.device_guard(z.device), _lib.timed("cgnn_aggregate_tiled_f32", f"F={f}"):
-        _lib.check(lib.cgnn_aggregate_tiled_bn_f32(
-            ctypes.byref(tiles), int(flags), _lib.ptr(z), z.stride(0), f, _lib.ptr(pre), _lib.ptr(post),
-            _lib.ptr(bias), _lib.ptr(y), y.stride(0), _lib.ptr(coef), int(relu), float(p), int(seed), seed_dev,
-            _lib.ptr(mask), _lib.ptr(xout), xout.stride(0), _lib.stream_ptr()), "cgnn_aggregate_tiled_bn_f32")
+    # (timed under the plain tiled aggregate's key: bench.py prices both as the same aggregation)
+    _lib.call("cgnn_aggregate_tiled_bn_f32", structure.tiles_struct(meta), int(flags), z, z.stride(0), f, pre, post,
+              bias, y, y.stride(0), coef, int(relu), float(p), int(seed), seed_dev, mask, xout, xout.stride(0),
+              device=z.device, key=f"cgnn_aggregate_tiled_f32[F={f}]")
     return y
 
 
 def aggregate_tiled_f16_raw(structure, meta, flags: int, x, pre, post, bias) -> torch.Tensor:
     """fp16-storage / fp32-accumulate tiled aggregate (cgnn_aggregate_tiled_f16): x, result half."""
-    lib = _lib.load()
     _require_device(x, "x")
     if x.dtype != torch.float16:
         raise TypeError(f"x must be float16, got {x.dtype}")
     n, f = x.shape
     y = torch.empty(n, f, dtype=torch.float16, device=x.device)
-    tiles = structure.tiles_struct(meta)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_aggregate_tiled_f16", f"F={f}"):
-        _lib.check(lib.cgnn_aggregate_tiled_f16(
-            ctypes.byref(tiles), int(flags), _lib.ptr(x), x.stride(0), f, _lib.ptr(pre), _lib.ptr(post),
-            _lib.ptr(bias), _lib.ptr(y), y.stride(0), _lib.stream_ptr()), "cgnn_aggregate_tiled_f16")
+    _lib.call("cgnn_aggregate_tiled_f16", structure.tiles_struct(meta), int(flags), x, x.stride(0), f, pre, post,
+              bias, y, y.stride(0), device=x.device, key=f"cgnn_aggregate_tiled_f16[F={f}]")
     return y
 
 
 def dense_adj_f16(structure, coef, selfc, transposed: bool = False) -> torch.Tensor:
     """[B, P, P] half dense operator of one CSR ordering (cgnn_dense_adj_f16); static per batch."""
-    lib = _lib.load()
     s = structure
     pitch = (s.max_nodes_per_graph + 63) // 64 * 64
     m = torch.empty(s.num_graphs, pitch, pitch, dtype=torch.float16, device=coef.device)
     rowptr, col = (s.rowptr_src, s.col_src) if transposed else (s.rowptr_dst, s.col_dst)
-    with _lib.device_guard(coef.device):
-        _lib.check(lib.cgnn_dense_adj_f16(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), _lib.ptr(selfc),
-                                          _lib.ptr(s.gptr), s.num_graphs, pitch, _lib.ptr(m),
-                                          _lib.stream_ptr()), "cgnn_dense_adj_f16")
+    _lib.call("cgnn_dense_adj_f16", rowptr, col, coef, selfc, s.gptr, s.num_graphs, pitch, m, device=coef.device)
     return m
 
 
 def dense_aggregate_f16_raw(structure, m, x, bias=None, stat_slab=None) -> torch.Tensor:
     """Y_g = M_g X_g on the fp16 matrix cores (cgnn_dense_aggregate_f16); x, result half.
     stat_slab: optional fp64 [cgnn_fused_grid(), 2F] for the result's BatchNorm sums."""
-    lib = _lib.load()
     _require_device(x, "x")
     if x.dtype != torch.float16 or m.dtype != torch.float16:
         raise TypeError("x and m must be float16")
     n, f = x.shape
     y = torch.empty(n, f, dtype=torch.float16, device=x.device)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_dense_aggregate_f16", f"F={f}"):
-        _lib.check(lib.cgnn_dense_aggregate_f16(
-            _lib.ptr(m), m.shape[1], _lib.ptr(structure.gptr), structure.num_graphs, _lib.ptr(x),
-            x.stride(0), f, _lib.ptr(bias), _lib.ptr(y), y.stride(0), _lib.ptr(stat_slab), _lib.nbytes(stat_slab), _lib.stream_ptr()),
-            "cgnn_dense_aggregate_f16")
+    _lib.call("cgnn_dense_aggregate_f16", m, m.shape[1], structure.gptr, structure.num_graphs, x, x.stride(0), f,
+              bias, y, y.stride(0), *_lib.buf(stat_slab), device=x.device, key=f"cgnn_dense_aggregate_f16[F={f}]")
     return y
 
 
@@ -409,17 +348,16 @@ class DensePack:
 
 
 def dense_pack_f16(structure, coef, selfc, transposed: bool = False) -> DensePack:
-    lib = _lib.load()
     s = structure
     dev = coef.device
     pitch = (s.max_nodes_per_graph + 63) // 64 * 64
     steps, nrows = pitch // 16, s.num_graphs * (pitch // 32)
     rowptr, col = (s.rowptr_src, s.col_src) if transposed else (s.rowptr_dst, s.col_dst)
     counts = torch.empty(nrows * steps, dtype=torch.int32, device=dev)
-    args = (_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(coef), _lib.ptr(selfc), _lib.ptr(s.gptr), s.num_graphs, pitch)
+    args = (rowptr, col, coef, selfc, s.gptr, s.num_graphs, pitch)
     pk = DensePack()
     with _lib.device_guard(dev):
-        _lib.check(lib.cgnn_dense_pack_count(*args, _lib.ptr(counts), _lib.stream_ptr()), "cgnn_dense_pack_count")
+        _lib.call("cgnn_dense_pack_count", *args, counts)
         cnt = counts.view(nrows, steps).to(torch.int64)
         is_d, is_s = cnt > 64, (cnt > 0) & (cnt <= 64)
         nd, ns = is_d.sum(1), is_s.sum(1)
@@ -442,9 +380,7 @@ def dense_pack_f16(structure, coef, selfc, transposed: bool = False) -> DensePac
         pk.sent = torch.full((max(tot_s, 4) * 64,), 0xFFFF, dtype=torch.int32, device=dev)
         pk.sstep = torch.zeros(max(tot_s, 4), dtype=torch.int32, device=dev)
         pk.doff, pk.soff = doff.to(torch.int32), soff.to(torch.int32)
-        _lib.check(lib.cgnn_dense_pack_fill(*args, _lib.ptr(fpos.contiguous()), _lib.ptr(pk.dfrag), _lib.ptr(pk.dstep),
-                                            _lib.ptr(pk.sent), _lib.ptr(pk.sstep), _lib.stream_ptr()),
-                   "cgnn_dense_pack_fill")
+        _lib.call("cgnn_dense_pack_fill", *args, fpos.contiguous(), pk.dfrag, pk.dstep, pk.sent, pk.sstep)
         torch.cuda.current_stream(dev).synchronize()        # fpos is a temporary of this call
     pk.pitch, pk.nnz, pk.num_dense, pk.num_sparse = pitch, int(counts.sum()), tot_d, int(ns.sum())
     return pk
@@ -452,18 +388,14 @@ def dense_pack_f16(structure, coef, selfc, transposed: bool = False) -> DensePac
 
 def dense_aggregate_c16_raw(structure, pack: DensePack, x, bias=None, stat_slab=None) -> torch.Tensor:
     """Y_g = M_g X_g from the per-fragment operator (cgnn_dense_aggregate_c16); x, result half."""
-    lib = _lib.load()
     _require_device(x, "x")
     if x.dtype != torch.float16:
         raise TypeError("x must be float16")
     n, f = x.shape
     y = torch.empty(n, f, dtype=torch.float16, device=x.device)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_dense_aggregate_c16", f"F={f}"):
-        _lib.check(lib.cgnn_dense_aggregate_c16(
-            _lib.ptr(pack.dfrag), _lib.ptr(pack.dstep), _lib.ptr(pack.doff), _lib.ptr(pack.sent),
-            _lib.ptr(pack.sstep), _lib.ptr(pack.soff), pack.pitch, _lib.ptr(structure.gptr),
-            structure.num_graphs, _lib.ptr(x), x.stride(0), f, _lib.ptr(bias), _lib.ptr(y), y.stride(0),
-            _lib.ptr(stat_slab), _lib.nbytes(stat_slab), _lib.stream_ptr()), "cgnn_dense_aggregate_c16")
+    _lib.call("cgnn_dense_aggregate_c16", pack.dfrag, pack.dstep, pack.doff, pack.sent, pack.sstep, pack.soff,
+              pack.pitch, structure.gptr, structure.num_graphs, x, x.stride(0), f, bias, y, y.stride(0),
+              *_lib.buf(stat_slab), device=x.device, key=f"cgnn_dense_aggregate_c16[F={f}]")
     return y
 
 
@@ -471,17 +403,13 @@ def dense_aggregate_c16_bnbwd_raw(structure, pack: DensePack, dx, dP, yl, mask, 
     """dT = M_g dY with dY = BatchNorm'(dX' * act' * drop') formed while the slices are staged
     (cgnn_dense_aggregate_c16_bnbwd): returns (dT half [M, F], cs_slab fp64 [B, F] = per-graph column
     sums of dY).  Exactly one of dx (half [M, F]) and dP (fp32 [B, F], readout gradient)."""
-    lib = _lib.load()
     n, f = yl.shape
     dt = torch.empty(n, f, dtype=torch.float16, device=yl.device)
     cs = torch.empty(structure.num_graphs, f, dtype=torch.float64, device=yl.device)
-    with _lib.device_guard(yl.device), _lib.timed("cgnn_dense_aggregate_c16_bnbwd", f"F={f}"):
-        _lib.check(lib.cgnn_dense_aggregate_c16_bnbwd(
-            _lib.ptr(pack.dfrag), _lib.ptr(pack.dstep), _lib.ptr(pack.doff), _lib.ptr(pack.sent),
-            _lib.ptr(pack.sstep), _lib.ptr(pack.soff), pack.pitch, _lib.ptr(structure.gptr), structure.num_graphs,
-            _lib.ptr(dx), 0 if dx is None else dx.stride(0), _lib.ptr(dP), _lib.ptr(yl), yl.stride(0), _lib.ptr(mask),
-            _lib.ptr(coef), _lib.ptr(bwc), int(relu), float(p), f, _lib.ptr(dt), dt.stride(0), _lib.ptr(cs), _lib.nbytes(cs),
-            _lib.stream_ptr()), "cgnn_dense_aggregate_c16_bnbwd")
+    _lib.call("cgnn_dense_aggregate_c16_bnbwd", pack.dfrag, pack.dstep, pack.doff, pack.sent, pack.sstep, pack.soff,
+              pack.pitch, structure.gptr, structure.num_graphs, dx, 0 if dx is None else dx.stride(0), dP,
+              yl, yl.stride(0), mask, coef, bwc, int(relu), float(p), f, dt, dt.stride(0), *_lib.buf(cs),
+              device=yl.device, key=f"cgnn_dense_aggregate_c16_bnbwd[F={f}]")
     return dt, cs
 
 
@@ -495,81 +423,65 @@ def _need_half(t: torch.Tensor, what: str) -> None:
 def linear_fwd_f16_raw(x, w, bias=None) -> torch.Tensor:
     """Y = X W^T + bias: X half [M, K], W fp32 [N, Kw] with Kw <= K (columns k >= Kw of X are
     ignored: layer 0's few input features ride in a 64-column panel); Y half [M, N]."""
-    lib = _lib.load()
     _need_half(x, "x")
     m, k = x.shape
     n, kw = w.shape
     y = torch.empty(m, n, dtype=torch.float16, device=x.device)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_linear_fwd_f16", f"K={k},N={n}"):
-        _lib.check(lib.cgnn_linear_fwd_f16(_lib.ptr(x), x.stride(0), k, _lib.ptr(w), w.stride(0), kw,
-                                           _lib.ptr(bias), _lib.ptr(y), y.stride(0), m, n, _lib.stream_ptr()),
-                   "cgnn_linear_fwd_f16")
+    _lib.call("cgnn_linear_fwd_f16", x, x.stride(0), k, w, w.stride(0), kw, bias, y, y.stride(0), m, n,
+              device=x.device, key=f"cgnn_linear_fwd_f16[K={k},N={n}]")
     return y
 
 
 def linear_fwd_stats_f16_raw(x, w, bias, grid: int):
     """linear_fwd_f16_raw that also leaves the BatchNorm statistics of Y (sum | sum of squares per
     column, fp64 per-workgroup partials [grid, 2N]) -- or (None, None) outside the kernel's shapes."""
-    lib = _lib.load()
     _need_half(x, "x")
     m, k = x.shape
     n, kw = w.shape
     y = torch.empty(m, n, dtype=torch.float16, device=x.device)
     slab = torch.empty(grid, 2 * n, dtype=torch.float64, device=x.device)
-    with _lib.device_guard(x.device), _lib.timed("cgnn_linear_fwd_stats_f16", f"K={k},N={n}"):
-        rc = lib.cgnn_linear_fwd_stats_f16(_lib.ptr(x), x.stride(0), k, _lib.ptr(w), w.stride(0), kw, _lib.ptr(bias),
-                                           _lib.ptr(y), y.stride(0), m, n, _lib.ptr(slab), _lib.nbytes(slab), _lib.stream_ptr())
-    if rc == _lib.CGNN_EUNSUPPORTED:
-        return None, None
-    _lib.check(rc, "cgnn_linear_fwd_stats_f16")
-    return y, slab
+    rc = _lib.call("cgnn_linear_fwd_stats_f16", x, x.stride(0), k, w, w.stride(0), kw, bias, y, y.stride(0), m, n,
+                   *_lib.buf(slab), device=x.device, key=f"cgnn_linear_fwd_stats_f16[K={k},N={n}]",
+                   accept=(_lib.CGNN_EUNSUPPORTED,))
+    return (None, None) if rc == _lib.CGNN_EUNSUPPORTED else (y, slab)
 
 
 def linear_bwd_input_f16_raw(dy, w) -> torch.Tensor:
     """dX = dY W: dY half [M, N], W fp32 [N, K]; dX half [M, K]."""
-    lib = _lib.load()
     _need_half(dy, "dy")
     m, n = dy.shape
     k = w.shape[1]
     dx = torch.empty(m, k, dtype=torch.float16, device=dy.device)
-    with _lib.device_guard(dy.device), _lib.timed("cgnn_linear_bwd_input_f16", f"K={k},N={n}"):
-        _lib.check(lib.cgnn_linear_bwd_input_f16(_lib.ptr(dy), dy.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(dx),
-                                                 dx.stride(0), m, n, k, _lib.stream_ptr()),
-                   "cgnn_linear_bwd_input_f16")
+    _lib.call("cgnn_linear_bwd_input_f16", dy, dy.stride(0), w, w.stride(0), dx, dx.stride(0), m, n, k,
+              device=dy.device, key=f"cgnn_linear_bwd_input_f16[K={k},N={n}]")
     return dx
 
 
 def linear_bwd_weight_f16_raw(dy, x, kw: Optional[int] = None) -> torch.Tensor:
     """dW[N, kw] (fp32) = dY^T X[:, :kw]: dY half [M, N], X half [M, K]."""
-    lib = _lib.load()
     _need_half(dy, "dy")
     _need_half(x, "x")
     m, n = dy.shape
     k = x.shape[1]
     kw = k if kw is None else int(kw)
-    nbytes = int(lib.cgnn_linear_bwd_weight_f16_workspace_bytes(m, n, k))
+    nbytes = int(_lib.load().cgnn_linear_bwd_weight_f16_workspace_bytes(m, n, k))
     if nbytes < 0:
         raise _lib.CgnnError(f"cgnn_linear_bwd_weight_f16: shape N={n}, K={k} not covered")
     slab = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=dy.device)
     dw = torch.empty(n, kw, dtype=torch.float32, device=dy.device)
-    with _lib.device_guard(dy.device), _lib.timed("cgnn_linear_bwd_weight_f16", f"K={k},N={n}"):
-        _lib.check(lib.cgnn_linear_bwd_weight_f16(_lib.ptr(dy), dy.stride(0), _lib.ptr(x), x.stride(0), _lib.ptr(dw),
-                                                  kw, kw, m, n, k, _lib.ptr(slab), _lib.nbytes(slab), _lib.stream_ptr()),
-                   "cgnn_linear_bwd_weight_f16")
+    _lib.call("cgnn_linear_bwd_weight_f16", dy, dy.stride(0), x, x.stride(0), dw, kw, kw, m, n, k, *_lib.buf(slab),
+              device=dy.device, key=f"cgnn_linear_bwd_weight_f16[K={k},N={n}]")
     return dw
 
 
 def pad_cast_f16(x, width: int) -> torch.Tensor:
     """[x | zeros] as a half [M, width] panel (x fp32 [M, F], F <= width)."""
-    lib = _lib.load()
     _require_device(x, "x")
     if x.dtype != torch.float32 or x.stride(1) != 1:
         raise TypeError("x must be a float32 matrix with contiguous rows")
     m, f = x.shape
     y = torch.empty(m, width, dtype=torch.float16, device=x.device)
-    with _lib.device_guard(x.device):
-        _lib.check(lib.cgnn_pad_cast_f16(_lib.ptr(x), x.stride(0), f, _lib.ptr(y), width, m, _lib.stream_ptr()),
-                   "cgnn_pad_cast_f16")
+    _lib.call("cgnn_pad_cast_f16", x, x.stride(0), f, y, width, m, device=x.device)
     return y
 
 
@@ -672,27 +584,19 @@ def linear(x1, x2, w, bias, relu: bool = False) -> torch.Tensor:
 class _PoolMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gptr, num_graphs):
-        lib = _lib.load()
         x = _prep(x, "x")
         f = x.shape[1]
         p = torch.empty(num_graphs, f, dtype=torch.float32, device=x.device)
-        with _lib.device_guard(x.device):
-            _lib.check(lib.cgnn_pool_mean_fwd_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gptr),
-                                                  _lib.ptr(p), num_graphs, f, _lib.stream_ptr()),
-                       "cgnn_pool_mean_fwd_f32")
+        _lib.call("cgnn_pool_mean_fwd_f32", x, x.stride(0), gptr, p, num_graphs, f, device=x.device)
         ctx.gptr, ctx.shape = gptr, x.shape
         return p
 
     @staticmethod
     def backward(ctx, dp):
-        lib = _lib.load()
         dp = _prep(dp, "grad")
         n, f = ctx.shape
         dx = torch.empty(n, f, dtype=torch.float32, device=dp.device)
-        with _lib.device_guard(dp.device):
-            _lib.check(lib.cgnn_pool_mean_bwd_f32(_lib.ptr(dp), _lib.ptr(ctx.gptr), _lib.ptr(dx),
-                                                  dx.stride(0), dp.shape[0], f, _lib.stream_ptr()),
-                       "cgnn_pool_mean_bwd_f32")
+        _lib.call("cgnn_pool_mean_bwd_f32", dp, ctx.gptr, dx, dx.stride(0), dp.shape[0], f, device=dp.device)
         return dx, None, None
 
 
@@ -715,24 +619,18 @@ class _BnActDrop(torch.autograd.Function):
         x = torch.empty_like(y)
         mask = torch.empty(m * (n // 4), dtype=torch.uint8, device=dev) if p_eff > 0 else None
         seed = _lib.next_seed(dev) if p_eff > 0 else 0
-        _sp = _lib.stream_ptr(dev)          # one lookup per pass (torch.cuda.current_stream is ~10 us)
-        st = lambda: _sp
+        sp = _lib.stream_ptr(dev)           # one lookup per pass (torch.cuda.current_stream is ~10 us)
         with _lib.device_guard(dev):
             rows = int(lib.cgnn_bn_act_slab_rows(m))
             slab = torch.empty(rows, 2 * n, dtype=torch.float64, device=dev) if training else None
             if training:
-                _lib.check(lib.cgnn_bn_act_fwd_stats(_lib.ptr(y), m, n, _lib.ptr(slab), _lib.nbytes(slab), st()),
-                           "cgnn_bn_act_fwd_stats")
-            _lib.check(lib.cgnn_bn_act_finalize(
-                _lib.ptr(slab), rows, n, float(max(m, 1)), None, int(training), _lib.ptr(gamma.contiguous()),
-                _lib.ptr(beta.contiguous()), _lib.ptr(bn_mod.running_mean), _lib.ptr(bn_mod.running_var),
-                float(bn_mod.momentum), float(bn_mod.eps),
-                _lib.ptr(bn_mod.num_batches_tracked) if training else None, _lib.ptr(coef), st()),
-                "cgnn_bn_act_finalize")
-            _lib.check(lib.cgnn_bn_act_fwd_apply(_lib.ptr(y), _lib.ptr(coef), int(relu), p_eff, seed,
-                                                 rng_word if p_eff > 0 else None,
-                                                 _lib.ptr(mask), _lib.ptr(x), m, n, st()),
-                       "cgnn_bn_act_fwd_apply")
+                _lib.call("cgnn_bn_act_fwd_stats", y, m, n, *_lib.buf(slab), stream=sp)
+            _lib.call("cgnn_bn_act_finalize", slab, rows, n, float(max(m, 1)), None, int(training),
+                      gamma.contiguous(), beta.contiguous(), bn_mod.running_mean, bn_mod.running_var,
+                      float(bn_mod.momentum), float(bn_mod.eps), bn_mod.num_batches_tracked if training else None,
+                      coef, stream=sp)
+            _lib.call("cgnn_bn_act_fwd_apply", y, coef, int(relu), p_eff, seed, rng_word if p_eff > 0 else None,
+                      mask, x, m, n, stream=sp)
         if record is not None:
             record.setdefault("layers", []).append(mask)
         ctx.save_for_backward(y, coef, mask)
@@ -748,24 +646,18 @@ class _BnActDrop(torch.autograd.Function):
         m, n = y.shape
         dev = y.device
         f32 = dict(dtype=torch.float32, device=dev)
-        _sp = _lib.stream_ptr(dev)          # one lookup per pass (torch.cuda.current_stream is ~10 us)
-        st = lambda: _sp
+        sp = _lib.stream_ptr(dev)           # one lookup per pass (torch.cuda.current_stream is ~10 us)
         dgamma, dbeta, bwc = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(2 * n, **f32)
         dy = torch.empty_like(y)
         with _lib.device_guard(dev):
             rows = int(lib.cgnn_bn_act_slab_rows(m))
             slab = torch.empty(rows, 2 * n, dtype=torch.float64, device=dev)
-            _lib.check(lib.cgnn_bn_act_bwd_stats(_lib.ptr(dx), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(coef),
-                                                 int(relu), p_eff, m, n, _lib.ptr(slab), _lib.nbytes(slab), None, None, None,
-                                                 st()),
-                       "cgnn_bn_act_bwd_stats")
-            _lib.check(lib.cgnn_bn_act_bwd_finalize(_lib.ptr(slab), rows, n, float(max(m, 1)), None,
-                                                    int(not training), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                                    _lib.ptr(bwc), st()), "cgnn_bn_act_bwd_finalize")
-            _lib.check(lib.cgnn_bn_act_bwd_apply(_lib.ptr(dx), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(coef),
-                                                 _lib.ptr(bwc), int(relu), p_eff, 0, None, 0, _lib.ptr(dy), m, n,
-                                                 None, None, None, st()),
-                       "cgnn_bn_act_bwd_apply")
+            _lib.call("cgnn_bn_act_bwd_stats", dx, y, mask, coef, int(relu), p_eff, m, n, *_lib.buf(slab),
+                      None, None, None, stream=sp)
+            _lib.call("cgnn_bn_act_bwd_finalize", slab, rows, n, float(max(m, 1)), None, int(not training),
+                      dgamma, dbeta, bwc, stream=sp)
+            _lib.call("cgnn_bn_act_bwd_apply", dx, y, mask, coef, bwc, int(relu), p_eff, 0, None, 0, dy, m, n,
+                      None, None, None, stream=sp)
         return dy, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -786,7 +678,6 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, w1, b1, w2, b2, p_drop, training, rng_word, record=None):
-        lib = _lib.load()
         p, w1, b1, w2, b2 = (_prep(t, "head tensor") for t in (p, w1, b1, w2, b2))
         bsz, h = p.shape
         h2, c = w1.shape[0], w2.shape[0]
@@ -796,11 +687,8 @@ class _Head(torch.autograd.Function):
         seed = _lib.next_seed(dev) if p_eff > 0 else 0
         h1, fac = torch.empty(bsz, h2, **f32), torch.empty(bsz, h2, **f32)
         logits = torch.empty(bsz, c, **f32)
-        with _lib.device_guard(dev):
-            _lib.check(lib.cgnn_head_fwd_f32(_lib.ptr(p), bsz, h, h2, c, _lib.ptr(w1), _lib.ptr(b1),
-                                             _lib.ptr(w2), _lib.ptr(b2), p_eff, seed,
-                                             rng_word if p_eff > 0 else None, _lib.ptr(h1), _lib.ptr(fac),
-                                             _lib.ptr(logits), _lib.stream_ptr()), "cgnn_head_fwd_f32")
+        _lib.call("cgnn_head_fwd_f32", p, bsz, h, h2, c, w1, b1, w2, b2, p_eff, seed,
+                  rng_word if p_eff > 0 else None, h1, fac, logits, device=dev)
         if record is not None:
             record["head_factor"] = fac          # relu'(z) * keep / (1 - p) per hidden unit
         ctx.save_for_backward(p, w1, w2, h1, fac)
@@ -820,11 +708,8 @@ class _Head(torch.autograd.Function):
             slab = torch.empty(rows, wd, dtype=torch.float32, device=dev)
             dp = torch.empty_like(p)
             flat = torch.empty(wd, dtype=torch.float32, device=dev)
-            _lib.check(lib.cgnn_head_bwd_f32(_lib.ptr(dl), _lib.ptr(p), _lib.ptr(h1), _lib.ptr(fac), bsz, h,
-                                             h2, c, _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(dp), _lib.ptr(slab), _lib.nbytes(slab),
-                                             _lib.stream_ptr()), "cgnn_head_bwd_f32")
-            _lib.check(lib.cgnn_slab_reduce_f32(_lib.ptr(slab), rows, 1, wd, wd, _lib.ptr(flat), wd,
-                                                _lib.stream_ptr()), "cgnn_slab_reduce_f32")
+            _lib.call("cgnn_head_bwd_f32", dl, p, h1, fac, bsz, h, h2, c, w1, w2, dp, *_lib.buf(slab))
+            _lib.call("cgnn_slab_reduce_f32", slab, rows, 1, wd, wd, flat, wd)
         o1, o2, o3 = h2 * h, h2 * h + h2, h2 * h + h2 + c * h2
         return (dp, flat[:o1].view(h2, h), flat[o1:o2], flat[o2:o3].view(c, h2), flat[o3:],
                 None, None, None, None)
@@ -861,16 +746,13 @@ class _HeadLoss(torch.autograd.Function):
             rows = int(lib.cgnn_head_loss_grid(bsz, h, h2, c))
             slab = torch.empty(rows, wd + 1, **f32)
             sp = _lib.stream_ptr()
-            _lib.check(lib.cgnn_head_loss_f32(_lib.ptr(p), bsz, h, h2, c, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
-                                              _lib.ptr(b2), _lib.ptr(labels.contiguous()), p_eff, seed,
-                                              rng_word if p_eff > 0 else None, _lib.ptr(h1), _lib.ptr(fac),
-                                              _lib.ptr(logits), _lib.ptr(dp), _lib.ptr(slab), _lib.nbytes(slab), sp), "cgnn_head_loss_f32")
+            _lib.call("cgnn_head_loss_f32", p, bsz, h, h2, c, w1, b1, w2, b2, labels.contiguous(), p_eff, seed,
+                      rng_word if p_eff > 0 else None, h1, fac, logits, dp, *_lib.buf(slab), stream=sp)
             if grad_dst is not None:
-                _lib.check(lib.cgnn_slab_reduce_f32_split(_lib.ptr(slab), rows, wd + 1, wd, _lib.ptr(grad_dst),
-                                                          flat.data_ptr() + 4 * wd, sp), "cgnn_slab_reduce_f32_split")
+                _lib.call("cgnn_slab_reduce_f32_split", slab, rows, wd + 1, wd, grad_dst, flat.data_ptr() + 4 * wd,
+                          stream=sp)
             else:
-                _lib.check(lib.cgnn_slab_reduce_f32(_lib.ptr(slab), rows, 1, wd + 1, wd + 1, _lib.ptr(flat), wd + 1, sp),
-                           "cgnn_slab_reduce_f32")
+                _lib.call("cgnn_slab_reduce_f32", slab, rows, 1, wd + 1, wd + 1, flat, wd + 1, stream=sp)
         if record is not None:
             record["head_factor"] = fac
         ctx.save_for_backward(p, w1, w2, h1, fac, dp, flat)
@@ -904,11 +786,8 @@ class _HeadLoss(torch.autograd.Function):
                 slab = torch.empty(rows, wd, dtype=torch.float32, device=p.device)
                 dp2 = torch.empty_like(p)
                 fl2 = torch.empty(wd, dtype=torch.float32, device=p.device)
-                _lib.check(lib.cgnn_head_bwd_f32(_lib.ptr(dl), _lib.ptr(p), _lib.ptr(h1), _lib.ptr(fac), bsz, h, h2, c,
-                                                 _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(dp2), _lib.ptr(slab), _lib.nbytes(slab),
-                                                 _lib.stream_ptr()), "cgnn_head_bwd_f32")
-                _lib.check(lib.cgnn_slab_reduce_f32(_lib.ptr(slab), rows, 1, wd, wd, _lib.ptr(fl2), wd,
-                                                    _lib.stream_ptr()), "cgnn_slab_reduce_f32")
+                _lib.call("cgnn_head_bwd_f32", dl, p, h1, fac, bsz, h, h2, c, w1, w2, dp2, *_lib.buf(slab))
+                _lib.call("cgnn_slab_reduce_f32", slab, rows, 1, wd, wd, fl2, wd)
             extra = [dp2, fl2[:o1].view(h2, h), fl2[o1:o2], fl2[o2:o3].view(c, h2), fl2[o3:]]
             outs = extra if outs is None else [b if a is None else a + b for a, b in zip(outs, extra)]
         if outs is None:
@@ -1013,7 +892,6 @@ class _CrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels):
-        lib = _lib.load()
         logits = _prep(logits, "logits")
         _require_device(labels, "labels")
         if labels.dtype != torch.int64:
@@ -1021,10 +899,7 @@ class _CrossEntropy(torch.autograd.Function):
         bsz, c = logits.shape
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         dl = torch.empty_like(logits)
-        with _lib.device_guard(logits.device):
-            _lib.check(lib.cgnn_cross_entropy_f32(_lib.ptr(logits), _lib.ptr(labels.contiguous()), bsz, c,
-                                                  _lib.ptr(loss), _lib.ptr(dl), _lib.stream_ptr()),
-                       "cgnn_cross_entropy_f32")
+        _lib.call("cgnn_cross_entropy_f32", logits, labels.contiguous(), bsz, c, loss, dl, device=logits.device)
         ctx.save_for_backward(dl)
         return loss
 

@@ -13,8 +13,6 @@ counter (``state[p]['step']`` is the same 0-dim fp32 device tensor for every par
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -111,15 +109,13 @@ class Adam(torch.optim.Adam):
             return loss
         if self._plan is None or self._plan[0] != self._current_key():
             self._plan = self._build_plan()
-        lib = _lib.load()
         launches = self._plan[1]
         with _lib.device_guard(dev):
             sp = _lib.stream_ptr(dev)
             for i, (jb, gi) in enumerate(launches):
                 grp = self.param_groups[gi]
                 b1, b2 = grp["betas"]
-                _lib.check(lib.cgnn_adam_step(
-                    ctypes.byref(jb), _lib.ptr(self._shared_step), _lib.ptr(self._arrivals),
-                    int(i == len(launches) - 1), float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
-                    float(grp["weight_decay"]), sp), "cgnn_adam_step")
+                _lib.call("cgnn_adam_step", jb, self._shared_step, self._arrivals, int(i == len(launches) - 1),
+                          float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
+                          stream=sp)
         return loss

@@ -67,12 +67,9 @@ def _assemble_ragged(ds: RaggedPackedDataset, subject_ids: torch.Tensor, host_id
     edge_weight = torch.empty(ne, dtype=torch.float32, device=dev)
     # all zeros when the batch has no edge: the library then launches and writes nothing
     eptr_dev = (torch.empty if ne else torch.zeros)(b + 1, dtype=torch.int32, device=dev)
-    with _lib.device_guard(dev):
-        _lib.check(_lib.load().cgnn_collate_edges(
-            _lib.ptr(ds.edge_local), _lib.ptr(ds.edge_weight), _lib.ptr(ds.edge_ptr_dev), ds.num_subjects,
-            int(ds.edge_weight.numel()), _lib.ptr(ids), b, n, ne, _lib.ptr(edge_index), _lib.nbytes(edge_index),
-            _lib.ptr(edge_weight), _lib.nbytes(edge_weight), _lib.ptr(eptr_dev), _lib.nbytes(eptr_dev),
-            _lib.stream_ptr(dev)), "cgnn_collate_edges")
+    _lib.call("cgnn_collate_edges", ds.edge_local, ds.edge_weight, ds.edge_ptr_dev, ds.num_subjects,
+              int(ds.edge_weight.numel()), ids, b, n, ne, *_lib.buf(edge_index), *_lib.buf(edge_weight),
+              *_lib.buf(eptr_dev), device=dev)
     out = ConnectomeBatch(
         node_features=ds.x.index_select(0, ids).reshape(b * n, -1),
         edge_index=edge_index,

@@ -136,7 +136,7 @@ class SageEncode(torch.autograd.Function):
                 z = None
                 if bn.training:
                     # projection with the BatchNorm statistics of its output in the epilogue
-                    z, slab = linear_fwd_stats(lib, *gemm_in, b, grid)
+                    z, slab = linear_fwd_stats(*gemm_in, b, grid)
                 if z is None:
                     z = ops.linear_fwd_raw(*gemm_in, b, True)
                 bn.forward(z, gamma, beta, slab)

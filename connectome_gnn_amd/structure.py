@@ -188,25 +188,17 @@ class BatchStructure:
                 eptr_dev = getattr(batch, "_eptr_dev", None)      # left on the device by the ragged collate
                 if eptr_dev is None or eptr_dev.device != dev or eptr_dev.numel() != eptr.numel():
                     eptr_dev = eptr.to(device=dev, dtype=torch.int32)
-                rc = lib.cgnn_csr_build_grouped(
-                    _lib.ptr(ei), _lib.ptr(s.gptr), _lib.ptr(eptr_dev),
-                    batch.num_graphs, nn_, ne, s.max_nodes_per_graph, emax,
-                    _lib.ptr(s.rowptr_dst), _lib.ptr(s.eid_dst), _lib.ptr(s.col_dst),
-                    _lib.ptr(s.rowptr_src), _lib.ptr(s.eid_src), _lib.ptr(s.col_src),
-                    _lib.ptr(flags), _lib.stream_ptr(dev))
+                rc = _lib.call("cgnn_csr_build_grouped", ei, s.gptr, eptr_dev, batch.num_graphs, nn_, ne,
+                               s.max_nodes_per_graph, emax, s.rowptr_dst, s.eid_dst, s.col_dst,
+                               s.rowptr_src, s.eid_src, s.col_src, flags, accept=(_lib.CGNN_EUNSUPPORTED,))
                 if rc == _lib.CGNN_OK:
                     f = flags.tolist()              # one sync per batch, at build time only
                     if f[0] or f[1]:
                         f = None                    # not grouped after all: generic build decides
-                elif rc != _lib.CGNN_EUNSUPPORTED:
-                    _lib.check(rc, "cgnn_csr_build_grouped")
             if f is None:
                 ws = torch.empty(int(lib.cgnn_csr_workspace_bytes(nn_, ne)), dtype=torch.uint8, device=dev)
-                _lib.check(lib.cgnn_csr_build(
-                    _lib.ptr(ei), _lib.ptr(node_graph), nn_, ne,
-                    _lib.ptr(s.rowptr_dst), _lib.ptr(s.eid_dst), _lib.ptr(s.col_dst),
-                    _lib.ptr(s.rowptr_src), _lib.ptr(s.eid_src), _lib.ptr(s.col_src),
-                    _lib.ptr(flags), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr(dev)), "cgnn_csr_build")
+                _lib.call("cgnn_csr_build", ei, node_graph, nn_, ne, s.rowptr_dst, s.eid_dst, s.col_dst,
+                          s.rowptr_src, s.eid_src, s.col_src, flags, *_lib.buf(ws))
                 f = flags.tolist()                  # one sync per batch, at build time only
         if f[0]:
             # the reference would raise from scatter_add_/index (models.py:104,112)
@@ -287,34 +279,25 @@ class BatchStructure:
     # -- normalisations: layer independent, recomputed once per forward pass ----------------
     def gcn_norm(self) -> GcnNorm:
         """models.py:94-108 via cgnn_gcn_norm."""
-        lib = _lib.load()
         dev = self.rowptr_dst.device
         f32 = dict(dtype=torch.float32, device=dev)
         n = GcnNorm(torch.empty(self.num_nodes, **f32), torch.empty(self.num_nodes, **f32),
                     torch.empty(self.num_edges, **f32), torch.empty(self.num_edges, **f32))
-        with _lib.device_guard(dev):
-            _lib.check(lib.cgnn_gcn_norm(
-                _lib.ptr(self._edge_index), _lib.ptr(self._edge_weight), self.num_nodes,
-                self.num_edges, _lib.ptr(self.rowptr_dst), _lib.ptr(self.eid_dst),
-                _lib.ptr(self.rowptr_src), _lib.ptr(self.eid_src), _lib.ptr(n.dis),
-                _lib.ptr(n.selfc), _lib.ptr(n.coef_dst), _lib.ptr(n.coef_src),
-                _lib.stream_ptr()), "cgnn_gcn_norm")
+        _lib.call("cgnn_gcn_norm", self._edge_index, self._edge_weight, self.num_nodes, self.num_edges,
+                  self.rowptr_dst, self.eid_dst, self.rowptr_src, self.eid_src, n.dis, n.selfc, n.coef_dst, n.coef_src,
+                  device=dev)
         return n
 
     def sage_norm(self, backward_coef: bool = True) -> SageNorm:
         """models.py:146-149 via cgnn_sage_norm.  backward_coef=False skips the per-edge
         w_e / den[dst_e] array of the gather-form backward (the tiled form divides by den itself)."""
-        lib = _lib.load()
         dev = self.rowptr_dst.device
         f32 = dict(dtype=torch.float32, device=dev)
         n = SageNorm(torch.empty(self.num_nodes, **f32), torch.empty(self.num_edges, **f32),
                      torch.empty(self.num_edges, **f32) if backward_coef else None)
-        with _lib.device_guard(dev):
-            _lib.check(lib.cgnn_sage_norm(
-                _lib.ptr(self._edge_index), _lib.ptr(self._edge_weight), self.num_nodes,
-                self.num_edges, _lib.ptr(self.rowptr_dst), _lib.ptr(self.eid_dst),
-                _lib.ptr(self.rowptr_src), _lib.ptr(self.eid_src), _lib.ptr(n.den),
-                _lib.ptr(n.w_dst), _lib.ptr(n.coef_src_bwd), _lib.stream_ptr()), "cgnn_sage_norm")
+        _lib.call("cgnn_sage_norm", self._edge_index, self._edge_weight, self.num_nodes, self.num_edges,
+                  self.rowptr_dst, self.eid_dst, self.rowptr_src, self.eid_src, n.den, n.w_dst, n.coef_src_bwd,
+                  device=dev)
         return n
 
     # -- tiling for the fused per-tile kernels ----------------------------------------------
@@ -360,7 +343,6 @@ class BatchStructure:
         key = ("meta", max_rows, num_workgroups, float(self_weight))
         if key in self._tiles:
             return self._tiles[key]
-        lib = _lib.load()
         dev = self.rowptr_dst.device
         tptr, rows = self.tile_ptr(max_rows, num_workgroups)
         cuts = tptr.cpu().numpy().astype(np.int64)
@@ -376,9 +358,7 @@ class BatchStructure:
                                            ("src", self.rowptr_src, self.col_src, self.eid_src)):
                 blk_off = torch.empty(nb + 1, **i32)
                 scratch = torch.empty(nb // 2048 + 8, **i32)
-                _lib.check(lib.cgnn_bell_plan(_lib.ptr(tptr), _lib.ptr(tile_blk), nt, nb,
-                                              _lib.ptr(rowptr), _lib.ptr(blk_off), _lib.ptr(scratch), _lib.nbytes(scratch),
-                                              _lib.stream_ptr()), "cgnn_bell_plan")
+                _lib.call("cgnn_bell_plan", tptr, tile_blk, nt, nb, rowptr, blk_off, *_lib.buf(scratch))
                 # entries <= 16 * (max degree of the ordering + 1) per block: sized from the degree
                 # bound recorded at CSR build, so no read-back (and no stall of the stream) here
                 maxdeg = self.max_in_degree if name == "dst" else self.max_out_degree
@@ -386,16 +366,11 @@ class BatchStructure:
                 if total > 2 ** 31 - 17:
                     raise ValueError("blocked-ELL of this batch exceeds 2^31 entries; use smaller batches")
                 ent = torch.empty(max(total, 1) * 8, dtype=torch.uint8, device=dev)
-                _lib.check(lib.cgnn_bell_fill(_lib.ptr(tptr), _lib.ptr(tile_blk), nt,
-                                              _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(eid),
-                                              _lib.ptr(self._edge_weight), float(self_weight),
-                                              _lib.ptr(blk_off), _lib.ptr(ent), _lib.stream_ptr()),
-                           "cgnn_bell_fill")
+                _lib.call("cgnn_bell_fill", tptr, tile_blk, nt, rowptr, col, eid, self._edge_weight,
+                          float(self_weight), blk_off, ent)
                 out[name] = (blk_off, ent)
             w_src = torch.empty(self.num_edges, dtype=torch.float32, device=dev)
-            _lib.check(lib.cgnn_gather_f32(_lib.ptr(self._edge_weight), _lib.ptr(self.eid_src),
-                                           self.num_edges, _lib.ptr(w_src), _lib.stream_ptr()),
-                       "cgnn_gather_f32")
+            _lib.call("cgnn_gather_f32", self._edge_weight, self.eid_src, self.num_edges, w_src)
         m = FusedMeta(tptr, tile_blk, rows, nb, out["dst"][0], out["dst"][1], out["src"][0],
                       out["src"][1], w_src)
         self._tiles[key] = m
@@ -428,13 +403,9 @@ class BatchStructure:
             hit = self._dis
             if hit is not None and hit[0] is meta:
                 return hit[1]
-        lib = _lib.load()
         dev = self.rowptr_dst.device
         dis = torch.empty(self.num_nodes, dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            _lib.check(lib.cgnn_gcn_dis(_lib.ptr(meta.w_src), _lib.ptr(self.rowptr_src),
-                                        self.num_nodes, _lib.ptr(dis), _lib.stream_ptr()),
-                       "cgnn_gcn_dis")
+        _lib.call("cgnn_gcn_dis", meta.w_src, self.rowptr_src, self.num_nodes, dis, device=dev)
         if kept and not torch.cuda.is_current_stream_capturing():
             self._dis = (meta, dis)       # (never a tensor from a graph's pool)
         return dis

@@ -267,9 +267,7 @@ class ResidentBatch(ConnectomeBatch):
                 assert src.is_contiguous()
                 jobs.src[i], jobs.dst[i] = src.data_ptr(), dst.data_ptr()
                 jobs.row_bytes[i] = src[0].numel() * src.element_size()
-            with _lib.device_guard(dev):
-                _lib.check(_lib.load().cgnn_gather_rows(jobs, _lib.ptr(self._ids), self._b, _lib.ptr(self._ids_offset),
-                                                        _lib.stream_ptr(dev)), "cgnn_gather_rows")
+            _lib.call("cgnn_gather_rows", jobs, self._ids, self._b, self._ids_offset, device=dev)
 
     def _assembled_family(self, kind):
         """A family's (blk_off_dst, blk_off_src, norm) of this batch; a family the cache builds only now

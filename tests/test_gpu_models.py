@@ -1243,3 +1243,30 @@ def test_capture_with_a_live_earlier_autograd_graph_raises_instead_of_crashing(m
     assert "captured + replayed ok" in r.stdout
     if mode == "keep":
         assert "detected:" in r.stdout
+
+
+def test_kernel_timer_keys_the_benchmark_reads_are_recorded(monkeypatch):
+    """bench.py's roofline line reads per-kernel times from a KernelTimer under fixed keys; a key that no launch
+    records any more prints 0 there without failing anything.  One eager forward + backward on the smallest batch
+    that reaches each path (the rows of tools/encoder_bits.py), and every key must have recorded a launch."""
+    import connectome_gnn_amd as C
+    from connectome_gnn_amd import _lib
+    gen = C.generate_dataset
+    cases = [("cgnn_gcn_fused_bwd", 64, lambda: gen(4, 84, 8, seed=1)),                                   # "tile"
+             ("cgnn_aggregate_tiled_f32[F=128]", 128, lambda: gen(4, 84, 8, seed=2)),                     # "wide h128"
+             ("cgnn_band_aggregate_f32+cgnn_aggregate_acc_f32[F=64]", 64,
+              lambda: gen(2, 400, 6, seed=3) + gen(1, 30, 4, seed=4)),                                    # "wide 400 band"
+             # more than 1024 nodes in a graph: no band operator, the plain CSR gather aggregate ("wide 1100")
+             ("cgnn_aggregate_f32[F=64]", 64, lambda: gen(1, 1100, 6, seed=9) + gen(1, 30, 4, seed=4))]
+    timer = _lib.KernelTimer([key for key, _, _ in cases])
+    monkeypatch.setattr(_lib, "TIMER", timer)
+    for key, hidden, make in cases:
+        torch.manual_seed(11)
+        m = C.GCNConnectome(5, hidden, dropout=0.3).to(DEV).train()
+        b = C.collate_graphs(make()).to(DEV)
+        torch.nn.functional.cross_entropy(m(b), b.labels).backward()
+    torch.cuda.synchronize()
+    counts = {key: len(timer.events[key]) for key, _, _ in cases}
+    print(counts)
+    assert all(n >= 1 for n in counts.values()), counts
+    assert all(ms >= 0.0 for key in counts for ms in timer.ms(key))

@@ -51,6 +51,112 @@ def test_library_exports_every_declared_symbol():
     assert loaded.cgnn_csr_workspace_bytes(-1, 0) < 0          # CGNN_EINVAL, no crash
 
 
+_HEADER_STRUCTS = {"cgnn_tiles": _lib.CgnnTiles, "cgnn_l0src": _lib.CgnnL0Src, "cgnn_bn_tail": _lib.CgnnBnTail,
+                   "cgnn_dw_jobs": _lib.CgnnDwJobs, "cgnn_adam_jobs": _lib.CgnnAdamJobs,
+                   "cgnn_gather_jobs": _lib.CgnnGatherJobs, "cgnn_reduce_jobs": _lib.CgnnReduceJobs}
+_HEADER_SCALARS = {"int": _lib.I32, "int32_t": _lib.I32, "int64_t": _lib.I64, "uint64_t": _lib.U64,
+                   "float": _lib.F32, "double": _lib.F64}
+
+
+def _header_ctype(decl: str, is_return: bool = False):
+    """The ctypes type of one C parameter (or return type) as include/cgnn.h writes it."""
+    words = decl.replace("*", " * ").split()
+    if "*" not in words:
+        base = [w for w in words if w != "const"][0]
+        return ctypes.c_int if (is_return and base == "int") else _HEADER_SCALARS[base]
+    base = [w for w in words[:words.index("*")] if w != "const"][0]
+    if base == "char":
+        return ctypes.c_char_p
+    return ctypes.POINTER(_HEADER_STRUCTS[base]) if base in _HEADER_STRUCTS else _lib.DevPtr
+
+
+def _abi_mismatches(header: str) -> set:
+    """Names whose declaration in ``header`` and whose row of _lib.PROTOTYPES differ in the return type or in any
+    argument type (or that only one of the two has)."""
+    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    declared = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        declared[name] = (_header_ctype(ret, True), [_header_ctype(p) for p in params])
+    bad = set(declared) ^ set(_lib.PROTOTYPES)
+    for name in set(declared) & set(_lib.PROTOTYPES):
+        res, args = _lib.PROTOTYPES[name]
+        if declared[name] != (res, list(args)):
+            bad.add(name)
+    return bad
+
+
+def test_prototypes_match_the_header_type_by_type():
+    """Return type and every argument type of all 127 rows of _lib.PROTOTYPES against include/cgnn.h -- and the
+    comparison itself against a doctored header (one widened integer, one dropped parameter), so that a parser
+    that matches nothing cannot pass."""
+    hdr = open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    assert len(_lib.PROTOTYPES) == 127
+    assert _abi_mismatches(hdr) == set()
+    one = "int cgnn_rng_advance(uint32_t* state, int32_t n, void* stream);"
+    two = "int cgnn_bn_reduce(const double* slab, int32_t rows, int32_t width, double* sums, void* stream);"
+    assert one in hdr and two in hdr
+    doctored = hdr.replace(one, one.replace("int32_t n", "int64_t n")).replace(two, two.replace("int32_t width, ", ""))
+    assert _abi_mismatches(doctored) == {"cgnn_rng_advance", "cgnn_bn_reduce"}
+
+
+def test_devptr_through_a_foreign_call():
+    """DevPtr as an argtype of libc's memcmp: tensors, their addresses as ints and None (NULL) are taken, in any
+    mix, with the same answer; a float or a str is refused with the argument's position."""
+    memcmp = ctypes.CDLL(None).memcmp
+    memcmp.restype, memcmp.argtypes = ctypes.c_int, [_lib.DevPtr, _lib.DevPtr, ctypes.c_size_t]
+    a = torch.arange(1000, dtype=torch.int64)
+    same, other = a.clone(), a.clone()
+    other[999] += 1
+    n = _lib.nbytes(a)
+    for b, equal in ((same, True), (other, False)):
+        answers = {memcmp(a, b, n) == 0, memcmp(a.data_ptr(), b, n) == 0, memcmp(a, b.data_ptr(), n) == 0,
+                   memcmp(_lib.ptr(a), _lib.ptr(b), n) == 0}
+        assert answers == {equal}
+    assert memcmp(None, None, 0) == 0
+    for bad in (1.5, "a"):
+        with pytest.raises(ctypes.ArgumentError, match="argument 2"):
+            memcmp(a, bad, n)
+
+
+class _StubLib:
+    """Stands in for the loaded library: every cgnn_* attribute is a callable that records its arguments and
+    returns ``rc``."""
+
+    def __init__(self, rc=0):
+        self.rc, self.calls = rc, []
+
+    def __getattr__(self, name):
+        if not name.startswith("cgnn_"):
+            raise AttributeError(name)
+        return lambda *args: (self.calls.append((name, args)), self.rc)[1]
+
+
+def test_call_appends_the_stream_checks_the_code_and_leaves_torch_cuda_alone(monkeypatch):
+    """_lib.call against a stub library.  This machine has no GPU: with stream= given, a call that touched torch.cuda
+    (device guard, stream lookup, events) would raise -- with no timer installed, and with one that does not name
+    the key."""
+    t = torch.zeros(4)
+    for timer in (None, _lib.KernelTimer(["cgnn_other", "cgnn_x[F=8]"])):
+        stub = _StubLib()
+        monkeypatch.setattr(_lib, "_lib", stub)
+        monkeypatch.setattr(_lib, "TIMER", timer)
+        assert _lib.call("cgnn_x", t, 3, *_lib.buf(t), stream=0x1234) == _lib.CGNN_OK
+        assert _lib.call("cgnn_x", None, stream=0x5678, key="cgnn_x[F=64]") == _lib.CGNN_OK
+        assert stub.calls == [("cgnn_x", (t, 3, t, 16, 0x1234)), ("cgnn_x", (None, 0x5678))]
+        stub.rc = _lib.CGNN_EUNSUPPORTED
+        assert _lib.call("cgnn_x", stream=1, accept=(_lib.CGNN_EUNSUPPORTED,)) == _lib.CGNN_EUNSUPPORTED
+        with pytest.raises(_lib.CgnnError, match=r"cgnn_x failed: CGNN_EUNSUPPORTED"):
+            _lib.call("cgnn_x", stream=1)
+        stub.rc = _lib.CGNN_EINVAL
+        with pytest.raises(_lib.CgnnError, match=r"cgnn_y failed: CGNN_EINVAL"):
+            _lib.call("cgnn_y", stream=1, accept=(_lib.CGNN_EUNSUPPORTED,))
+        assert [c[1][-1] for c in stub.calls[2:]] == [1, 1, 1]
+    assert _lib.buf(None) == (None, 0)
+
+
 def test_tiles_struct_layout_matches_header():
     t = _lib.CgnnTiles()
     assert ctypes.sizeof(t) == 8 + 4 + 4 + 7 * 8

@@ -2,8 +2,6 @@
 (tests/shrinkage_data.py) against scikit-learn and on the cases whose answer is known, every refusal of
 ``ledoit_wolf_shrinkage`` / ``partial_correlation`` / ``correlation_matrices`` / ``from_timeseries`` that the new
 arguments add, and the two new functions of the C ABI."""
-import ctypes
-
 import pytest
 import torch
 
@@ -176,7 +174,7 @@ def test_the_estimate_refuses_what_the_correlation_refuses():
 def test_the_binding_declares_both_symbols():
     for name, args in (("cgnn_ingest_shrinkage", 11), ("cgnn_ingest_partial_each", 10)):
         assert name in _lib.PROTOTYPES and len(_lib.PROTOTYPES[name][1]) == args
-    assert _lib.PROTOTYPES["cgnn_ingest_partial_each"][1][3] is ctypes.c_void_p          # shrinkage: a device pointer
+    assert _lib.PROTOTYPES["cgnn_ingest_partial_each"][1][3] is _lib.DevPtr              # shrinkage: a device pointer
     assert _lib.ABI_VERSION == 2 and _lib.load().cgnn_abi_version() == 2
 
 

@@ -98,8 +98,8 @@ def wide_tables(out: dict) -> None:
         kpad = (K + 31) // 32 * 32
         print(f"cgnn_ingest_filter T = {T}, K = {K}: Kpad = {kpad}", file=sys.stderr)
         res = torch.empty_like(ts)
-        ingest._call(ts.device, "cgnn_ingest_filter", _lib.ptr(ts), S, T, n, (ctypes.c_int32 * K)(*range(1, K + 1)), K, 0,
-                     ingest._WORK, *ingest._buf(res), workspace=("cgnn_ingest_filter", S, T, n, K))
+        ingest._call(ts.device, "cgnn_ingest_filter", ts, S, T, n, (ctypes.c_int32 * K)(*range(1, K + 1)), K, 0,
+                     ingest._WORK, *_lib.buf(res), workspace=("cgnn_ingest_filter", S, T, n, K))
         out[f"n{n} T{T}: filter Kpad {kpad}"] = digest(res)
 
 

@@ -29,7 +29,7 @@ def bwd_w():
                                                2 * h, m, h, _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()), "bw")
 
 
-fns = {"fwd+stats K=256 N=128": lambda: bn_stage.linear_fwd_stats(lib, x1, x2, w, b, grid),
+fns = {"fwd+stats K=256 N=128": lambda: bn_stage.linear_fwd_stats(x1, x2, w, b, grid),
        "bwd_input N=128 K=256": lambda: ops.linear_bwd_input_raw(dy, w, 0, 2 * h),
        "bwd_weight K=256 N=128": bwd_w}
 for tag, fn in fns.items():
