@@ -1,4 +1,4 @@
-"""ctypes binding of libcgnn_hip.so (the C ABI declared in include/cgnn.h).
+"""ctypes binding of libcgnn_hip.so (the C ABI declared in include/cgnn.h and the headers it includes).
 
 This is the binding a maintainer of the reference would add: the reference
 reaches its hot path only through ATen calls in connectome_gnn/models.py:40-152, so the
@@ -276,6 +276,13 @@ PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_butterworth.h declares (cgnn.h includes it), in the same form.
+BUTTERWORTH_PROTOTYPES = {
+    "cgnn_ingest_butterworth_workspace_bytes": (I64, [I64, I32, I32, I32]),
+    "cgnn_ingest_butterworth": (c_int, [P, I64, I32, I32, P, I32, I32, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -294,7 +301,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` or `make -C connectome_gnn_amd/csrc`.  connectome_gnn_amd has no "
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -1,7 +1,7 @@
 // series_request.h -- the host side that the time-series entry points share (filter.hip, timeseries.hip, shrinkage.hip,
-// confounds.hip, interpolate.hip): the bound on the frames of a run, the units of a window request,
-// the component list of a band, and the byte count of an array of floats.  Host code only; every check is CGNN_OK or
-// CGNN_EINVAL and touches no device.
+// confounds.hip, interpolate.hip, butterworth.hip): the bound on the frames of a run, the units of a
+// window request, the component list of a band, and the byte count of an array of floats.  Host code only; every check
+// is CGNN_OK or CGNN_EINVAL and touches no device.
 #pragma once
 #include "common.h"
 

@@ -338,14 +338,51 @@ orthogonal DCT projection centred over all ``T`` frames; then, with ``confounds=
 ``o = filter_timeseries(o, t_r=t_r, sample_mask=m, out=o)``, masked centring.  Censored frames of the result are exactly
 ``0.0``, as everywhere under a mask.  The checks are the unmasked path's (a non-empty band, the smaller set at most
 ``FILTER_MAX_COMPONENTS``); ``interpolate=True`` without a ``sample_mask`` is a ``ValueError``.
+
+A Butterworth band-pass instead of the cosine projection: ``filter_timeseries(..., filter="butterworth",
+order=5)`` is nilearn's ``signal.clean(filter="butterworth")``, its default -- a Butterworth filter of that order run forward
+and backward, zero-phase -- on the device (csrc/butterworth.hip), float32 ``[S, T, n]``; confounds ``[S, T, q]`` are served
+alike.  ``filter`` is one of ``FILTERS``; with ``"cosine"``, the default, nothing above changes and ``order`` must be left
+at its default.  Per subject and column ``i``, with ``sos = butterworth_sos(t_r, high_pass, low_pass, order)``:
+``y = sosfiltfilt(sos, float64(x[s, :, i]))`` as ``scipy.signal.sosfiltfilt`` defines it with its defaults
+(``padtype="odd"``, ``padlen=None``), and ``out[s, :, i] = fl32(y)``: one rounding.
+
+* ``butterworth_sos`` is host code (Python floats, no scipy): the analogue prototype's poles, critical frequencies
+  pre-warped, the low-pass to band or high transform, the bilinear transform, conjugate pairs into second-order sections
+  ``b0 b1 b2 1 a1 a2``, float64 ``[L, 6]``.  Both bounds give a band-pass of ``order`` sections, one bound a high- or
+  low-pass of ``ceil(order / 2)``; ``1 <= order <= BUTTERWORTH_MAX_ORDER = 8``.  The transfer function is
+  ``scipy.signal.butter(order, ..., output="sos", fs=1 / t_r)``'s; the order of the sections and the pairing are not.
+* Unlike the cosine path the result is not centred first: a low-pass keeps a column's level, as scipy and nilearn do.
+* ``ValueError``s, each naming the number that decides: an ``order`` outside the range; bounds not in
+  ``0 < high_pass < low_pass < 1 / (2 t_r)`` (the message names the Nyquist frequency; nilearn clips the bound and warns);
+  both bounds ``None`` (the cosine filter removes the means); ``T <= edge``, scipy's pad length
+  ``3 (2 L + 1 - min(#sections with b2 == 0, #sections with a2 == 0))``: 33 for the default band-pass, 18 for a 5th-order
+  high- or low-pass; ``sample_mask=`` without ``interpolate=True``, a recursive filter cannot skip frames.
+* ``confounds=c`` is ``regress_confounds(butter(timeseries), butter(c))``, which centres.  ``sample_mask=m,
+  interpolate=True`` is the sequence above with the Butterworth call in the projection's place: the series and the
+  confounds interpolated, both filtered over all ``T`` frames, the regression on the kept frames (without confounds:
+  masked centring); censored frames exactly ``0.0``; bit for bit the public calls.
+
+Arithmetic: everything is fp64.  The column is filtered as ``d = double(x) - double(x[0])`` -- the odd extension commutes
+with that shift, and the initial states (``sosfilt_zi``'s, scaled by the first frame) make a constant input give a
+constant output, so ``sosfiltfilt(x) = sosfiltfilt(d) + H(1)^2 x[0]`` with ``H(1)^2`` 0 for a high- or band-pass and 1 for a
+low-pass, for which ``x[0]`` is added back before the one rounding.  So a constant ROI gives exactly ``0.0``, or exactly its
+value under a low-pass, and an offset of 10^4 costs no accuracy.  A section is transposed direct form II,
+``y = fma(b0, x, z0); z0 = fma(-a1, y, fma(b1, x, z1)); z1 = fma(-a2, y, b2 x)``; the value between the forward and the
+backward pass is never rounded to fp32.  One launch, a lane per column; the forward pass keeps the states every 48 frames
+only, in a workspace that depends on ``T`` and the device and not on ``S``, and the backward pass forms the forward outputs
+again chunk by chunk.  A NaN anywhere in a column makes that whole column NaN and no other.  No atomics, no read-back;
+every run, every grid and ``out=timeseries`` give the same bits.  The cost is the same for every band.
 """
 from __future__ import annotations
 
 import ctypes
+import cmath
 import itertools
 import math
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -364,6 +401,9 @@ FILTER_MAX_COMPONENTS = 256                           # CGNN_FILTER_MAX_COMPONEN
 _FILTER_MAX_FRAMES = 2 ** 30                          # cgnn_ingest_filter's bound on T
 CONFOUND_MAX = 64                                     # CGNN_CONFOUND_MAX: the widest table of k_filter's regress form
 CONFOUND_RANK_TOL = 1e-10                             # CGNN_CONFOUND_RANK_TOL: a column is kept iff its pivot d_j exceeds it
+FILTERS = ("cosine", "butterworth")                   # filter_timeseries's filter=
+BUTTERWORTH_MAX_ORDER = 8                             # CGNN_BUTTER_MAX_SECTIONS (cgnn_butterworth.h): a band-pass has `order` sections
+_BUTTERWORTH_ORDER = 5                                # nilearn's
 
 
 class _Family(NamedTuple):
@@ -761,6 +801,100 @@ def interpolate_censored(timeseries: torch.Tensor, sample_mask: torch.Tensor, *,
     return out
 
 
+def _check_order(order) -> int:
+    if isinstance(order, bool) or not isinstance(order, int):
+        raise TypeError(f"order must be an int, got {type(order).__name__}")
+    if not 1 <= order <= BUTTERWORTH_MAX_ORDER:
+        raise ValueError(f"order must lie in [1, BUTTERWORTH_MAX_ORDER] = [1, {BUTTERWORTH_MAX_ORDER}], got {order}")
+    return order
+
+
+def butterworth_sos(t_r, high_pass=None, low_pass=None, order=5) -> np.ndarray:
+    """The second-order sections, float64 ``[L, 6]`` (``b0 b1 b2 1 a1 a2``, a numpy array), of the digital Butterworth filter of
+    that ``order`` for series sampled every ``t_r`` seconds (module docstring): a band-pass of ``order`` sections with
+    both bounds, a high-pass (``high_pass`` alone) or a low-pass (``low_pass`` alone) of ``ceil(order / 2)``.  The
+    transfer function is ``scipy.signal.butter(order, ..., output="sos", fs=1 / t_r)``'s: the analogue prototype's poles,
+    critical frequencies pre-warped, the low-pass to band or high transform, the bilinear transform, conjugate pairs
+    into sections; the order of the sections and the pairing are this function's own.  Every section of a high- or
+    band-pass has ``b0 + b1 + b2 == 0`` exactly.  Host only: Python floats and ``cmath``, no tensor, no device.  Both
+    bounds ``None``, an ``order`` outside ``1 .. BUTTERWORTH_MAX_ORDER`` and a bound outside ``(0, 1 / (2 t_r))`` are
+    ``ValueError``s."""
+    t_r = _finite_number("t_r", t_r)
+    if t_r <= 0.0:
+        raise ValueError(f"t_r must be > 0, got {t_r}")
+    order = _check_order(order)
+    nyquist = 1.0 / (2.0 * t_r)
+    if high_pass is None and low_pass is None:
+        raise ValueError("a Butterworth filter needs high_pass=, low_pass= or both (filter=\"cosine\" without bounds "
+                         "removes the means)")
+    bounds = []
+    for name, f in (("high_pass", high_pass), ("low_pass", low_pass)):
+        if f is None:
+            continue
+        f = _finite_number(name, f)
+        if not 0.0 < f < nyquist:
+            raise ValueError(f"{name} must lie in (0, 1 / (2 t_r)), below the Nyquist frequency {nyquist} Hz at "
+                             f"t_r={t_r}, got {f}")
+        bounds.append(f)
+    if len(bounds) == 2 and not bounds[0] < bounds[1]:
+        raise ValueError(f"high_pass must lie below low_pass, got {bounds[0]} >= {bounds[1]}")
+    # the analogue prototype's poles with a non-negative imaginary part (the others are their conjugates); critical
+    # frequencies pre-warped for the bilinear transform at fs = 2, z = (4 + s) / (4 - s)
+    proto = [-cmath.exp(1j * math.pi * m / (2 * order)) for m in range(order - 1, 0, -2)]
+    if order % 2:
+        proto.append(complex(-1.0, 0.0))              # m == 0: the real pole, exactly
+    warped = [4.0 * math.tan(math.pi * f / nyquist / 2.0) for f in bounds]
+    # the analogue poles of each section: one of a conjugate pair, or the two that the real pole gives a band-pass
+    if len(bounds) == 2:
+        bw, wo = warped[1] - warped[0], math.sqrt(warped[0] * warped[1])
+        groups = []
+        for q in proto:
+            half = q * bw / 2.0
+            root = cmath.sqrt(half * half - wo * wo)
+            groups += [(half + root, half - root)] if q.imag == 0.0 else [(half + root,), (half - root,)]
+        unit = (4.0 + 1j * wo) / (4.0 - 1j * wo)      # the band's centre, where the gain is 1
+    elif high_pass is not None:
+        groups = [(warped[0] / q,) for q in proto]
+        unit = complex(-1.0, 0.0)                     # the Nyquist frequency
+    else:
+        groups = [(q * warped[0],) for q in proto]
+        unit = complex(1.0, 0.0)                      # frequency 0
+    sos = []
+    for group in groups:
+        z = [(4.0 + q) / (4.0 - q) for q in group]
+        if len(z) == 2:                               # two poles, real or each other's conjugates
+            a1, a2 = -(z[0] + z[1]).real, (z[0] * z[1]).real
+        elif z[0].imag != 0.0:                        # a pole and its conjugate
+            a1, a2 = -2.0 * z[0].real, z[0].real ** 2 + z[0].imag ** 2
+        else:                                         # the real pole of an odd low- or high-pass: a first-order section
+            a1, a2 = -z[0].real, 0.0
+        if len(bounds) == 2:
+            b = (1.0, 0.0, -1.0)                      # a zero at +1 and one at -1
+        else:
+            sign = -1.0 if high_pass is not None else 1.0             # zeros at +1 / at -1
+            b = (1.0, 2.0 * sign, 1.0) if a2 != 0.0 else (1.0, sign, 0.0)
+        # the section's gain: 1 at `unit`.  (b0, b1, b2) stay multiples of small integers by one number, so that a
+        # high- or band-pass section has b0 + b1 + b2 == 0 exactly
+        u = 1.0 / unit
+        g = abs((1.0 + u * (a1 + u * a2)) / (b[0] + u * (b[1] + u * b[2])))
+        sos.append([g * b[0], g * b[1], g * b[2], 1.0, a1, a2])
+    return np.array(sos, dtype=np.float64)
+
+
+def _butterworth_edge(sos) -> int:
+    """scipy's default pad length of ``sosfiltfilt`` for these sections."""
+    L = len(sos)
+    return 3 * (2 * L + 1 - min(sum(r[2] == 0.0 for r in sos), sum(r[5] == 0.0 for r in sos)))
+
+
+def _butterworth(timeseries: torch.Tensor, sos, add_level: bool, out: torch.Tensor) -> None:
+    S, T, n = timeseries.shape
+    L = len(sos)
+    flat = (ctypes.c_double * (6 * L))(*(float(v) for row in sos for v in row))
+    _call(timeseries.device, "cgnn_ingest_butterworth", timeseries, S, T, n, flat, L, int(add_level), _WORK,
+          *_lib.buf(out), workspace=("cgnn_ingest_butterworth", S, T, n, L))
+
+
 def _filter_interpolated(timeseries: torch.Tensor, band: dict, confounds, keep, out) -> torch.Tensor:
     """``filter_timeseries(..., sample_mask=, interpolate=True)``: the sequence of public calls of the module docstring."""
     _require_resident(timeseries, *_SERIES)
@@ -773,8 +907,39 @@ def _filter_interpolated(timeseries: torch.Tensor, band: dict, confounds, keep, 
     return regress_confounds(out, clean, sample_mask=keep, out=out)
 
 
+def _filter_butterworth(timeseries, t_r, high_pass, low_pass, order, out, confounds, sample_mask,
+                        interpolate: bool) -> torch.Tensor:
+    """``filter_timeseries(..., filter="butterworth")``: the checks, then one launch, or the composition around it."""
+    S, T, n = _check_run(timeseries)[:3]
+    sos = butterworth_sos(t_r, high_pass, low_pass, order)
+    edge = _butterworth_edge(sos)
+    if T <= edge:
+        raise ValueError(f"a Butterworth filter of {len(sos)} sections pads both ends with edge = {edge} mirrored "
+                         f"frames (scipy's default): the run must have T > {edge} frames, got T = {T}")
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+    if keep is not None and not interpolate:
+        raise ValueError("a Butterworth filter is recursive and cannot skip the censored frames of a sample_mask: pass "
+                         "interpolate=True, which replaces them first")
+    _check_out(out, timeseries)
+    if confounds is not None:
+        _check_confounds(confounds, S, T, timeseries.device)
+    band = dict(t_r=t_r, high_pass=high_pass, low_pass=low_pass, filter="butterworth", order=order)
+    if interpolate:
+        return _filter_interpolated(timeseries, band, confounds, keep, out)
+    out = _resident_out(timeseries, out)
+    if S == 0:
+        return out
+    _butterworth(timeseries, sos, high_pass is None, out)             # a low-pass keeps the level
+    if confounds is not None:                         # the same filter on the confounds, then out -= Q (Q^T out) in place
+        clean = filter_timeseries(confounds, **band)
+        basis, _ = _confound_basis(clean)
+        del clean
+        _regress(out, basis, out)
+    return out
+
+
 def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass=None, out=None,
-                      confounds=None, sample_mask=None, interpolate=False) -> torch.Tensor:
+                      confounds=None, sample_mask=None, interpolate=False, filter="cosine", order=5) -> torch.Tensor:
     """The time series centred and band-passed column by column, by projection on the DCT-II components
     ``filter_components(T, t_r, high_pass, low_pass)`` of the whole run: float32 ``[S, T, n]`` on the time series'
     device (module docstring), what ``correlation_matrices``, ``ledoit_wolf_shrinkage`` and ``from_timeseries`` take.
@@ -796,11 +961,27 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
     (without confounds: the kept frames are centred); exactly that sequence of public calls (module docstring), under
     the checks of the unmasked path, the censored frames of the result exactly ``0.0``.  Its temporaries are the
     interpolated and filtered confounds and their basis, the filter's table and means, and the interpolation
-    workspace."""
+    workspace.  ``filter`` is one of ``FILTERS``.  ``"cosine"``, the default, is all of the above, and ``order`` must
+    then be left at its default.  ``"butterworth"`` is nilearn's default instead, a zero-phase Butterworth filter of
+    that ``order`` (``1 .. BUTTERWORTH_MAX_ORDER``): every column through ``scipy.signal.sosfiltfilt`` of
+    ``butterworth_sos(t_r, high_pass, low_pass, order)`` with scipy's default padding, in fp64 with one rounding to
+    fp32 (module docstring); one launch, the same cost for every band and every ``T``, its temporary the slab of
+    boundary states (which depends on ``T`` and the device, not on ``S``).  At least one bound is needed, each inside
+    ``(0, 1 / (2 t_r))``, and ``T`` must exceed scipy's pad length (33 for the default band-pass).  The result is not
+    centred first: a low-pass keeps a column's level.  ``out``, ``confounds`` and ``sample_mask=, interpolate=True``
+    are as above with the Butterworth call in the projection's place; a ``sample_mask`` without ``interpolate=True``
+    is a ``ValueError``, a recursive filter cannot skip frames."""
+    if filter not in FILTERS:
+        raise ValueError(f"unknown filter {filter!r}: the filters are FILTERS = {FILTERS}")
     if not isinstance(interpolate, bool):
         raise TypeError(f"interpolate must be a bool, got {type(interpolate).__name__}")
     if interpolate and sample_mask is None:
         raise ValueError("interpolate=True replaces the censored frames: give sample_mask= with it")
+    if filter == "butterworth":
+        return _filter_butterworth(timeseries, t_r, high_pass, low_pass, order, out, confounds, sample_mask, interpolate)
+    if isinstance(order, bool) or order != _BUTTERWORTH_ORDER:
+        raise ValueError(f"order={order!r} belongs to filter=\"butterworth\": filter=\"cosine\" takes order="
+                         f"{_BUTTERWORTH_ORDER}, its default, only")
     S, T, n = _check_run(timeseries)[:3]
     k_lo, k_hi = filter_components(T, t_r, high_pass, low_pass)
     if k_lo > k_hi:

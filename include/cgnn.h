@@ -1356,4 +1356,8 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 #ifdef __cplusplus
 }
 #endif
+
+/* Entry points declared in headers of their own; including cgnn.h includes them. */
+#include "cgnn_butterworth.h"
+
 #endif /* CGNN_H */
