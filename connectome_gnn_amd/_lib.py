@@ -283,6 +283,14 @@ BUTTERWORTH_PROTOTYPES = {
 }
 
 
+# The entry point that include/cgnn_optim.h declares (cgnn.h includes it), in the same form; a row of the
+# hyper-parameter table it reads is {lr, beta1, beta2, eps, weight_decay} padded to ADAM_HYPER_STRIDE doubles.
+ADAM_HYPER_STRIDE = 8
+OPTIM_PROTOTYPES = {
+    "cgnn_adam_step_dev": (c_int, [ctypes.POINTER(CgnnAdamJobs), P, P, I32, P, I32, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -301,7 +309,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` or `make -C connectome_gnn_amd/csrc`.  connectome_gnn_amd has no "
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -49,10 +49,46 @@ from . import ops
 from .structure import call_prepare
 
 
+def _hyper_token(v):
+    """What a captured step remembers of one param-group entry: a tensor by identity and ``_version`` (the tensor is
+    kept, so its identity cannot be reused), anything else by value."""
+    return (v, v._version) if torch.is_tensor(v) else v
+
+
+def hyper_snapshot(param_groups) -> list:
+    """Every entry of every param group except ``"params"``, as a captured step freezes it."""
+    return [{k: _hyper_token(v) for k, v in g.items() if k != "params"} for g in param_groups]
+
+
+def hyper_changed(snapshot: list, param_groups) -> Optional[str]:
+    """None while ``param_groups`` still are what ``snapshot`` recorded, else the first entry that differs, as
+    ``param_groups[i]['key']``.  Numbers, bools, None and tuples of those compare by equality; tensors by identity and
+    ``_version`` (a replaced tensor and one edited in place both count); ``"params"`` is ignored."""
+    if len(snapshot) != len(param_groups):
+        return "len(param_groups)"
+    for gi, (snap, grp) in enumerate(zip(snapshot, param_groups)):
+        for k in list(snap) + [k for k in grp if k != "params" and k not in snap]:
+            if k not in grp or k not in snap:
+                return f"param_groups[{gi}][{k!r}]"
+            was, now = snap[k], grp[k]
+            if torch.is_tensor(now) or (isinstance(was, tuple) and len(was) == 2 and torch.is_tensor(was[0])):
+                same = isinstance(was, tuple) and len(was) == 2 and was[0] is now and was[1] == now._version
+            else:
+                same = was == now
+            if same is not True:                              # (an array-valued or NaN comparison is no proof either)
+                return f"param_groups[{gi}][{k!r}]"
+    return None
+
+
 class GraphedTrainStep:
     """``step = GraphedTrainStep(model, optimizer, batch); loss = step()`` replays the captured
     training step on ``batch`` (a device-resident ConnectomeBatch).  ``loss`` is a static device
-    tensor that every replay overwrites."""
+    tensor that every replay overwrites.
+
+    Hyper-parameters: an optimizer with ``refresh_hyper()`` (optim.Adam / optim.AdamW: the values live in a device table
+    that the captured launch reads when it runs) is refreshed before every replay, so schedules are honoured.  Any
+    other optimizer's launches carry the values of the moment of capture: the step records them (``hyper_snapshot``)
+    and REFUSES to replay once they differ (``hyper_current()`` is then False; the Trainer captures the step again)."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, batch,
                  loss_fn: Optional[Callable] = None, grad_sync: Optional[Callable[[], None]] = None,
@@ -103,6 +139,8 @@ class GraphedTrainStep:
             self.first_loss = first.clone()
         torch.cuda.current_stream(dev).wait_stream(side)
         self._zero()
+        # the hyper-parameters this capture freezes (none, for an optimizer that reads them on the device)
+        self._hyper_snapshot = None if hasattr(optimizer, "refresh_hyper") else hyper_snapshot(optimizer.param_groups)
         self.graph = torch.cuda.CUDAGraph()
         self.graph_tail = None
         # with a process group alive, its watchdog thread polls events while we capture: only THIS
@@ -269,14 +307,45 @@ class GraphedTrainStep:
         else:
             self.grad_sync()
 
-    def __call__(self) -> torch.Tensor:
-        if self.graph is None:
-            raise RuntimeError(f"this step was not captured: {self.capture_error!r}")
+    def hyper_current(self) -> bool:
+        """Whether a replay would still use the optimizer's hyper-parameters as they are now: always, for an optimizer
+        whose values live on the device; else while nothing differs from the snapshot taken at capture."""
+        return self._hyper_snapshot is None or hyper_changed(self._hyper_snapshot, self.optimizer.param_groups) is None
+
+    def _hyper_ready(self) -> None:
+        """Before the first replay of a call: the device table brought up to date on this stream, ahead of the replayed
+        launches that read it -- or, for an optimizer whose values are frozen in the graph, the refusal."""
+        if self._hyper_snapshot is None:
+            self.optimizer.refresh_hyper()
+            return
+        key = hyper_changed(self._hyper_snapshot, self.optimizer.param_groups)
+        if key is not None:
+            raise RuntimeError(
+                f"this captured step froze the optimizer's hyper-parameters and {key} has changed since: a replay "
+                f"would silently use the old value.  Capture the step again, or use connectome_gnn_amd.optim.Adam / "
+                f"AdamW, whose hyper-parameters live on the device and may change between replays.")
+
+    def _replay(self) -> torch.Tensor:
         self.graph.replay()
         if self.graph_tail is not None:
             self._exchange()
             self.graph_tail.replay()
         return self.loss
+
+    def __call__(self) -> torch.Tensor:
+        if self.graph is None:
+            raise RuntimeError(f"this step was not captured: {self.capture_error!r}")
+        self._hyper_ready()
+        return self._replay()
+
+    def release(self) -> None:
+        """Give up the captured graphs and their private pools now (not whenever the garbage collector finds this
+        object: a step that assembles its batch holds a cycle through ``make_batch``).  The step cannot be replayed
+        afterwards."""
+        self.capture_error = self.capture_error or RuntimeError("released")
+        self.graph = self.graph_tail = None
+        self.make_batch = None
+        self.loss = None
 
 
 class GraphedResidentStep(GraphedTrainStep):
@@ -333,6 +402,9 @@ class GraphedResidentStep(GraphedTrainStep):
         n = steps * self._b
         if int(ids.numel()) != n or n > int(self.order_buf.numel()):
             raise ValueError("run_epoch: ids must hold steps x batch_size subject ids (at most the dataset's size)")
+        if self.graph is None:
+            raise RuntimeError(f"this step was not captured: {self.capture_error!r}")
+        self._hyper_ready()             # once, ahead of every replay of this call (and of a capture_run below)
         self.order_buf[:n].copy_(ids, non_blocking=True)      # (ids may be pinned host memory: one upload per epoch)
         self._state.zero_()             # cursor and tally (single-batch calls in between also fed the tally:
                                         # their losses were read directly)
@@ -350,9 +422,13 @@ class GraphedResidentStep(GraphedTrainStep):
                 self._run_graph.replay()
                 done += k
         for _ in range(steps - done):
-            super().__call__()
+            self._replay()
 
-    RUN_MAX_NODES = 65536       # batches up to this many nodes (BASELINE config 2: 43,008) replay 4 steps per graph,
+    def release(self) -> None:
+        super().release()
+        self._run_graph, self._run_failed = None, True
+
+    RUN_MAX_NODES = 65536      # batches up to this many nodes (BASELINE config 2: 43,008) replay 4 steps per graph,
     RUN_MID_NODES = 262144      # up to this many (a 512 x 360 shard: 184,320) 2 steps; larger steps hide the launch
 
     def _run_len(self, steps: int) -> int:

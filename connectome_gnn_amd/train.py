@@ -122,7 +122,17 @@ class Trainer:
         every step) run the ordinary eager step and leave nothing behind.  At
         most ``max_graphs`` steps are kept (each holds its batch and a private pool with every
         activation and gradient of the step); once that many exist, further batches stay eager.
-        The optimizer must be capturable (``torch.optim.Adam(..., capturable=True)``)."""
+        The optimizer must be capturable (``torch.optim.Adam(..., capturable=True)``).
+
+        Learning-rate schedules and other hyper-parameter changes BETWEEN epochs (a ``torch.optim.lr_scheduler``, a
+        manual ``param_groups[i]["lr"] = ...``, a new ``weight_decay``) are honoured by captured steps.  With
+        ``connectome_gnn_amd.optim.Adam`` / ``AdamW`` the values live in a device table that the captured launch reads
+        when it runs: a change costs one small copy and nothing is captured again.  Any other optimizer's captured
+        launches carry the values of the moment of capture, so a step whose optimizer's param groups have changed
+        since is released and captured again on its next batch (that batch's step runs eagerly, as on first
+        sighting); ``hyper_recaptures`` counts these.  A step that went stale ``STALE_RUNS_MAX`` times in a row
+        without ever being replayed (the remainder batch under a per-epoch schedule) stays eager, with one warning.
+        Changes inside an epoch that is replayed as one run are seen at the next epoch."""
         self.device = device
         self.model = model.to(device)
         self.optimizer = optimizer
@@ -136,6 +146,9 @@ class Trainer:
         self.max_graphs = int(max_graphs)
         self._graphs: Dict[tuple, object] = {}
         self._seen: "OrderedDict[tuple, weakref.ref]" = OrderedDict()
+        self.hyper_recaptures = 0                 # captured steps released because a hyper-parameter changed
+        self._stale_runs: Dict[tuple, int] = {}   # per key: stale releases in a row without one replay in between
+        self._eager_keys: set = set()             # keys whose captured step never got to replay: eager from then on
         if self.graph:
             for grp in optimizer.param_groups:
                 if not grp.get("capturable", False):
@@ -275,6 +288,32 @@ class Trainer:
                 batch.labels.data_ptr(), batch.num_nodes, batch.num_graphs, batch.edge_index._version,
                 batch.edge_weight._version)
 
+    STALE_RUNS_MAX = 3        # stale captures of one key in a row, none of them ever replayed, before it stays eager
+
+    def _live_step(self, key: tuple):
+        """The captured training step kept under ``key``, or None -- also when its optimizer's hyper-parameters are no
+        longer what it froze at capture (graphed.GraphedTrainStep.hyper_current): that step is released HERE, before
+        any new capture begins, and the caller's ordinary first-sighting path captures the key again.  (Nothing is
+        ever stale with optim.Adam / optim.AdamW, whose hyper-parameters the captured launch reads on the device.)"""
+        step = self._graphs.get(key)
+        if step is None or step.hyper_current():
+            return step
+        del self._graphs[key]
+        step.release()
+        self.hyper_recaptures += 1
+        runs = self._stale_runs[key] = self._stale_runs.get(key, 0) + 1
+        if runs >= self.STALE_RUNS_MAX:
+            # e.g. the remainder batch under a per-epoch schedule: each capture served no step at all
+            import warnings
+            self._eager_keys.add(key)
+            what = f"batches of {key[2]} graphs" if key[0] == "resident" else "one of the resident batches"
+            warnings.warn(f"Trainer: the captured step for {what} went stale {runs} "
+                          f"times in a row without one replay (the optimizer's hyper-parameters change more often "
+                          f"than the step is reused); it runs eagerly from here.  connectome_gnn_amd.optim.Adam / "
+                          f"AdamW keep their hyper-parameters on the device: their captured steps follow a "
+                          f"schedule and are never captured again.")
+        return None
+
     def _graphed_step(self, batch, borrow: bool = False) -> Optional[torch.Tensor]:
         """Replay (or, on a batch's second sighting, capture) the step; None = run it eagerly."""
         if getattr(batch, "_ids_src", None) is not None and getattr(batch, "_cache", None) is not None:
@@ -282,9 +321,12 @@ class Trainer:
             # batch size serves every composition (the batch is assembled inside the graph from the
             # ids) -- fresh shuffles every epoch replay too
             rkey = ("resident", id(batch._cache), batch.num_graphs)
-            step = self._graphs.get(rkey)
+            step = self._live_step(rkey)
             if step is not None:
+                self._stale_runs.pop(rkey, None)
                 return step(batch) if borrow else step(batch).clone()
+            if rkey in self._eager_keys:
+                return None
             if len(self._graphs) < self.max_graphs:
                 from .graphed import GraphedResidentStep
                 local = batch.num_graphs if isinstance(self.grad_sync, cdist.GradSync) else None
@@ -309,9 +351,12 @@ class Trainer:
                 return step.first_loss        # the warm-up pass WAS this batch's step (eager)
             return None
         key = self._graph_key(batch)
-        step = self._graphs.get(key)
+        step = self._live_step(key)
         if step is not None:
+            self._stale_runs.pop(key, None)
             return step() if borrow else step().clone()
+        if key in self._eager_keys:
+            return None
         # second sighting = the very tensor seen before is still alive (addresses alone recur: the
         # caching allocator hands a fresh batch the block its predecessor just released)
         ref = self._seen.get(key)
@@ -335,6 +380,8 @@ class Trainer:
         """Release every captured step (and its private memory pool)."""
         self._graphs.clear()
         self._seen.clear()
+        self._stale_runs.clear()
+        self._eager_keys.clear()
 
     def train_step(self, batch, _borrow: bool = False) -> torch.Tensor:
         """One optimisation step (reference train.py:46-51); returns the detached device loss.
@@ -377,7 +424,8 @@ class Trainer:
             j = i
             while j < len(chunks) and int(chunks[j].numel()) == size:
                 j += 1
-            step = self._graphs.get(("resident", id(cache), size))
+            rkey = ("resident", id(cache), size)
+            step = self._live_step(rkey)          # (None too for a step whose frozen hyper-parameters went stale)
             if step is None or self._data_parallel():
                 # first sighting of this size (the ordinary path captures it); under data parallelism
                 # the exchange sits between two graphs per step, which the per-batch path handles
@@ -386,6 +434,7 @@ class Trainer:
             else:
                 run = chunks[i:j]
                 ids = run[0] if len(run) == 1 else _joined(run)
+                self._stale_runs.pop(rkey, None)
                 step.run_epoch(ids.to(step.order_buf.device), len(run))
                 tally.add(step.take_tally(), size * len(run))
             i = j

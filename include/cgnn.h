@@ -1188,7 +1188,8 @@ int cgnn_bn_act_bwd_apply_f16(const void* dX, const void* Y, const uint8_t* mask
  * CGNN_ADAM_MAX_JOBS fp32 tensors in ONE launch (reference: torch.optim.Adam in demo.py:105-134).
  * `step` is the shared fp32 step counter on the device (t = *step + 1 is used); with advance != 0
  * the same launch stores *step + 1 once every workgroup has read it (`arrivals`: a zeroed uint32
- * the launch leaves zero again).  Graph-capturable: nothing comes from the host but lr/betas. */
+ * the launch leaves zero again).  Graph-capturable: nothing comes from the host but lr/betas, which
+ * a captured launch therefore keeps; cgnn_adam_step_dev (cgnn_optim.h) reads them from the device. */
 #define CGNN_ADAM_MAX_JOBS 32
 typedef struct cgnn_adam_jobs {
   int32_t n;
@@ -1359,5 +1360,6 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 
 /* Entry points declared in headers of their own; including cgnn.h includes them. */
 #include "cgnn_butterworth.h"
+#include "cgnn_optim.h"
 
 #endif /* CGNN_H */
