@@ -291,6 +291,13 @@ OPTIM_PROTOTYPES = {
 }
 
 
+# The entry point that include/cgnn_knn.h declares (cgnn.h includes it), in the same form, and its modes.
+KNN_DIRECTED, KNN_UNION, KNN_MUTUAL = 0, 1, 2
+KNN_PROTOTYPES = {
+    "cgnn_ingest_knn": (c_int, [P, I64, I32, I64, I32, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -309,7 +316,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` or `make -C connectome_gnn_amd/csrc`.  connectome_gnn_amd has no "
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -373,6 +373,44 @@ backward pass is never rounded to fp32.  One launch, a lane per column; the forw
 only, in a workspace that depends on ``T`` and the device and not on ``S``, and the backward pass forms the forward outputs
 again chunk by chunk.  A NaN anywhere in a column makes that whole column NaN and no other.  No atomics, no read-back;
 every run, every grid and ``out=timeseries`` give the same bits.  The cost is the same for every band.
+
+k-nearest-neighbour sparsification: ``keep=``, ``num_edges=`` and ``min_weight=`` compare every entry
+of a subject with one number, which at the usual densities leaves weakly connected ROIs without any edge.
+``knn_sparsify(matrices, k, mode="union", out=None)`` builds the other standard graph on the device (csrc/knn.hip):
+every ROI keeps its ``k`` strongest connections and the picks are symmetrised.  Everything is per subject, with matrix
+``A`` ``[n, n]``, fp32, any sign, not necessarily symmetric.
+
+* Positive candidates: row ``i`` has ``P_i = { j != i : A_ij > 0 }`` and ``p_i = |P_i|``.  A NaN is not positive,
+  ``+inf`` is, and the diagonal is never a candidate.
+* Order: within a row ``j`` comes before ``j'`` iff ``A_ij > A_ij'``, or ``A_ij == A_ij'`` and ``j < j'``: the stable
+  descending sort.
+* Picks: ``D_i`` is the first ``min(k, p_i)`` members of ``P_i`` in that order, and ``d_ij`` means ``j in D_i``.  A row
+  gets exactly ``min(k, p_i)`` picks; ties are broken by the lower column, and no row is left empty by a tie class that
+  straddles the cut.  This is deliberately NOT the "strictly above the rank-k value" rule of ``keep=``: the guaranteed
+  minimum degree is the reason the call exists.
+* Modes (``KNN_MODES``): ``"directed"``: ``kept_ij = d_ij``; ``"union"``, the default and the usual k-NN graph:
+  ``kept_ij = d_ij or (d_ji and A_ij > 0)``; ``"mutual"``: ``kept_ij = d_ij and d_ji``.
+* Output: ``B_ij`` is the bits of ``A_ij`` where ``kept_ij`` and ``+0.0`` elsewhere; the diagonal and every NaN are
+  ``+0.0`` too.
+
+Consequences: ``from_matrices(B, min_weight=0.0)`` has exactly the edges ``kept``; a row's out-degree is at most ``p_i``
+in every mode, exactly ``min(k, p_i)`` in ``"directed"`` and at least that in ``"union"``; ``mutual`` is a subset of
+``directed``, which is one of ``union``; a bit-symmetric ``A`` gives a bit-symmetric ``B`` in ``"union"`` and
+``"mutual"``; ``k >= n - 1`` keeps every positive off-diagonal entry (in ``"mutual"``: every one whose mirror entry
+is positive too) and ``k = 0`` gives all zeros; scaling ``A`` by a
+positive power of two scales ``B`` and changes no choice.  A row's picks are two numbers, the value ``v_i`` and the
+column ``c_i`` of its last pick (``+inf`` and ``-1`` for a row without one):
+``d_ij  <=>  A_ij > 0 and (A_ij > v_i or (A_ij == v_i and j <= c_i))``, which is what the kernel keeps per row.
+
+One launch, ``n <= KNN_MAX_NODES = 1024`` (a ``ValueError`` beyond).  No atomics on global memory (a row's select counts
+in LDS, integer adds whose order does not matter), and no work assignment depends on the
+grid: every run and every grid gives the same bits, and ``out=matrices`` gives the bits of a separate output (all picks
+of a subject exist before any of its entries is written).  ``knn=k`` and ``knn_mode=`` of ``from_matrices``,
+``node_measures``, ``path_lengths`` and ``from_timeseries`` are a fourth way to choose the edges, refused together with
+any of the other three: each call is, bit for bit, the same call on ``knn_sparsify(matrices, k, mode=knn_mode)`` with
+``min_weight=0.0``.  ``from_timeseries`` sparsifies its connectivity temporary in place; the other three leave the
+caller's matrices untouched and hold one cohort-sized temporary for the length of the call
+(``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` avoid it for a caller who can give the matrices up).
 """
 from __future__ import annotations
 
@@ -404,6 +442,9 @@ CONFOUND_RANK_TOL = 1e-10                             # CGNN_CONFOUND_RANK_TOL: 
 FILTERS = ("cosine", "butterworth")                   # filter_timeseries's filter=
 BUTTERWORTH_MAX_ORDER = 8                             # CGNN_BUTTER_MAX_SECTIONS (cgnn_butterworth.h): a band-pass has `order` sections
 _BUTTERWORTH_ORDER = 5                                # nilearn's
+KNN_MODES = ("union", "mutual", "directed")           # knn_sparsify's mode=, knn_mode= elsewhere
+KNN_MAX_NODES = 1024                                  # CGNN_KNN_MAX_NODES (cgnn_knn.h): a row lives in 16 registers per lane
+_KNN_MODE_IDS = {"union": _lib.KNN_UNION, "mutual": _lib.KNN_MUTUAL, "directed": _lib.KNN_DIRECTED}
 
 
 class _Family(NamedTuple):
@@ -1169,24 +1210,102 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
-                    kind="correlation", shrinkage=0.0, sample_mask=None) -> RaggedPackedDataset:
+                    kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
+                    knn_mode="union") -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
     ``shrinkage`` and ``sample_mask`` are ``correlation_matrices``'s (a unit with fewer than two kept frames is a graph
-    without edges).  The one read-back is ``from_matrices``'s."""
+    without edges).  The one read-back is ``from_matrices``'s.  ``knn=k`` (with ``knn_mode``) instead of the three
+    thresholds: the k-NN graph of every unit's matrix, as in ``from_matrices``; the connectivity temporary is sparsified
+    in place, which costs no extra memory."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
     _check_path_size(_check_measures_argument(measures, node_features), n)
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    if choice is not None:
+        min_weight = 0.0
     _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
     matrices = _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, sample_mask)
+    if choice is not None:
+        _knn(matrices, choice, matrices)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
                          num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
+
+
+def _check_knn(n: int, k, mode) -> tuple:
+    """``(k, mode id)`` of a valid k-NN request on matrices of ``n`` nodes, as cgnn_ingest_knn takes them."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"k must be an int, got {type(k).__name__}")
+    if k < 0:
+        raise ValueError(f"k must be >= 0, got {k}")
+    if not isinstance(mode, str) or mode not in KNN_MODES:
+        raise ValueError(f"unknown mode {mode!r}: the modes are KNN_MODES = {KNN_MODES}")
+    if n > KNN_MAX_NODES:
+        raise ValueError(f"k-NN sparsification takes n <= {KNN_MAX_NODES} nodes (a row lives in 16 registers per "
+                         f"lane), got n = {n}")
+    return min(k, _LIMIT), _KNN_MODE_IDS[mode]        # anything >= n - 1 keeps every positive entry
+
+
+def _knn_choice(n: int, knn, knn_mode, keep, num_edges, min_weight):
+    """None without ``knn=`` (the call then chooses its edges as it always did); else ``_check_knn``'s pair of a valid
+    ``knn=`` / ``knn_mode=``, which goes with none of the three thresholds."""
+    if knn is None:
+        if knn_mode != "union":
+            raise ValueError(f"knn_mode={knn_mode!r} says how the picks of knn= are symmetrised: give knn= with it")
+        return None
+    if any(a is not None for a in (keep, num_edges, min_weight)):
+        raise ValueError("knn= is a fourth way to choose the edges: give none of keep=, num_edges= and min_weight= "
+                         "with it")
+    return _check_knn(n, knn, knn_mode)
+
+
+def _check_matrix_out(out, matrices: torch.Tensor) -> None:
+    if out is None:
+        return
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
+    if out.dtype != torch.float32:
+        raise TypeError(f"out must be float32, got {out.dtype}")
+    if out.shape != matrices.shape:
+        raise ValueError(f"out must be {tuple(matrices.shape)} as the matrices are, got {tuple(out.shape)}")
+    if out.device != matrices.device:
+        raise ValueError(f"out is on {out.device}, the matrices on {matrices.device}")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+
+
+def _knn(matrices: torch.Tensor, choice: tuple, out=None) -> torch.Tensor:
+    """cgnn_ingest_knn of resident matrices for ``_check_knn``'s pair, into ``out`` (which may be ``matrices``) or a new
+    tensor."""
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
+    if out is None:
+        out = torch.empty_like(matrices)
+    if S:
+        _call(matrices.device, "cgnn_ingest_knn", matrices, S, n, *choice, *_lib.buf(out))
+    return out
+
+
+def knn_sparsify(matrices: torch.Tensor, k: int, *, mode="union", out=None) -> torch.Tensor:
+    """The k-nearest-neighbour graph of every subject as a matrix: float32 ``[S, n, n]`` on ``matrices.device`` with
+    the bits of ``matrices`` where an entry is kept and ``+0.0`` elsewhere (module docstring), so that every call of
+    this module at ``min_weight=0.0`` sees exactly the k-NN graph.  Every row picks its ``min(k, p_i)`` strongest
+    positive off-diagonal entries, ties by the lower column; ``mode`` is one of ``KNN_MODES``: ``"union"`` keeps
+    ``i -> j`` if either end picked the other (the usual k-NN graph), ``"mutual"`` if both did, ``"directed"`` the picks
+    themselves.  ``k`` is an int ``>= 0``; ``n <= KNN_MAX_NODES``.  ``out`` is where the result goes: a float32 contiguous
+    tensor of the same shape on the same device, which is returned; it may be ``matrices`` itself (in place, the same
+    bits as out of place; any other overlap is refused).  One launch on resident data (csrc/knn.hip); no temporaries,
+    no read-back, no atomics on global memory: every run and every grid gives the same bits."""
+    S, n = _check_matrices(matrices)
+    choice = _check_knn(n, k, mode)
+    _check_matrix_out(out, matrices)
+    _require_resident(matrices, *_MATRICES)
+    return _knn(matrices, choice, out)
 
 
 def _measure_ids(measures) -> list:
@@ -1266,29 +1385,42 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
 
 
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  measures=MEASURES) -> torch.Tensor:
+                  measures=MEASURES, knn=None, knn_mode="union") -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
     ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES`` and
     ``WEIGHTED_PATH_MEASURES`` in any order and mix (module docstring).  The thresholds are those ``from_matrices``
-    applies for the same ``keep`` / ``num_edges`` / ``min_weight``, selected once.  No read-back."""
+    applies for the same ``keep`` / ``num_edges`` / ``min_weight``, selected once.  No read-back.  ``knn=k`` (with
+    ``knn_mode``) instead of the three: the measures of the k-NN graph, as in ``from_matrices``."""
     S, n = _check_matrices(matrices)
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    if choice is not None:
+        min_weight = 0.0
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
     _require_resident(matrices, *_MATRICES)
+    if choice is not None:
+        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
     return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids)
 
 
-def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None) -> torch.Tensor:
+def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
+                 knn_mode="union") -> torch.Tensor:
     """The weighted distances ``dw`` of the module docstring: float32 ``[S, n, n]`` on ``matrices.device``, ``+inf``
     where ``j`` is not reached from ``i`` and a zero diagonal, at the thresholds ``from_matrices`` applies for the same
     ``keep`` / ``num_edges`` / ``min_weight``.  This is the one call of this module whose output is cohort-sized: as
     large as ``matrices`` itself.  The measures of ``WEIGHTED_PATH_MEASURES`` are formed from the same distances without
-    it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back."""
+    it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back.  ``knn=k`` (with ``knn_mode``) instead of
+    the three: the distances on the k-NN graph, as in ``from_matrices``."""
     S, n = _check_matrices(matrices)
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    if choice is not None:
+        min_weight = 0.0
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_size(_WEIGHTED, n, "path_lengths takes")
     _require_resident(matrices, *_MATRICES)
+    if choice is not None:
+        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
     thr = _thresholds(matrices, S, keep, num_edges, min_weight)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
     _run_family(_WEIGHTED, matrices, S, n, thr, [], [], None, dist)
@@ -1307,14 +1439,24 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  node_features=None, measures=None) -> RaggedPackedDataset:
+                  node_features=None, measures=None, knn=None, knn_mode="union") -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
     ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES`` and ``WEIGHTED_PATH_MEASURES``, or ``True``
     for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call, which are selected once.
 
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
-    the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left."""
+    the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left.
+
+    ``knn=k`` is a fourth way to choose the edges, given instead of ``keep`` / ``num_edges`` / ``min_weight``: the
+    k-nearest-neighbour graph, symmetrised as ``knn_mode`` (one of ``KNN_MODES``) says.  The call is, bit for bit, this
+    call on ``knn_sparsify(matrices, k, mode=knn_mode)`` with ``min_weight=0.0``: the strength feature and every
+    measure are those of the k-NN graph.  The caller's matrices are left as they are, so the sparsified cohort is a
+    temporary as large as ``matrices`` for the length of the call (``node_measures`` and ``path_lengths`` alike); a
+    caller who can give the matrices up passes ``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` instead."""
     S, n = _check_matrices(matrices)
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    if choice is not None:
+        min_weight = 0.0
     k, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "S", S, n)
     if node_features is not None and node_features.device != matrices.device:
@@ -1323,6 +1465,8 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     _check_path_size(ids, n)
     _require_resident(matrices, *_MATRICES)
     dev = matrices.device
+    if choice is not None:
+        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
     if min_weight is None:
         thr = torch.empty(S, dtype=torch.float32, device=dev)     # cgnn_ingest_count selects them: no launch of its own
     else:

@@ -1361,5 +1361,6 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 /* Entry points declared in headers of their own; including cgnn.h includes them. */
 #include "cgnn_butterworth.h"
 #include "cgnn_optim.h"
+#include "cgnn_knn.h"
 
 #endif /* CGNN_H */
