@@ -298,6 +298,14 @@ KNN_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_modules.h declares (cgnn.h includes it), in the same form, and the profile's flags.
+MODULE_PROFILE_BINARY, MODULE_PROFILE_NORMALIZE = 1, 2
+MODULE_PROTOTYPES = {
+    "cgnn_ingest_modules_workspace_bytes": (I64, [I64, I32, P, I32]),
+    "cgnn_ingest_modules": (c_int, [P, I64, I32, P, P, I32, P, I32, P, I32, P, I64, P, I64, P, I64, I32, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -316,7 +324,8 @@ def load() -> ctypes.CDLL:
             "g.build()'` or `make -C connectome_gnn_amd/csrc`.  connectome_gnn_amd has no "
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
+                              **MODULE_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

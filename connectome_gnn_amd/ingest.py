@@ -411,6 +411,30 @@ any of the other three: each call is, bit for bit, the same call on ``knn_sparsi
 ``min_weight=0.0``.  ``from_timeseries`` sparsifies its connectivity temporary in place; the other three leave the
 caller's matrices untouched and hold one cohort-sized temporary for the length of the call
 (``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` avoid it for a caller who can give the matrices up).
+
+Module measures: the atlases ship with a partition of their ROIs into functional networks, and
+``MODULE_MEASURES`` are the node descriptors built on it.  ``modules=`` of ``node_measures``, ``from_matrices`` and
+``from_timeseries`` is that partition: ``n`` labels ``c_j`` in ``0 .. M - 1``, each used, ``M <= MODULE_MAX = 64``, one
+per cohort, checked on the host (a sequence, an array or a CPU tensor; a device tensor is refused, since the check
+would read it back).  It is given exactly when a module measure is named.  With ``e_ij``, ``a_ij``, ``b_ij`` as above
+(rows are what is summed, nothing is symmetrised): ``k_i(m) = sum_{j: c_j = m} b_ij``, ``s_i(m) = sum_{j: c_j = m}
+a_ij``, ``k_i = sum_m k_i(m)``, ``s_i = sum_m s_i(m)``, ``kappa_i = k_i(c_i)``, ``sigma_i = s_i(c_i)``.
+
+* ``participation``: ``1 - sum_m (k_i(m) / k_i)^2``, 0 if ``k_i == 0``
+* ``weighted_participation``: ``1 - sum_m (s_i(m) / s_i)^2``, 0 if ``s_i == 0``
+* ``module_zscore``: ``(kappa_i - mean) / std`` over the nodes of module ``c_i`` (population std, as numpy and BCT);
+  0 if all ``kappa`` of that module compare equal (that test, not ``std == 0``: BCT sets those NaNs to 0)
+* ``weighted_module_zscore``: the same on ``sigma_i``
+* ``diversity``: ``-sum_{m: p > 0} p ln p / ln M`` with ``p = s_i(m) / s_i``; 0 if ``s_i == 0`` or ``M == 1``
+
+Everything after the fp32 edge test is fp64 in a fixed order, rounded to fp32 once; the binary sums are exact integers.
+A kept ``+inf`` follows the formulas: NaN in that row's weighted columns and in the weighted z-scores of its module.
+One launch (csrc/modules.hip), a wave per row with the row in registers (``n <= MODULE_MAX_NODES = 1024``), the
+z-scores in a second phase over LDS that runs only when one is asked for; no workspace, no atomics, no read-back, the
+same bits on every run and for every grid.  ``module_profile(matrices, modules, binary=False, normalize=False)``
+returns the network profile ``s_i(m)`` (``k_i(m)`` if ``binary``; divided by the row total if ``normalize``, an
+isolated node keeping an exact zero row) as ``[S, n, M]``: with the 7 Yeo networks that is 7 feature columns, which as
+``node_features=`` keep a cohort on the fused GCN path (``in_channels <= 8``).
 """
 from __future__ import annotations
 
@@ -445,6 +469,10 @@ _BUTTERWORTH_ORDER = 5                                # nilearn's
 KNN_MODES = ("union", "mutual", "directed")           # knn_sparsify's mode=, knn_mode= elsewhere
 KNN_MAX_NODES = 1024                                  # CGNN_KNN_MAX_NODES (cgnn_knn.h): a row lives in 16 registers per lane
 _KNN_MODE_IDS = {"union": _lib.KNN_UNION, "mutual": _lib.KNN_MUTUAL, "directed": _lib.KNN_DIRECTED}
+MODULE_MEASURES = ("participation", "weighted_participation", "module_zscore", "weighted_module_zscore",
+                   "diversity")                       # ids: include/cgnn_modules.h
+MODULE_MAX = 64                                       # CGNN_MODULE_MAX: a lane of a wave owns a module
+MODULE_MAX_NODES = 1024                               # CGNN_MODULE_MAX_NODES: a row lives in 16 registers per lane
 
 
 class _Family(NamedTuple):
@@ -456,6 +484,7 @@ class _Family(NamedTuple):
     max_nodes: Optional[int] = None                   # the largest n, and for the message who is limited and why
     what: str = ""
     why: str = ""
+    modules: bool = False                             # takes modules / M, and profile / profile_bytes / profile_flags
 
 
 _FAMILIES = (                                         # in the order of their calls
@@ -463,8 +492,11 @@ _FAMILIES = (                                         # in the order of their ca
     _Family(PATH_MEASURES, "cgnn_ingest_paths", True, False, PATH_MAX_NODES, "path measures",
             "the adjacency bitset of a subject must fit LDS"),
     _Family(WEIGHTED_PATH_MEASURES, "cgnn_ingest_wpaths", True, True, WEIGHTED_PATH_MAX_NODES,
-            "weighted path measures", "both panels of a Floyd-Warshall round must fit LDS"))
+            "weighted path measures", "both panels of a Floyd-Warshall round must fit LDS"),
+    _Family(MODULE_MEASURES, "cgnn_ingest_modules", True, False, MODULE_MAX_NODES, "module measures",
+            "a row lives in 16 registers per lane", modules=True))
 _WEIGHTED = _FAMILIES[2]                              # path_lengths's
+_MODULES = _FAMILIES[3]                               # module_profile's
 _ALL_MEASURES = tuple(name for fam in _FAMILIES for name in fam.names)
 
 
@@ -1211,19 +1243,21 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
                     kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
-                    knn_mode="union") -> RaggedPackedDataset:
+                    knn_mode="union", modules=None) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
     ``shrinkage`` and ``sample_mask`` are ``correlation_matrices``'s (a unit with fewer than two kept frames is a graph
     without edges).  The one read-back is ``from_matrices``'s.  ``knn=k`` (with ``knn_mode``) instead of the three
     thresholds: the k-NN graph of every unit's matrix, as in ``from_matrices``; the connectivity temporary is sparsified
-    in place, which costs no extra memory."""
+    in place, which costs no extra memory.  ``modules`` is ``from_matrices``'s."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
-    _check_path_size(_check_measures_argument(measures, node_features), n)
+    ids = _check_measures_argument(measures, node_features)
+    _check_path_size(ids, n)
+    _check_modules_argument(ids, modules, n)
     choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
     if choice is not None:
         min_weight = 0.0
@@ -1235,7 +1269,8 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     if choice is not None:
         _knn(matrices, choice, matrices)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
-                         num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures)
+                         num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures,
+                         modules=modules)
 
 
 def _check_knn(n: int, k, mode) -> tuple:
@@ -1346,28 +1381,84 @@ def _check_measures_argument(measures, node_features):
     return _measure_ids(MEASURES if measures is True else measures)
 
 
-def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x, dist=None):
+def _check_modules(modules, n: int, device=None) -> tuple:
+    """``(labels, M)`` of a valid partition of ``n`` ROIs: ``modules`` is a sequence, a numpy array or a CPU integer
+    tensor of ``n`` labels that are exactly ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``.  The labels
+    come back as a contiguous int32 tensor on ``device`` (None: the host), which is what the kernel trusts.  The whole
+    check runs on the host: a device tensor is refused, because checking it would be a read-back."""
+    if isinstance(modules, torch.Tensor):
+        if modules.device.type != "cpu":
+            raise ValueError(f"modules are on {modules.device}: give the partition as a CPU tensor, an array or a "
+                             "sequence (its labels are checked on the host; checking a device tensor would be a "
+                             "read-back)")
+        if modules.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise TypeError(f"modules must hold integer labels, got {modules.dtype}")
+        labels = modules.detach().to(torch.int64).numpy()
+    else:
+        if isinstance(modules, (str, bytes)) or not isinstance(modules, (list, tuple, range, np.ndarray)):
+            raise TypeError(f"modules must be a sequence, a numpy array or a CPU integer tensor of n = {n} labels, got "
+                            f"{type(modules).__name__}")
+        labels = np.asarray(modules)
+        if labels.size and (labels.dtype == np.bool_ or not np.issubdtype(labels.dtype, np.integer)):
+            raise TypeError(f"modules must hold integer labels, got {labels.dtype}")
+        labels = labels.astype(np.int64)
+    if labels.shape != (n,):
+        raise ValueError(f"modules must be [n] = [{n}] labels, one per ROI, got {tuple(labels.shape)}")
+    if int(labels.min()) < 0:
+        raise ValueError(f"modules must be labels 0 .. M - 1, got {int(labels.min())}")
+    M = int(labels.max()) + 1
+    if M > MODULE_MAX:
+        raise ValueError(f"modules name M = {M} modules: at most MODULE_MAX = {MODULE_MAX} (a lane of a wave owns one)")
+    unused = sorted(set(range(M)) - set(labels.tolist()))
+    if unused:
+        raise ValueError(f"modules must use every label of 0 .. M - 1 = 0 .. {M - 1}: {unused} have no ROI")
+    out = torch.from_numpy(labels.astype(np.int32))
+    return (out if device is None else out.to(device)), M
+
+
+def _check_modules_argument(ids, modules, n: int):
+    """``_check_modules``'s pair, on the host, when the request ``ids`` names a module measure (``modules=`` is then
+    required), None when it names none (``modules=`` is then refused: it would be ignored)."""
+    named = [MODULE_MEASURES[i] for fam, i in (ids or ()) if fam is _MODULES]
+    if not named:
+        if modules is not None:
+            raise ValueError(f"modules= was given but no measure of MODULE_MEASURES = {MODULE_MEASURES} is named")
+        return None
+    if modules is None:
+        raise ValueError(f"the module measures {tuple(named)} need the partition: give modules=, one label per ROI")
+    return _check_modules(modules, n)
+
+
+def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x, dist=None,
+                modules=None, profile=None, profile_flags=0):
     """One call of ``fam``: measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as
     they are; a family without ``cols`` fills ``x`` ``[S, n, len(ids)]`` in the order of ``ids``), and the distances into
-    ``dist`` ``[S, n, n]`` if given.  The workspace is what the family's query asks for: nothing for the paths, one slab
-    per workgroup for the weighted paths.  Returns ``x``."""
+    ``dist`` ``[S, n, n]`` if given.  The workspace is what the family's query asks for: nothing for the paths and the
+    module measures, one slab per workgroup for the weighted paths.  ``modules`` is ``_check_modules``'s pair on the
+    matrices' device and ``profile`` ``[S, n, M]`` the network profile, for the family that takes them.  Returns ``x``."""
     if S == 0:
         return x
     num = len(ids)
     arr = (ctypes.c_int32 * num)(*ids)
-    args = [matrices, S, n, thr, arr, num]
+    args = [matrices, S, n, thr]
+    if fam.modules:
+        args += list(modules)
+    args += [arr, num]
     if fam.cols:
         args += [(ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1]
     args += [_WORK, *_lib.buf(x)]
     if fam.dist:
         args += _lib.buf(dist)
+    if fam.modules:
+        args += [*_lib.buf(profile), profile_flags]
     _call(matrices.device, fam.call, *args, workspace=(fam.call, S, n, arr, num))
     return x
 
 
-def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list) -> torch.Tensor:
+def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, modules=None) -> torch.Tensor:
     """``[S, n, len(ids)]``, one call per family that is named.  A request of classic names only is one packed
-    cgnn_ingest_measures call, as before; the path families write their columns in place (cols / ldx)."""
+    cgnn_ingest_measures call, as before; the other families write their columns in place (cols / ldx).  ``modules`` is
+    ``_check_modules_argument``'s."""
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
     for fam in _FAMILIES:
         cols = [c for c, (f, _) in enumerate(ids) if f is fam]
@@ -1375,7 +1466,7 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
         if not cols:
             continue
         if fam.cols or len(cols) == len(ids):
-            _run_family(fam, matrices, S, n, thr, fam_ids, cols, x)
+            _run_family(fam, matrices, S, n, thr, fam_ids, cols, x, modules=modules)
         else:
             # cgnn_ingest_measures writes a packed block only, so in a mixed request its columns are copied in.  Removing
             # this temporary takes a cols / ldx entry point for the classic family: another change.
@@ -1385,12 +1476,15 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
 
 
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  measures=MEASURES, knn=None, knn_mode="union") -> torch.Tensor:
+                  measures=MEASURES, knn=None, knn_mode="union", modules=None) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
-    ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES`` and
-    ``WEIGHTED_PATH_MEASURES`` in any order and mix (module docstring).  The thresholds are those ``from_matrices``
-    applies for the same ``keep`` / ``num_edges`` / ``min_weight``, selected once.  No read-back.  ``knn=k`` (with
-    ``knn_mode``) instead of the three: the measures of the k-NN graph, as in ``from_matrices``."""
+    ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES``,
+    ``WEIGHTED_PATH_MEASURES`` and ``MODULE_MEASURES`` in any order and mix (module docstring).  The thresholds are
+    those ``from_matrices`` applies for the same ``keep`` / ``num_edges`` / ``min_weight``, selected once.  No
+    read-back.  ``knn=k`` (with ``knn_mode``) instead of the three: the measures of the k-NN graph, as in
+    ``from_matrices``.  ``modules`` is the partition of the ROIs that the names of ``MODULE_MEASURES`` need, and is
+    given exactly when one of them is named: a sequence, a numpy array or a CPU integer tensor of ``n`` labels
+    ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``; one partition for the cohort, checked on the host."""
     S, n = _check_matrices(matrices)
     choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
     if choice is not None:
@@ -1398,10 +1492,41 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
+    partition = _check_modules_argument(ids, modules, n)
+    _require_resident(matrices, *_MATRICES)
+    if partition is not None:
+        partition = (partition[0].to(matrices.device), partition[1])
+    if choice is not None:
+        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
+    return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids, partition)
+
+
+def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None, min_weight=None, knn=None,
+                   knn_mode="union", binary=False, normalize=False) -> torch.Tensor:
+    """The network profile of every node, the node-to-network feature: float32 ``[S, n, M]`` on ``matrices.device`` with
+    ``s_i(m)``, node ``i``'s kept strength into module ``m`` (module docstring), at the thresholds ``from_matrices``
+    applies for the same ``keep`` / ``num_edges`` / ``min_weight`` (or on the k-NN graph of ``knn=`` / ``knn_mode=``).
+    ``modules`` is ``node_measures``'s partition.  ``binary=True`` gives ``k_i(m)``, the number of kept connections
+    into the module; ``normalize=True`` divides a row by its total, an isolated node keeping an exact zero row.  One
+    launch (cgnn_ingest_modules without measures); no cohort-sized temporary, no read-back.  With a partition of
+    ``M <= 8`` modules (the 7 Yeo networks) the result, passed as ``from_matrices(..., node_features=)``, keeps a
+    cohort on the fused GCN path.  ``n <= MODULE_MAX_NODES``."""
+    S, n = _check_matrices(matrices)
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    if choice is not None:
+        min_weight = 0.0
+    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    _check_size(_MODULES, n, "module_profile takes")
+    labels, M = _check_modules(modules, n)
     _require_resident(matrices, *_MATRICES)
     if choice is not None:
         matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
-    return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids)
+    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
+    profile = torch.empty(S, n, M, dtype=torch.float32, device=matrices.device)
+    flags = (_lib.MODULE_PROFILE_BINARY if binary else 0) | (_lib.MODULE_PROFILE_NORMALIZE if normalize else 0)
+    _run_family(_MODULES, matrices, S, n, thr, [], [], None, modules=(labels.to(matrices.device), M), profile=profile,
+                profile_flags=flags)
+    return profile
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
@@ -1439,10 +1564,12 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  node_features=None, measures=None, knn=None, knn_mode="union") -> RaggedPackedDataset:
+                  node_features=None, measures=None, knn=None, knn_mode="union",
+                  modules=None) -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
-    ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES`` and ``WEIGHTED_PATH_MEASURES``, or ``True``
-    for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call, which are selected once.
+    ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES``, ``WEIGHTED_PATH_MEASURES`` and
+    ``MODULE_MEASURES``, or ``True`` for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call,
+    which are selected once; ``modules`` is ``node_measures``'s partition, given exactly when a module measure is named.
 
     One synchronisation: the ``S + 1`` edge offsets are read back once, to size the edge arrays and to fill
     the host ``edge_ptr`` the dataset carries; ``edge_ptr_dev`` is the array the kernels' running sum left.
@@ -1463,8 +1590,11 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
         raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
+    partition = _check_modules_argument(ids, modules, n)
     _require_resident(matrices, *_MATRICES)
     dev = matrices.device
+    if partition is not None:
+        partition = (partition[0].to(dev), partition[1])
     if choice is not None:
         matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
     if min_weight is None:
@@ -1490,5 +1620,5 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
         _lib.call("cgnn_ingest_fill", matrices, S, n, thr, row_off, E, *_lib.buf(edge_local), *_lib.buf(edge_weight),
                   stream=sp)
     if ids is not None:
-        x = _measures(matrices, S, n, thr, ids)       # at the thresholds cgnn_ingest_count selected
+        x = _measures(matrices, S, n, thr, ids, partition)        # at the thresholds cgnn_ingest_count selected
     return RaggedPackedDataset(x, edge_local, edge_weight, labels.to(dev), edge_ptr, edge_ptr_dev)

@@ -1362,5 +1362,6 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 #include "cgnn_butterworth.h"
 #include "cgnn_optim.h"
 #include "cgnn_knn.h"
+#include "cgnn_modules.h"
 
 #endif /* CGNN_H */
