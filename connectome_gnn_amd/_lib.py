@@ -306,6 +306,13 @@ MODULE_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_mst.h declares (cgnn.h includes it), in the same form.
+MST_PROTOTYPES = {
+    "cgnn_ingest_mst_workspace_bytes": (I64, [I64, I32]),
+    "cgnn_ingest_mst": (c_int, [P, I64, I32, P, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -325,7 +332,7 @@ def load() -> ctypes.CDLL:
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
-                              **MODULE_PROTOTYPES}.items():
+                              **MODULE_PROTOTYPES, **MST_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -412,6 +412,33 @@ any of the other three: each call is, bit for bit, the same call on ``knn_sparsi
 caller's matrices untouched and hold one cohort-sized temporary for the length of the call
 (``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` avoid it for a caller who can give the matrices up).
 
+Maximum-spanning-tree backbone: neither a threshold nor the k-NN graph returns a connected graph; on
+modular data, which connectomes are, the strongest entries all lie inside the modules.  ``mst_backbone(matrices, keep=,
+num_edges=, min_weight=, out=)`` unites the choice with the maximum spanning forest of the positive weights (BCT's
+``backbone_wu``; csrc/mst.hip).  Per subject with matrix ``A`` ``[n, n]``, fp32, any sign, not necessarily symmetric:
+
+* ``p(x) = x if x > 0 else 0``: a NaN is not positive, ``+inf`` and a subnormal are.
+* The pair ``{i, j}``, ``i < j``, has weight ``w_ij = max(p(A_ij), p(A_ji))`` and is a candidate iff ``w_ij > 0``.
+* Order: ``(i, j)`` comes before ``(i', j')`` iff ``w > w'``, or ``w == w'`` and ``(i, j)`` is lexicographically lower:
+  a strict total order, so the maximum spanning forest ``F`` (Kruskal: a pair is taken iff its ends lie in different
+  components) is unique.  It has ``n - c`` pairs, ``c`` the number of components of the candidate graph; the all-0.5
+  matrix gives the star at node 0.
+* ``kept_ij`` iff ``i != j``, ``A_ij > 0`` and (``{i, j}`` in ``F`` or ``A_ij > t_s``), ``t_s`` the subject's threshold
+  (``+inf`` without a choice: the tree alone).  A tree pair whose reverse entry is not positive keeps only the positive
+  direction, as ``"union"`` does.
+* Output: the bits of ``A_ij`` where kept, ``+0.0`` elsewhere, the diagonal and every NaN too.
+
+One launch, ``n <= MST_MAX_NODES = 1024``: the symmetrised weights go to a slab per workgroup of a workspace, Prim with
+restarts runs on 64-bit integer keys in registers (no subnormal is flushed), and every decision of a subject exists
+before any entry is written: no atomics, the same bits on every run and grid, in place and out of place.
+``backbone="mst"`` (one of ``BACKBONES``) of ``from_matrices``, ``node_measures``, ``module_profile``, ``path_lengths``
+and ``from_timeseries``, together with one of the three thresholds, is bit for bit the same call on
+``mst_backbone(m, <that choice>)`` with ``min_weight=0.0``; alone it is the tree alone; together with ``knn=`` it is the
+same call on ``torch.maximum(knn_sparsify(m, k, mode=knn_mode), mst_backbone(m))``, which is exact because every entry is
+a positive value's bits or ``+0.0``, and which holds two cohort-sized temporaries for the length of the call, the k-NN
+graph and the tree (``from_timeseries``: the tree only).  The united graph has at most ``2 (n - 1)`` more entries than the
+choice alone.
+
 Module measures: the atlases ship with a partition of their ROIs into functional networks, and
 ``MODULE_MEASURES`` are the node descriptors built on it.  ``modules=`` of ``node_measures``, ``from_matrices`` and
 ``from_timeseries`` is that partition: ``n`` labels ``c_j`` in ``0 .. M - 1``, each used, ``M <= MODULE_MAX = 64``, one
@@ -469,6 +496,8 @@ _BUTTERWORTH_ORDER = 5                                # nilearn's
 KNN_MODES = ("union", "mutual", "directed")           # knn_sparsify's mode=, knn_mode= elsewhere
 KNN_MAX_NODES = 1024                                  # CGNN_KNN_MAX_NODES (cgnn_knn.h): a row lives in 16 registers per lane
 _KNN_MODE_IDS = {"union": _lib.KNN_UNION, "mutual": _lib.KNN_MUTUAL, "directed": _lib.KNN_DIRECTED}
+BACKBONES = ("mst",)                                  # backbone= of the matrix entry points
+MST_MAX_NODES = 1024                                  # CGNN_MST_MAX_NODES (cgnn_mst.h): a lane owns 4 nodes of the tree phase
 MODULE_MEASURES = ("participation", "weighted_participation", "module_zscore", "weighted_module_zscore",
                    "diversity")                       # ids: include/cgnn_modules.h
 MODULE_MAX = 64                                       # CGNN_MODULE_MAX: a lane of a wave owns a module
@@ -1243,14 +1272,15 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
                     kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
-                    knn_mode="union", modules=None) -> RaggedPackedDataset:
+                    knn_mode="union", modules=None, backbone=None) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
     ``shrinkage`` and ``sample_mask`` are ``correlation_matrices``'s (a unit with fewer than two kept frames is a graph
     without edges).  The one read-back is ``from_matrices``'s.  ``knn=k`` (with ``knn_mode``) instead of the three
     thresholds: the k-NN graph of every unit's matrix, as in ``from_matrices``; the connectivity temporary is sparsified
-    in place, which costs no extra memory.  ``modules`` is ``from_matrices``'s."""
+    in place, which costs no extra memory.  ``modules`` is ``from_matrices``'s.  ``backbone`` is ``from_matrices``'s: the
+    connectivity temporary becomes the united graph in place (with ``knn=`` the tree is one more temporary)."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
@@ -1258,16 +1288,14 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
     _check_modules_argument(ids, modules, n)
-    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
-    if choice is not None:
-        min_weight = 0.0
+    edges, keep, num_edges, min_weight = _edge_choice(n, U, "U", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
     matrices = _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, sample_mask)
-    if choice is not None:
-        _knn(matrices, choice, matrices)
+    if edges is not None:
+        _sparsified(matrices, U, edges, matrices)
     return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
                          num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures,
                          modules=modules)
@@ -1298,6 +1326,66 @@ def _knn_choice(n: int, knn, knn_mode, keep, num_edges, min_weight):
         raise ValueError("knn= is a fourth way to choose the edges: give none of keep=, num_edges= and min_weight= "
                          "with it")
     return _check_knn(n, knn, knn_mode)
+
+
+def _check_backbone(n: int, backbone) -> bool:
+    """Whether a valid ``backbone=`` asks for the tree on matrices of ``n`` nodes (None: no backbone)."""
+    if backbone is None:
+        return False
+    if not isinstance(backbone, str) or backbone not in BACKBONES:
+        raise ValueError(f"unknown backbone {backbone!r}: the backbones are BACKBONES = {BACKBONES}")
+    _check_mst_size(n)
+    return True
+
+
+def _check_mst_size(n: int) -> None:
+    if n > MST_MAX_NODES:
+        raise ValueError(f"the spanning-tree backbone takes n <= {MST_MAX_NODES} nodes (a lane owns 4 nodes of the tree "
+                         f"phase), got n = {n}")
+
+
+def _at_most_one(keep, num_edges, min_weight) -> bool:
+    """Whether one of the three thresholds is given, where none need be; two are refused."""
+    given = sum(a is not None for a in (keep, num_edges, min_weight))
+    if given > 1:
+        raise ValueError("the backbone is united with at most one of keep=, num_edges= and min_weight=")
+    return given == 1
+
+
+class _Edges(NamedTuple):
+    """How a call sparsifies its matrices before it runs at ``min_weight=0.0``: the k-NN graph of ``_check_knn``'s pair
+    (None: no ``knn=``), united with the tree if ``tree``; without ``knn=`` the tree united with the threshold choice
+    (all three None: the tree alone)."""
+    knn: Optional[tuple]
+    tree: bool
+    keep: Optional[float]
+    num_edges: Optional[int]
+    min_weight: object
+
+
+def _edge_choice(n: int, units: int, unit_name: str, knn, knn_mode, backbone, keep, num_edges, min_weight) -> tuple:
+    """``(edges, keep, num_edges, min_weight)``: without ``knn=`` and ``backbone=`` None and the three as they came (the
+    call then chooses its edges as it always did, and checks the three itself); else the valid ``_Edges`` and the choice
+    the call goes on with on the sparsified matrices, ``min_weight=0.0``."""
+    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
+    tree = _check_backbone(n, backbone)
+    if choice is None and not tree:
+        return None, keep, num_edges, min_weight
+    if choice is None and _at_most_one(keep, num_edges, min_weight):
+        _, min_weight = _threshold_choice(n, units, unit_name, keep, num_edges, min_weight)
+    return _Edges(choice, tree, keep, num_edges, min_weight), None, None, 0.0
+
+
+def _sparsified(matrices: torch.Tensor, units: int, edges: _Edges, out=None) -> torch.Tensor:
+    """The resident matrices sparsified as ``edges`` says, into ``out`` (which may be ``matrices``) or a new tensor."""
+    if edges.knn is None:
+        thr = None
+        if any(a is not None for a in edges[2:]):
+            thr = _thresholds(matrices, units, *edges[2:])
+        return _mst(matrices, thr, out)
+    tree = _mst(matrices, None) if edges.tree else None               # (before `out` may overwrite the matrices)
+    out = _knn(matrices, edges.knn, out)
+    return out if tree is None else torch.maximum(out, tree, out=out)
 
 
 def _check_matrix_out(out, matrices: torch.Tensor) -> None:
@@ -1341,6 +1429,41 @@ def knn_sparsify(matrices: torch.Tensor, k: int, *, mode="union", out=None) -> t
     _check_matrix_out(out, matrices)
     _require_resident(matrices, *_MATRICES)
     return _knn(matrices, choice, out)
+
+
+def _mst(matrices: torch.Tensor, thr, out=None) -> torch.Tensor:
+    """cgnn_ingest_mst of resident matrices at the ``[S]`` thresholds ``thr`` (None: the tree alone), into ``out`` (which
+    may be ``matrices``) or a new tensor.  The workspace, a slab per workgroup of the launch, lives for the call."""
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
+    if out is None:
+        out = torch.empty_like(matrices)
+    if S:
+        _call(matrices.device, "cgnn_ingest_mst", matrices, S, n, thr, _WORK, *_lib.buf(out),
+              workspace=("cgnn_ingest_mst", S, n))
+    return out
+
+
+def mst_backbone(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, out=None) -> torch.Tensor:
+    """The maximum-spanning-tree backbone of every subject, united with a threshold, as a matrix: float32 ``[S, n, n]``
+    on ``matrices.device`` with the bits of ``matrices`` where an entry is kept and ``+0.0`` elsewhere (module
+    docstring), so that every call of this module at ``min_weight=0.0`` sees exactly the united graph.  A positive
+    off-diagonal entry is kept iff its pair belongs to the maximum spanning forest of the symmetrised positive weights
+    (ties by the lexicographically lower pair: the forest is unique) or the entry lies above the subject's threshold.
+    With none of ``keep`` / ``num_edges`` / ``min_weight`` the result is the tree alone; otherwise the thresholds are
+    those ``select_thresholds`` or ``from_matrices`` would apply to ``matrices`` for the same choice, of which at most
+    one may be given.  What the positive entries connect stays connected: a subject whose positive entries form one
+    component gives a connected graph at any density.  ``n <= MST_MAX_NODES``.  ``out`` is where the result goes: a
+    float32 contiguous tensor of the same shape on the same device, which is returned; it may be ``matrices`` itself (in
+    place, the same bits as out of place; any other overlap is refused).  One launch on resident data (csrc/mst.hip)
+    after the selection of the thresholds; the one temporary is the workspace, a matrix-sized slab per workgroup of the
+    launch and not per subject; no read-back, no atomics: every run and every grid gives the same bits."""
+    S, n = _check_matrices(matrices)
+    if _at_most_one(keep, num_edges, min_weight):
+        _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    _check_mst_size(n)
+    _check_matrix_out(out, matrices)
+    _require_resident(matrices, *_MATRICES)
+    return _sparsified(matrices, S, _Edges(None, True, keep, num_edges, min_weight), out)
 
 
 def _measure_ids(measures) -> list:
@@ -1476,7 +1599,7 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
 
 
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  measures=MEASURES, knn=None, knn_mode="union", modules=None) -> torch.Tensor:
+                  measures=MEASURES, knn=None, knn_mode="union", modules=None, backbone=None) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
     ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES``,
     ``WEIGHTED_PATH_MEASURES`` and ``MODULE_MEASURES`` in any order and mix (module docstring).  The thresholds are
@@ -1484,11 +1607,10 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     read-back.  ``knn=k`` (with ``knn_mode``) instead of the three: the measures of the k-NN graph, as in
     ``from_matrices``.  ``modules`` is the partition of the ROIs that the names of ``MODULE_MEASURES`` need, and is
     given exactly when one of them is named: a sequence, a numpy array or a CPU integer tensor of ``n`` labels
-    ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``; one partition for the cohort, checked on the host."""
+    ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``; one partition for the cohort, checked on the host.
+    ``backbone`` is ``from_matrices``'s: the measures of the graph united with the spanning tree."""
     S, n = _check_matrices(matrices)
-    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
-    if choice is not None:
-        min_weight = 0.0
+    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
@@ -1496,13 +1618,13 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     _require_resident(matrices, *_MATRICES)
     if partition is not None:
         partition = (partition[0].to(matrices.device), partition[1])
-    if choice is not None:
-        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
+    if edges is not None:
+        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
     return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids, partition)
 
 
 def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None, min_weight=None, knn=None,
-                   knn_mode="union", binary=False, normalize=False) -> torch.Tensor:
+                   knn_mode="union", binary=False, normalize=False, backbone=None) -> torch.Tensor:
     """The network profile of every node, the node-to-network feature: float32 ``[S, n, M]`` on ``matrices.device`` with
     ``s_i(m)``, node ``i``'s kept strength into module ``m`` (module docstring), at the thresholds ``from_matrices``
     applies for the same ``keep`` / ``num_edges`` / ``min_weight`` (or on the k-NN graph of ``knn=`` / ``knn_mode=``).
@@ -1510,17 +1632,16 @@ def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None
     into the module; ``normalize=True`` divides a row by its total, an isolated node keeping an exact zero row.  One
     launch (cgnn_ingest_modules without measures); no cohort-sized temporary, no read-back.  With a partition of
     ``M <= 8`` modules (the 7 Yeo networks) the result, passed as ``from_matrices(..., node_features=)``, keeps a
-    cohort on the fused GCN path.  ``n <= MODULE_MAX_NODES``."""
+    cohort on the fused GCN path.  ``n <= MODULE_MAX_NODES``.  ``backbone`` is ``from_matrices``'s (the profile of the
+    united graph; it and ``knn=`` cost the cohort-sized temporaries named there)."""
     S, n = _check_matrices(matrices)
-    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
-    if choice is not None:
-        min_weight = 0.0
+    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_size(_MODULES, n, "module_profile takes")
     labels, M = _check_modules(modules, n)
     _require_resident(matrices, *_MATRICES)
-    if choice is not None:
-        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
+    if edges is not None:
+        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
     thr = _thresholds(matrices, S, keep, num_edges, min_weight)
     profile = torch.empty(S, n, M, dtype=torch.float32, device=matrices.device)
     flags = (_lib.MODULE_PROFILE_BINARY if binary else 0) | (_lib.MODULE_PROFILE_NORMALIZE if normalize else 0)
@@ -1530,22 +1651,21 @@ def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
-                 knn_mode="union") -> torch.Tensor:
+                 knn_mode="union", backbone=None) -> torch.Tensor:
     """The weighted distances ``dw`` of the module docstring: float32 ``[S, n, n]`` on ``matrices.device``, ``+inf``
     where ``j`` is not reached from ``i`` and a zero diagonal, at the thresholds ``from_matrices`` applies for the same
     ``keep`` / ``num_edges`` / ``min_weight``.  This is the one call of this module whose output is cohort-sized: as
     large as ``matrices`` itself.  The measures of ``WEIGHTED_PATH_MEASURES`` are formed from the same distances without
     it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back.  ``knn=k`` (with ``knn_mode``) instead of
-    the three: the distances on the k-NN graph, as in ``from_matrices``."""
+    the three: the distances on the k-NN graph, as in ``from_matrices``.  ``backbone`` is ``from_matrices``'s: on a
+    subject whose positive entries form one component every distance is then finite."""
     S, n = _check_matrices(matrices)
-    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
-    if choice is not None:
-        min_weight = 0.0
+    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_size(_WEIGHTED, n, "path_lengths takes")
     _require_resident(matrices, *_MATRICES)
-    if choice is not None:
-        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
+    if edges is not None:
+        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
     thr = _thresholds(matrices, S, keep, num_edges, min_weight)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
     _run_family(_WEIGHTED, matrices, S, n, thr, [], [], None, dist)
@@ -1565,7 +1685,7 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   node_features=None, measures=None, knn=None, knn_mode="union",
-                  modules=None) -> RaggedPackedDataset:
+                  modules=None, backbone=None) -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
     ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES``, ``WEIGHTED_PATH_MEASURES`` and
     ``MODULE_MEASURES``, or ``True`` for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call,
@@ -1579,11 +1699,19 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     call on ``knn_sparsify(matrices, k, mode=knn_mode)`` with ``min_weight=0.0``: the strength feature and every
     measure are those of the k-NN graph.  The caller's matrices are left as they are, so the sparsified cohort is a
     temporary as large as ``matrices`` for the length of the call (``node_measures`` and ``path_lengths`` alike); a
-    caller who can give the matrices up passes ``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` instead."""
+    caller who can give the matrices up passes ``knn_sparsify(m, k, out=m)`` and ``min_weight=0.0`` instead.
+
+    ``backbone="mst"`` (one of ``BACKBONES``) unites the chosen edges with the maximum spanning forest of the positive
+    weights, so that whatever the positive entries connect stays connected at any density.  With one of ``keep`` /
+    ``num_edges`` / ``min_weight`` the call is, bit for bit, this call on ``mst_backbone(matrices, <that choice>)`` with
+    ``min_weight=0.0``, the thresholds being those of the original matrices; alone (only then may the three be left out)
+    it is the tree alone; with ``knn=`` it is this call on ``torch.maximum(knn_sparsify(matrices, k, mode=knn_mode),
+    mst_backbone(matrices))`` with ``min_weight=0.0``, which needs two cohort-sized temporaries for the length of the
+    call, the k-NN graph and the tree (the other choices need one, the united graph).  The strength feature and every
+    measure are those of the united graph, which has at most ``2 (n - 1)`` more entries than the choice alone.  Any
+    other value raises a ``ValueError`` naming ``BACKBONES``."""
     S, n = _check_matrices(matrices)
-    choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
-    if choice is not None:
-        min_weight = 0.0
+    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     k, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "S", S, n)
     if node_features is not None and node_features.device != matrices.device:
@@ -1595,8 +1723,8 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     dev = matrices.device
     if partition is not None:
         partition = (partition[0].to(dev), partition[1])
-    if choice is not None:
-        matrices = _knn(matrices, choice)             # the one cohort-sized temporary, for the length of the call
+    if edges is not None:
+        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
     if min_weight is None:
         thr = torch.empty(S, dtype=torch.float32, device=dev)     # cgnn_ingest_count selects them: no launch of its own
     else:
