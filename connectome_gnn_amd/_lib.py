@@ -313,6 +313,13 @@ MST_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_activity.h declares (cgnn.h includes it), in the same form.
+ACTIVITY_PROTOTYPES = {
+    "cgnn_ingest_activity_workspace_bytes": (I64, [I64, I32, I32, I32]),
+    "cgnn_ingest_activity": (c_int, [P, I64, I32, I32, P, I32, I32, I32, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -332,7 +339,7 @@ def load() -> ctypes.CDLL:
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
-                              **MODULE_PROTOTYPES, **MST_PROTOTYPES}.items():
+                              **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -462,6 +462,27 @@ same bits on every run and for every grid.  ``module_profile(matrices, modules, 
 returns the network profile ``s_i(m)`` (``k_i(m)`` if ``binary``; divided by the row total if ``normalize``, an
 isolated node keeping an exact zero row) as ``[S, n, M]``: with the 7 Yeo networks that is 7 feature columns, which as
 ``node_features=`` keep a cohort on the fused GCN path (``in_channels <= 8``).
+
+Series features (DESIGN.md 4.3s): everything above describes the thresholded matrix, which message passing sees anyway;
+``series_features(timeseries, t_r=, band=, features=SERIES_FEATURES)`` describes the series themselves, how strongly and
+how slowly each region fluctuates, as ``[S, n, F]``, which ``node_features=`` takes.  Per subject and column, stated in
+fp64 on the fp32 input: ``xc = x - mean``, ``q = sum xc^2``, ``X_k = sum_t xc[t] exp(-2 pi i k t / T)`` for
+``k = 1 .. K = T // 2`` (``numpy.fft.rfft``), ``w_k = 2`` but ``w_K = 1`` for even ``T``, and the band is the bins
+``series_band(T, t_r, band)``: ``k_lo = max(1, ceil(lo T t_r))`` to ``k_hi = min(K, floor(hi T t_r))``.
+
+* ``std``: ``sqrt(q / (T - 1))``, BOLD variability
+* ``autocorr1``: ``sum_{t < T-1} xc[t] xc[t+1] / q``
+* ``alff``: the mean over the band of ``2 |X_k| / T`` (Zang 2007; REST and DPABI without their zero-padding)
+* ``falff``: ``sum_band |X_k| / sum_{k = 1 .. K} |X_k|`` (Zou 2008)
+* ``band_std``: ``sqrt(sum_band w_k |X_k|^2 / T / (T - 1))``, the sample std of the ideally band-passed column: C-PAC's ALFF
+* ``band_fraction``: ``band_std / std``: C-PAC's fALFF
+
+A zero denominator gives ``+0.0``, so a constant column is exactly ``+0.0`` in every feature; a NaN makes the features of
+its own column NaN and no other.  The mean, ``q`` and the lag-1 sum are fp64 on the unrounded ``xc``; the spectrum is a
+product with a cos/sin table of the bins asked for on the fp32 matrix pipe (csrc/activity.hip), ``|X_k|^2``, its root, the
+sums, ratios and roots in fp64, one rounding; no coefficient is stored.  ``falff`` alone walks the whole spectrum: its table
+is ``[T, 2 K]`` floats, hence ``T <= SERIES_MAX_FRAMES`` for the spectral names, and it costs ``K / (k_hi - k_lo + 1)``
+times the band's product; ``band_fraction`` is the cheap substitute.
 """
 from __future__ import annotations
 
@@ -502,6 +523,9 @@ MODULE_MEASURES = ("participation", "weighted_participation", "module_zscore", "
                    "diversity")                       # ids: include/cgnn_modules.h
 MODULE_MAX = 64                                       # CGNN_MODULE_MAX: a lane of a wave owns a module
 MODULE_MAX_NODES = 1024                               # CGNN_MODULE_MAX_NODES: a row lives in 16 registers per lane
+SERIES_FEATURES = ("std", "autocorr1", "alff", "falff", "band_std", "band_fraction")   # ids: include/cgnn_activity.h
+SERIES_MAX_FRAMES = 4096                              # CGNN_ACTIVITY_MAX_FRAMES: falff's table [T, 2 (T // 2)] stays <= 64 MB
+_SERIES_SPECTRAL = SERIES_FEATURES[2:]                # the names that need t_r and a band
 
 
 class _Family(NamedTuple):
@@ -1111,6 +1135,81 @@ def filter_timeseries(timeseries: torch.Tensor, *, t_r, high_pass=None, low_pass
         basis, _ = _confound_basis(clean)
         del clean
         _regress(out, basis, out)
+    return out
+
+
+def series_band(T: int, t_r, band) -> tuple:
+    """``(k_lo, k_hi)``: the bins of the DFT of a ``T``-frame run sampled every ``t_r`` seconds that lie in the band
+    ``(lo, hi)`` Hz (module docstring); bin ``k`` has frequency ``k / (T t_r)``, ``k = 1 .. K = T // 2``.
+    ``k_lo = max(1, ceil(lo T t_r))`` and ``k_hi = min(K, floor(hi T t_r))``: a frequency exactly on a bin is inside.
+    Host only: Python floats, no tensor, no device.  ``k_lo > k_hi`` says that the band holds no bin."""
+    if isinstance(T, bool) or not isinstance(T, int):
+        raise TypeError(f"T must be an int, got {type(T).__name__}")
+    if T < 2:
+        raise ValueError(f"a run has T >= 2 frames, got T = {T}")
+    t_r = _finite_number("t_r", t_r)
+    if t_r <= 0.0:
+        raise ValueError(f"t_r must be > 0, got {t_r}")
+    if not isinstance(band, (tuple, list)) or len(band) != 2:
+        raise TypeError(f"band must be a pair (lo, hi) in Hz, got {band!r}")
+    lo, hi = _finite_number("band[0]", band[0]), _finite_number("band[1]", band[1])
+    if not 0.0 <= lo < hi:
+        raise ValueError(f"band must be (lo, hi) with 0 <= lo < hi, got ({lo}, {hi})")
+    return max(1, math.ceil(lo * T * t_r)), min(T // 2, math.floor(hi * T * t_r))
+
+
+def _series_feature_ids(features) -> list:
+    if isinstance(features, str):
+        features = (features,)
+    names = list(features)
+    if not names:
+        raise ValueError(f"features is empty; choose from SERIES_FEATURES = {SERIES_FEATURES}")
+    for name in names:
+        if name not in SERIES_FEATURES:
+            raise ValueError(f"unknown series feature {name!r}; choose from SERIES_FEATURES = {SERIES_FEATURES}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"features repeats a name: {names}; each of SERIES_FEATURES = {SERIES_FEATURES} at most once")
+    return [SERIES_FEATURES.index(name) for name in names]
+
+
+def series_features(timeseries: torch.Tensor, *, t_r=None, band=(0.01, 0.08), features=SERIES_FEATURES) -> torch.Tensor:
+    """Regional activity features of the series themselves (module docstring): float32 ``[S, n, len(features)]`` on the
+    time series' device, the columns in the order of ``features``, any non-empty subset of ``SERIES_FEATURES`` without
+    repeats.  What ``node_features=`` of ``from_timeseries`` and ``from_matrices`` takes; with graph measures,
+    ``torch.cat`` it with ``node_measures``.  ``t_r`` (seconds) and ``band = (lo, hi)`` in Hz, ``0 <= lo < hi``, are needed
+    exactly by the spectral names, those other than ``std`` and ``autocorr1``: the band is the bins
+    ``series_band(T, t_r, band)``, and a band without a bin is a ``ValueError``; so is ``T > SERIES_MAX_FRAMES`` with a
+    spectral name.  The time series are float32 ``[S, T, n]``, contiguous and resident; they are left untouched, whole
+    runs only.  There is no ``sample_mask=``: a censored run goes through ``interpolate_censored`` first, as it does in
+    front of a band-pass.  One launch for ``std`` and ``autocorr1``, three with a band, four with ``falff``, which walks
+    the whole spectrum (``band_fraction`` is its cheap substitute); the temporaries are the cos/sin table ``[T, 2 bins]``
+    and seven doubles per column.  The same bits on every run, for every grid and for every subset or order of names.
+    No read-back.  Raises, before any device work: ``ValueError`` for an unknown, repeated or missing name, a missing,
+    non-finite or non-positive ``t_r``, a band that is not ``0 <= lo < hi`` or holds no bin, a run too long or not
+    ``[S, T, n]``; and, as every time-series call does, ``TypeError`` for series that are not float32 and
+    ``RuntimeError`` for series that are not on a ROCm device."""
+    ids = _series_feature_ids(features)
+    spectral = any(SERIES_FEATURES[i] in _SERIES_SPECTRAL for i in ids)
+    S, T, n = _check_run(timeseries)[:3]
+    k_lo = k_hi = bins = 0
+    if spectral:
+        if t_r is None:
+            raise ValueError(f"the features {_SERIES_SPECTRAL} are spectral: give t_r= (seconds per frame) with them")
+        k_lo, k_hi = series_band(T, t_r, band)
+        if k_lo > k_hi:
+            raise ValueError(f"the band {tuple(band)} Hz at t_r={t_r} holds no bin of a {T}-frame run (bins {k_lo} .. "
+                             f"{k_hi}; bin k has k / (T t_r) Hz, k = 1 .. {T // 2})")
+        if T > SERIES_MAX_FRAMES:
+            raise ValueError(f"T = {T} > SERIES_MAX_FRAMES = {SERIES_MAX_FRAMES}: the spectral features "
+                             f"{_SERIES_SPECTRAL} take runs up to that length; ('std', 'autocorr1') take any")
+        # the table's bins: the whole spectrum for falff, else the band from an odd bin on (cgnn_activity.h)
+        bins = T // 2 if SERIES_FEATURES.index("falff") in ids else k_hi - ((k_lo - 1) | 1) + 1
+    _require_resident(timeseries, *_SERIES)
+    out = torch.empty((S, n, len(ids)), dtype=torch.float32, device=timeseries.device)
+    if S == 0:
+        return out
+    _call(timeseries.device, "cgnn_ingest_activity", timeseries, S, T, n, (ctypes.c_int32 * len(ids))(*ids), len(ids),
+          k_lo, k_hi, _WORK, *_lib.buf(out), workspace=("cgnn_ingest_activity", S, T, n, bins))
     return out
 
 
