@@ -320,6 +320,14 @@ ACTIVITY_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_pagerank.h declares (cgnn.h includes it), in the same form, and the largest damping.
+PAGERANK_MAX_DAMPING = 0.99
+PAGERANK_PROTOTYPES = {
+    "cgnn_ingest_pagerank_workspace_bytes": (I64, [I64, I32, P, I32]),
+    "cgnn_ingest_pagerank": (c_int, [P, I64, I32, P, P, I32, P, I32, F64, P, I64, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -339,7 +347,8 @@ def load() -> ctypes.CDLL:
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
-                              **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES}.items():
+                              **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
+                              **PAGERANK_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

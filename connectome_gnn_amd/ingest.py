@@ -483,6 +483,20 @@ product with a cos/sin table of the bins asked for on the fp32 matrix pipe (csrc
 sums, ratios and roots in fp64, one rounding; no coefficient is stored.  ``falff`` alone walks the whole spectrum: its table
 is ``[T, 2 K]`` floats, hence ``T <= SERIES_MAX_FRAMES`` for the spectral names, and it costs ``K / (k_hi - k_lo + 1)``
 times the band's product; ``band_fraction`` is the cheap substitute.
+
+Centrality: ``centrality_measures(matrices, keep=.., measures=CENTRALITY_MEASURES, damping=0.85)`` gives
+the PageRank of every node, the one measure here of the recursive kind (a node matters because its neighbours do), as
+``[S, n, len(measures)]``, which ``node_features=`` takes.  With the edge test ``e_ij`` above, entry ``(i, j)`` an edge
+``j -> i``, ``w_ij = A_ij`` (``weighted_pagerank``) or 1 (``pagerank``) where ``e_ij``, and ``c_j = sum_i w_ij`` the
+out-strength of ``j`` (a column sum: the row sum on the symmetric matrices of real cohorts), ``x`` is the solution of
+``x_i = d (sum_j w_ij x_j / c_j + (sum_{c_j == 0} x_j) / n) + (1 - d) / n``, which sums to 1: a dangling node's mass is
+spread uniformly (networkx's convention).  The solution is unique on any graph, disconnected ones included.  Everything
+after the fp32 edge test is fp64, rounded to fp32 once: the iteration from ``x = 1 / n``, two products a step, stops at
+the first step whose L1 change is at most ``(1 - d) 2^-42``, which leaves ``2^-42`` in L1, at the latest after
+``ceil(43 ln 2 / -ln d) + 2`` steps (186 at ``d = 0.85``; never reached in exact arithmetic).  A subject without kept
+entries is exactly ``1 / n``; a kept ``+inf`` makes that subject's ``weighted_pagerank`` NaN and nothing else.  One launch (csrc/pagerank.hip), a workgroup per subject with its kept entries
+compacted into LDS where they fit (``n <= PAGERANK_MAX_NODES = 1024``); no workspace, no atomics, no read-back, the same
+bits on every run, for every grid and for every subset and order of the two names.
 """
 from __future__ import annotations
 
@@ -526,6 +540,9 @@ MODULE_MAX_NODES = 1024                               # CGNN_MODULE_MAX_NODES: a
 SERIES_FEATURES = ("std", "autocorr1", "alff", "falff", "band_std", "band_fraction")   # ids: include/cgnn_activity.h
 SERIES_MAX_FRAMES = 4096                              # CGNN_ACTIVITY_MAX_FRAMES: falff's table [T, 2 (T // 2)] stays <= 64 MB
 _SERIES_SPECTRAL = SERIES_FEATURES[2:]                # the names that need t_r and a band
+CENTRALITY_MEASURES = ("pagerank", "weighted_pagerank")   # ids: include/cgnn_pagerank.h
+PAGERANK_MAX_NODES = 1024                             # CGNN_PAGERANK_MAX_NODES: a kept entry's column is stored in 16 bits
+PAGERANK_MAX_DAMPING = _lib.PAGERANK_MAX_DAMPING      # CGNN_PAGERANK_MAX_DAMPING: the step bound grows as 1 / (1 - d)
 
 
 class _Family(NamedTuple):
@@ -1747,6 +1764,85 @@ def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None
     _run_family(_MODULES, matrices, S, n, thr, [], [], None, modules=(labels.to(matrices.device), M), profile=profile,
                 profile_flags=flags)
     return profile
+
+
+def _centrality_ids(measures) -> list:
+    """A valid request of ``centrality_measures``, a non-empty tuple of distinct names, as their ids."""
+    if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
+        raise TypeError(f"measures must be a tuple of names from {CENTRALITY_MEASURES}, got {measures!r}")
+    if len(measures) == 0:
+        raise ValueError(f"measures is empty: name at least one of {CENTRALITY_MEASURES}")
+    ids = []
+    for name in measures:
+        if name not in CENTRALITY_MEASURES:
+            raise ValueError(f"unknown measure {name!r}: the centrality measures are {CENTRALITY_MEASURES}")
+        if CENTRALITY_MEASURES.index(name) in ids:
+            raise ValueError(f"measure {name!r} is named twice")
+        ids.append(CENTRALITY_MEASURES.index(name))
+    return ids
+
+
+def _check_damping(damping) -> float:
+    if isinstance(damping, bool) or not isinstance(damping, (int, float)):
+        raise TypeError(f"damping must be a number, got {type(damping).__name__}")
+    if not 0.0 <= damping <= PAGERANK_MAX_DAMPING:    # (a NaN is refused here too)
+        raise ValueError(f"damping must lie in [0, {PAGERANK_MAX_DAMPING}], got {damping}")
+    return float(damping)
+
+
+def pagerank_max_steps(damping) -> int:
+    """``K_max(d) = ceil(43 ln 2 / -ln d) + 2``, the cap on the steps of ``centrality_measures`` (2 for ``d == 0``).  A
+    step is two products, each contracts at rate ``d`` in L1, and the start is at most 2 away: step ``K`` changes by at
+    most ``2 (1 + d) d^(2 K - 1)``, below ``2^-84`` at the cap, so the stopping rule ``change <= (1 - d) 2^-42`` holds
+    before it in exact arithmetic."""
+    d = _check_damping(damping)
+    return int(math.ceil(43.0 * math.log(2.0) / -math.log(d))) + 2 if d > 0.0 else 2
+
+
+def _pagerank(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x: torch.Tensor, damping: float,
+              iterations=None) -> torch.Tensor:
+    """cgnn_ingest_pagerank: measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as
+    they are), and the step counts into ``iterations`` ``[S]`` int32 if given.  Returns ``x``."""
+    if S:
+        num = len(ids)
+        arr = (ctypes.c_int32 * num)(*ids)
+        _call(matrices.device, "cgnn_ingest_pagerank", matrices, S, n, thr, arr, num, (ctypes.c_int32 * num)(*cols),
+              x.shape[2], damping, _WORK, *_lib.buf(x), *_lib.buf(iterations),
+              workspace=("cgnn_ingest_pagerank", S, n, arr, num))
+    return x
+
+
+def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
+                        knn_mode="union", backbone=None, measures=CENTRALITY_MEASURES, damping=0.85) -> torch.Tensor:
+    """PageRank centrality of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
+    ``matrices.device``, one column per name in ``measures``, names from ``CENTRALITY_MEASURES`` in any order (module
+    docstring): ``pagerank`` walks the kept entries with equal weights, ``weighted_pagerank`` with the entries' values.
+    The edges are those ``node_measures`` sees for the same ``keep`` / ``num_edges`` / ``min_weight`` / ``knn`` /
+    ``knn_mode`` / ``backbone``, chosen the same way (``knn=`` and ``backbone=`` cost the cohort-sized temporaries named
+    in ``from_matrices``).  ``damping`` is the probability ``d`` of following an edge, a number in
+    ``[0, PAGERANK_MAX_DAMPING]``.  Every value is at least ``(1 - d) / n`` and a subject's values sum to 1; an entry
+    ``(i, j)`` is an edge ``j -> i`` and a node without out-strength spreads its mass uniformly.  One launch on resident
+    data (csrc/pagerank.hip); no workspace, no read-back, no atomics: every run, every grid and every subset and order of
+    the names gives the same bits.  ``n <= PAGERANK_MAX_NODES``.  The result is what ``node_features=`` of
+    ``from_matrices`` / ``from_timeseries`` takes; its two columns keep a cohort on the fused GCN path.
+
+    This is a call of its own beside ``module_profile`` and ``series_features`` and the names are not among those of
+    ``node_measures(measures=)``: that table of four families and seventeen names is pinned.  The C entry point writes
+    its columns inside a wider ``x`` (cols / ldx) so that a later change can merge the names into ``measures=``."""
+    S, n = _check_matrices(matrices)
+    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    ids = _centrality_ids(measures)
+    damping = _check_damping(damping)
+    if n > PAGERANK_MAX_NODES:
+        raise ValueError(f"centrality_measures takes n <= {PAGERANK_MAX_NODES} nodes (a kept entry's column is stored in "
+                         f"16 bits), got n = {n}")
+    _require_resident(matrices, *_MATRICES)
+    if edges is not None:
+        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
+    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
+    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
+    return _pagerank(matrices, S, n, thr, ids, list(range(len(ids))), x, damping)
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
