@@ -27,6 +27,8 @@
 
 #include "common.h"
 #include "ingest_rows.h"
+#include "measure_request.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -73,27 +75,6 @@ __device__ __forceinline__ void store4(float* B, int n, int i, int j0, f32x4 x) 
   }
 }
 
-// Between a wave's LDS accesses that other lanes of the same wave depend on: the hardware completes them in order, and
-// this keeps the compiler from reordering them.
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The inclusive prefix sum of v over the 64 lanes, in registers (no LDS traffic: the select is bound by it): sums within
-// rows of 16 lanes by row_shr 1, 2, 4, 8 (a lane without a source adds 0), then lane 15 of a row into the next row
-// (row_bcast:15 on rows 1 and 3) and lane 31 into the upper half (row_bcast:31 on rows 2 and 3).
-__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
-  int x = (int)v;
-  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-  return (uint32_t)x;
-}
-
 // Phase 1 for row i, by one wave: (v_i, c_i) into LDS.
 template <int NC>
 __device__ __forceinline__ void row_picks(const float* A, int n, int i, int64_t k, int lane, KnnShared& sh) {
@@ -134,7 +115,7 @@ __device__ __forceinline__ void row_picks(const float* A, int n, int i, int64_t 
     const cgnn_u32x4 h = *reinterpret_cast<const cgnn_u32x4*>(hist + 252 - 4 * lane);
     const uint32_t cnt[4] = {h[3], h[2], h[1], h[0]};                  // bins 255 - 4 l - q, q = 0..3
     const uint32_t tsum = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    const uint32_t incl = wave_prefix_sum(tsum);
+    const uint32_t incl = (uint32_t)wave_scan((int)tsum);   // (in registers: the select is bound by its LDS traffic)
     uint32_t run = incl - tsum, digit = 0u, left = 0u;
     const bool mine = run <= rank && rank < incl;                      // exactly one lane: the rank lies in its bins
 #pragma unroll
@@ -277,16 +258,11 @@ __global__ __launch_bounds__(kThreads) void k_knn(const float* matrices, int64_t
 
 extern "C" int cgnn_ingest_knn(const float* matrices, int64_t S, int32_t n, int64_t k, int32_t mode, float* out,
                                int64_t out_bytes, void* stream) {
-  if (S < 0 || n < 1 || k < 0) return CGNN_EINVAL;
-  if (mode != CGNN_KNN_DIRECTED && mode != CGNN_KNN_UNION && mode != CGNN_KNN_MUTUAL) return CGNN_EINVAL;
-  if (n > CGNN_KNN_MAX_NODES) return CGNN_EUNSUPPORTED;
-  if (cgnn_check_cohort(S, n) != CGNN_OK) return CGNN_EINVAL;
+  if (k < 0 || (mode != CGNN_KNN_DIRECTED && mode != CGNN_KNN_UNION && mode != CGNN_KNN_MUTUAL)) return CGNN_EINVAL;
+  if (const int rc = cgnn_check_cohort_within(S, n, CGNN_KNN_MAX_NODES)) return rc;
   if (S == 0) return CGNN_OK;
   if (!matrices || !out || cgnn_misaligned({matrices, out}, 3)) return CGNN_EINVAL;
-  const int64_t bytes = S * (int64_t)n * n * (int64_t)sizeof(float);
-  if (out_bytes < bytes) return CGNN_EINVAL;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(matrices), b = reinterpret_cast<uintptr_t>(out);
-  if (a != b && a < b + (uintptr_t)bytes && b < a + (uintptr_t)bytes) return CGNN_EINVAL;
+  if (cgnn_check_cohort_out(matrices, out, out_bytes, S, n) != CGNN_OK) return CGNN_EINVAL;
   const int grid = cgnn_grid_for(S, CGNN_KNN_WG_PER_CU);
   hipStream_t st = cgnn_stream(stream);
   switch ((n + 255) / 256) {

@@ -1,7 +1,8 @@
-// measure_request.h -- the host side that the node-measure families share (measures.hip, paths.hip, wpaths.hip;
-// DESIGN.md 4.3g): the columns a kernel writes, the check of a request, of the cohort's size and of its buffers, and
-// the two rules of a one-workgroup-per-subject launch on dynamic LDS.  Host code only; every check is CGNN_OK or
-// CGNN_EINVAL and touches no device.
+// measure_request.h -- the host side that the cohort entry points share (measures.hip, paths.hip, wpaths.hip,
+// modules.hip, pagerank.hip, knn.hip, mst.hip): the columns a kernel writes, the check of a
+// request, of the cohort's size, of its buffers and of an output that may be the input, and the two rules of a
+// one-workgroup-per-subject launch on dynamic LDS.  Host code only; every check is CGNN_OK or CGNN_EINVAL
+// (cgnn_check_cohort_within: or CGNN_EUNSUPPORTED) and touches no device.
 #pragma once
 #include "common.h"
 
@@ -40,6 +41,35 @@ inline int cgnn_check_request(const int32_t* measures, int32_t num, int32_t min_
 // cgnn_check_cohort for a family that keeps a subject in LDS: n <= max_n is the stricter bound on n * n.
 inline int cgnn_check_cohort_upto(int64_t S, int32_t n, int32_t max_n) {
   return n > max_n ? CGNN_EINVAL : cgnn_check_cohort(S, n);
+}
+
+// The sizes of an entry point that answers CGNN_EUNSUPPORTED beyond its node bound (knn.hip, mst.hip): bad values
+// first, then the bound, then cgnn_check_cohort.  cgnn_check_cohort_upto's families answer CGNN_EINVAL for the bound.
+inline int cgnn_check_cohort_within(int64_t S, int32_t n, int32_t max_n) {
+  if (S < 0 || n < 1) return CGNN_EINVAL;
+  if (n > max_n) return CGNN_EUNSUPPORTED;
+  return cgnn_check_cohort(S, n);
+}
+
+// Whether [p, p + p_bytes) and [q, q + q_bytes) share a byte.
+inline bool cgnn_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
+}
+
+// A cohort-shaped `out` that may be the input itself: it holds S n n floats, and is `matrices` or disjoint from them.
+inline int cgnn_check_cohort_out(const void* matrices, const void* out, int64_t out_bytes, int64_t S, int32_t n) {
+  const int64_t bytes = S * (int64_t)n * n * (int64_t)sizeof(float);
+  if (out_bytes < bytes) return CGNN_EINVAL;
+  return matrices != out && cgnn_overlap(matrices, bytes, out, bytes) ? CGNN_EINVAL : CGNN_OK;
+}
+
+// What a call refuses even when S == 0 keeps it from launching (modules.hip, pagerank.hip): a negative byte count, a
+// workspace that is not 16-byte aligned.
+inline int cgnn_check_byte_counts(const void* workspace, std::initializer_list<int64_t> byte_counts) {
+  for (const int64_t b : byte_counts)
+    if (b < 0) return CGNN_EINVAL;
+  return cgnn_misaligned({workspace}, 15) ? CGNN_EINVAL : CGNN_OK;
 }
 
 // The buffers of a call that launches (S > 0): matrices and thr are there, they and x are 4-byte aligned, the

@@ -37,6 +37,7 @@
 
 #include "ingest_rows.h"
 #include "measure_request.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -61,43 +62,6 @@ inline int pass_of(int M) { return M < kPass ? M : kPass; }
 inline size_t lds_of(int n, int M) {
   return sizeof(double) * ((size_t)kWaves * pass_of(M) * kSlotLd + 2 * (size_t)n + kStat * (size_t)M) +
          sizeof(int32_t) * ((size_t)n + 2 * (size_t)M);
-}
-
-// Between a wave's LDS accesses that other lanes of the same wave depend on: the hardware completes them in order, and
-// this keeps the compiler from reordering them.
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The sum of v over the 64 lanes, on every lane, in registers (a row's results hang on five such sums in a chain: no
-// LDS round trips): an inclusive scan -- sums within rows of 16 lanes by row_shr 1, 2, 4, 8 (a lane without a source
-// adds 0), then lane 15 of a row into the next row (row_bcast:15 on rows 1 and 3) and lane 31 into the upper half
-// (row_bcast:31 on rows 2 and 3) -- whose last lane is read back.  The order of the additions is fixed.
-template <int kCtrl, int kRows>
-__device__ __forceinline__ int dpp_add(int v) {
-  return v + __builtin_amdgcn_update_dpp(0, v, kCtrl, kRows, 0xf, false);
-}
-template <int kCtrl, int kRows>
-__device__ __forceinline__ double dpp_add(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, kRows, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, kRows, 0xf, false);
-  return v + __hiloint2double(hi, lo);
-}
-template <typename T>
-__device__ __forceinline__ T wave_scan(T v) {
-  v = dpp_add<0x111, 0xf>(v);
-  v = dpp_add<0x112, 0xf>(v);
-  v = dpp_add<0x114, 0xf>(v);
-  v = dpp_add<0x118, 0xf>(v);
-  v = dpp_add<0x142, 0xa>(v);
-  return dpp_add<0x143, 0xc>(v);
-}
-__device__ __forceinline__ int wave_total(int v) { return __builtin_amdgcn_readlane(wave_scan(v), 63); }
-__device__ __forceinline__ double wave_total(double v) {
-  v = wave_scan(v);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
-                          __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
 template <int R>
@@ -344,8 +308,7 @@ extern "C" int cgnn_ingest_modules(const float* matrices, int64_t S, int32_t n, 
   if (check(S, n, measures, num_measures, cols, ldx, true, &c) != CGNN_OK) return CGNN_EINVAL;
   if (M < 1 || M > CGNN_MODULE_MAX || M > n) return CGNN_EINVAL;
   if (profile_flags & ~(CGNN_MODULE_PROFILE_BINARY | CGNN_MODULE_PROFILE_NORMALIZE)) return CGNN_EINVAL;
-  if (workspace_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
-  if (x_bytes < 0 || profile_bytes < 0) return CGNN_EINVAL;
+  if (cgnn_check_byte_counts(workspace, {workspace_bytes, x_bytes, profile_bytes}) != CGNN_OK) return CGNN_EINVAL;
   if (num_measures == 0 && !profile) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
   // x [S n][ldx] if measures are asked for, profile [S n][M] if given; one of the two

@@ -42,6 +42,8 @@
 
 #include "common.h"
 #include "ingest_rows.h"
+#include "measure_request.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -77,13 +79,6 @@ __device__ __forceinline__ void store4(float* B, int n, int i, int j0, f32x4 x) 
     for (int q = 0; q < 3; ++q)
       if (j0 + q < n) row[j0 + q] = x[q];
   }
-}
-
-// Between a wave's LDS accesses that other lanes of the same wave depend on: the hardware completes them in order, and
-// this keeps the compiler from reordering them.
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 // the bits of p(x): those of x if x > 0, else 0
@@ -242,11 +237,6 @@ __global__ __launch_bounds__(kThreads) void k_mst(const float* matrices, int64_t
 
 int64_t slab_floats_of(int n) { return (int64_t)n * ((n + 3) & ~3); }      // rows of ld floats: a multiple of 16 bytes
 
-bool overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
 }  // namespace
 
 extern "C" int64_t cgnn_ingest_mst_workspace_bytes(int64_t S, int32_t n) {
@@ -256,21 +246,18 @@ extern "C" int64_t cgnn_ingest_mst_workspace_bytes(int64_t S, int32_t n) {
 
 extern "C" int cgnn_ingest_mst(const float* matrices, int64_t S, int32_t n, const float* thresholds, void* workspace,
                                int64_t workspace_bytes, float* out, int64_t out_bytes, void* stream) {
-  if (S < 0 || n < 1) return CGNN_EINVAL;
-  if (n > CGNN_MST_MAX_NODES) return CGNN_EUNSUPPORTED;
-  if (cgnn_check_cohort(S, n) != CGNN_OK) return CGNN_EINVAL;
+  if (const int rc = cgnn_check_cohort_within(S, n, CGNN_MST_MAX_NODES)) return rc;
   if (S == 0) return CGNN_OK;
   if (!matrices || !out || !workspace || cgnn_misaligned({matrices, out, thresholds}, 3) ||
       cgnn_misaligned({workspace}, 15))
     return CGNN_EINVAL;
+  if (cgnn_check_cohort_out(matrices, out, out_bytes, S, n) != CGNN_OK) return CGNN_EINVAL;
   const int64_t bytes = S * (int64_t)n * n * (int64_t)sizeof(float);
-  if (out_bytes < bytes) return CGNN_EINVAL;
   const int grid = cgnn_grid_for(S, CGNN_MST_WG_PER_CU);
   const int64_t slab = slab_floats_of(n), need = grid * slab * (int64_t)sizeof(float);
   if (workspace_bytes < need) return CGNN_EINVAL;
-  if (matrices != out && overlap(matrices, bytes, out, bytes)) return CGNN_EINVAL;
-  if (overlap(workspace, need, matrices, bytes) || overlap(workspace, need, out, bytes)) return CGNN_EINVAL;
-  if (thresholds && overlap(thresholds, S * (int64_t)sizeof(float), out, bytes)) return CGNN_EINVAL;
+  if (cgnn_overlap(workspace, need, matrices, bytes) || cgnn_overlap(workspace, need, out, bytes)) return CGNN_EINVAL;
+  if (thresholds && cgnn_overlap(thresholds, S * (int64_t)sizeof(float), out, bytes)) return CGNN_EINVAL;
   k_mst<<<grid, kThreads, 0, cgnn_stream(stream)>>>(matrices, S, n, thresholds, static_cast<float*>(workspace), slab,
                                                     out);
   CGNN_CHECK_LAUNCH();

@@ -36,6 +36,7 @@
 
 #include "ingest_rows.h"
 #include "measure_request.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -67,26 +68,6 @@ struct Params {
   int space;                                  // bytes of LDS behind the fixed part
 };
 
-// v + (v moved across lanes by the DPP control kCtrl, on the rows of kRows), in registers
-template <int kCtrl, int kRows>
-__device__ __forceinline__ double dpp_add(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, kRows, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, kRows, 0xf, false);
-  return v + __hiloint2double(hi, lo);
-}
-// The sum of v over the 64 lanes, on every lane (modules.hip's): an inclusive scan -- row_shr 1, 2, 4, 8 within rows of
-// 16 lanes (a lane without a source adds 0), row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3 -- whose
-// last lane is read back.  Needs every lane active.
-__device__ __forceinline__ double wave_total(double v) {
-  v = dpp_add<0x111, 0xf>(v);
-  v = dpp_add<0x112, 0xf>(v);
-  v = dpp_add<0x114, 0xf>(v);
-  v = dpp_add<0x118, 0xf>(v);
-  v = dpp_add<0x142, 0xa>(v);
-  v = dpp_add<0x143, 0xc>(v);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
-                          __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
 // The sum of v over each aligned group of 8 lanes, on every lane of the group: the neighbour (quad_perm [1,0,3,2]), the
 // other pair (quad_perm [2,3,0,1]), the other quad (row_half_mirror).  Needs every lane active.
 __device__ __forceinline__ double group8_total(double v) {
@@ -386,8 +367,7 @@ extern "C" int cgnn_ingest_pagerank(const float* matrices, int64_t S, int32_t n,
   Columns c;
   if (check(S, n, measures, num_measures, cols, ldx, true, &c) != CGNN_OK) return CGNN_EINVAL;
   if (!(damping >= 0.0 && damping <= CGNN_PAGERANK_MAX_DAMPING)) return CGNN_EINVAL;        // (a NaN fails both)
-  if (workspace_bytes < 0 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CGNN_EINVAL;
-  if (x_bytes < 0 || iterations_bytes < 0) return CGNN_EINVAL;
+  if (cgnn_check_byte_counts(workspace, {workspace_bytes, x_bytes, iterations_bytes}) != CGNN_OK) return CGNN_EINVAL;
   if (S == 0) return CGNN_OK;
   if (cgnn_check_cohort_buffers(matrices, thr, workspace, x, x_bytes, true, S * n, c.ldx) != CGNN_OK) return CGNN_EINVAL;
   if (cgnn_misaligned({iterations}, 3)) return CGNN_EINVAL;

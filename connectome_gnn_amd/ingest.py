@@ -555,6 +555,7 @@ class _Family(NamedTuple):
     what: str = ""
     why: str = ""
     modules: bool = False                             # takes modules / M, and profile / profile_bytes / profile_flags
+    tail: tuple = ()                                  # what follows x / x_bytes when no more than x is asked for
 
 
 _FAMILIES = (                                         # in the order of their calls
@@ -562,12 +563,16 @@ _FAMILIES = (                                         # in the order of their ca
     _Family(PATH_MEASURES, "cgnn_ingest_paths", True, False, PATH_MAX_NODES, "path measures",
             "the adjacency bitset of a subject must fit LDS"),
     _Family(WEIGHTED_PATH_MEASURES, "cgnn_ingest_wpaths", True, True, WEIGHTED_PATH_MAX_NODES,
-            "weighted path measures", "both panels of a Floyd-Warshall round must fit LDS"),
+            "weighted path measures", "both panels of a Floyd-Warshall round must fit LDS", tail=_lib.buf(None)),
     _Family(MODULE_MEASURES, "cgnn_ingest_modules", True, False, MODULE_MAX_NODES, "module measures",
-            "a row lives in 16 registers per lane", modules=True))
+            "a row lives in 16 registers per lane", modules=True, tail=_lib.buf(None) + (0,)))
 _WEIGHTED = _FAMILIES[2]                              # path_lengths's
 _MODULES = _FAMILIES[3]                               # module_profile's
 _ALL_MEASURES = tuple(name for fam in _FAMILIES for name in fam.names)
+# centrality_measures's: a call of its own, so not among _FAMILIES, whose names measures= takes (damping stands in front
+# of the workspace, iterations / iterations_bytes follow x)
+_CENTRALITY = _Family(CENTRALITY_MEASURES, "cgnn_ingest_pagerank", True, False, PAGERANK_MAX_NODES,
+                      "centrality measures", "a kept entry's column is stored in 16 bits", tail=_lib.buf(None))
 
 
 def _check_matrices(matrices) -> tuple:
@@ -649,10 +654,14 @@ def _call(dev, name: str, *args, workspace=None) -> None:
         _lib.call(name, *args, device=dev)
 
 
-def _thresholds(matrices: torch.Tensor, S: int, keep, num_edges, min_weight) -> torch.Tensor:
-    """The ``[S]`` float32 thresholds of a valid choice on the matrices' device: selected there, or ``min_weight``."""
+def _thresholds(matrices: torch.Tensor, k: int, min_weight) -> torch.Tensor:
+    """The ``[S]`` float32 thresholds of ``_threshold_choice``'s pair on the resident matrices' device: the entries of
+    rank ``k``, selected there (cgnn_ingest_select), or ``min_weight``."""
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
     if min_weight is None:
-        return select_thresholds(matrices, keep=keep, num_edges=num_edges)
+        thr = torch.empty(S, dtype=torch.float32, device=matrices.device)
+        _call(matrices.device, "cgnn_ingest_select", matrices, S, n, k, *_lib.buf(thr))
+        return thr
     if isinstance(min_weight, torch.Tensor):
         return min_weight.to(device=matrices.device, dtype=torch.float32).contiguous()
     return torch.full((S,), min_weight, dtype=torch.float32, device=matrices.device)
@@ -754,17 +763,17 @@ def filter_components(T: int, t_r, high_pass=None, low_pass=None) -> tuple:
     return k_lo, k_hi
 
 
-def _check_out(out, timeseries: torch.Tensor) -> None:
+def _check_out(out, like: torch.Tensor, noun="time series") -> None:
     if out is None:
         return
     if not isinstance(out, torch.Tensor):
         raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
     if out.dtype != torch.float32:
         raise TypeError(f"out must be float32, got {out.dtype}")
-    if out.shape != timeseries.shape:
-        raise ValueError(f"out must be {tuple(timeseries.shape)} as the time series are, got {tuple(out.shape)}")
-    if out.device != timeseries.device:
-        raise ValueError(f"out is on {out.device}, the time series on {timeseries.device}")
+    if out.shape != like.shape:
+        raise ValueError(f"out must be {tuple(like.shape)} as the {noun} are, got {tuple(out.shape)}")
+    if out.device != like.device:
+        raise ValueError(f"out is on {out.device}, the {noun} on {like.device}")
     if not out.is_contiguous():
         raise ValueError("out must be contiguous")
 
@@ -1404,17 +1413,17 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
     _check_modules_argument(ids, modules, n)
-    edges, keep, num_edges, min_weight = _edge_choice(n, U, "U", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    _, min_weight = _threshold_choice(n, U, "U", keep, num_edges, min_weight)
+    edges = _edge_plan(n, U, "U", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
     matrices = _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, sample_mask)
-    if edges is not None:
-        _sparsified(matrices, U, edges, matrices)
-    return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), keep=keep,
-                         num_edges=num_edges, min_weight=min_weight, node_features=node_features, measures=measures,
-                         modules=modules)
+    choice = dict(keep=keep, num_edges=num_edges, min_weight=min_weight)       # the caller's, as they came
+    if edges.sparsify:
+        edges.sparsified(matrices, matrices)
+        choice = dict(min_weight=0.0)
+    return from_matrices(matrices, labels if W == 1 else labels.repeat_interleave(W), node_features=node_features,
+                         measures=measures, modules=modules, **choice)
 
 
 def _check_knn(n: int, k, mode) -> tuple:
@@ -1460,74 +1469,82 @@ def _check_mst_size(n: int) -> None:
                          f"phase), got n = {n}")
 
 
-def _at_most_one(keep, num_edges, min_weight) -> bool:
-    """Whether one of the three thresholds is given, where none need be; two are refused."""
+def _tree_thresholds(n: int, units: int, unit_name: str, keep, num_edges, min_weight):
+    """``_threshold_choice``'s pair of the one threshold a backbone is united with, where none need be given (None: the
+    tree alone); two are refused."""
     given = sum(a is not None for a in (keep, num_edges, min_weight))
     if given > 1:
         raise ValueError("the backbone is united with at most one of keep=, num_edges= and min_weight=")
-    return given == 1
+    return _threshold_choice(n, units, unit_name, keep, num_edges, min_weight) if given else None
 
 
 class _Edges(NamedTuple):
-    """How a call sparsifies its matrices before it runs at ``min_weight=0.0``: the k-NN graph of ``_check_knn``'s pair
-    (None: no ``knn=``), united with the tree if ``tree``; without ``knn=`` the tree united with the threshold choice
-    (all three None: the tree alone)."""
+    """The valid edge choice of a call.  With ``knn`` (``_check_knn``'s pair) or ``tree`` the matrices are sparsified
+    first: the k-NN graph, united with the tree if ``tree``; without ``knn`` the tree united with the thresholds of
+    ``united`` (``_threshold_choice``'s pair; None: the tree alone).  The call then goes on at ``_threshold_choice``'s
+    pair ``(k, min_weight)``, which on sparsified matrices is ``min_weight=0.0``."""
     knn: Optional[tuple]
     tree: bool
-    keep: Optional[float]
-    num_edges: Optional[int]
+    united: Optional[tuple]
+    k: int
     min_weight: object
 
+    @property
+    def sparsify(self) -> bool:
+        return self.knn is not None or self.tree
 
-def _edge_choice(n: int, units: int, unit_name: str, knn, knn_mode, backbone, keep, num_edges, min_weight) -> tuple:
-    """``(edges, keep, num_edges, min_weight)``: without ``knn=`` and ``backbone=`` None and the three as they came (the
-    call then chooses its edges as it always did, and checks the three itself); else the valid ``_Edges`` and the choice
-    the call goes on with on the sparsified matrices, ``min_weight=0.0``."""
+    def sparsified(self, matrices: torch.Tensor, out=None) -> torch.Tensor:
+        """The resident matrices sparsified, into ``out`` (which may be ``matrices``) or a new tensor."""
+        if self.knn is None:
+            return _mst(matrices, None if self.united is None else _thresholds(matrices, *self.united), out)
+        tree = _mst(matrices, None) if self.tree else None            # (before `out` may overwrite the matrices)
+        out = _knn(matrices, self.knn, out)
+        return out if tree is None else torch.maximum(out, tree, out=out)
+
+    def apply(self, matrices: torch.Tensor, select=True) -> tuple:
+        """``(matrices, thr)`` for the caller's matrices, which must be resident and are left as they are: the matrices
+        the call goes on with -- sparsified ones are the cohort-sized temporary (two for ``knn=`` with a backbone) --
+        and their ``[S]`` thresholds.  Without ``select``, ``thr`` is None where a rank is to be selected: for
+        cgnn_ingest_count, which does that with no launch of its own."""
+        _require_resident(matrices, *_MATRICES)
+        if self.sparsify:
+            matrices = self.sparsified(matrices)
+        if self.min_weight is None and not select:
+            return matrices, None
+        return matrices, _thresholds(matrices, self.k, self.min_weight)
+
+
+def _edge_plan(n: int, units: int, unit_name: str, knn, knn_mode, backbone, keep, num_edges, min_weight) -> _Edges:
+    """The ``_Edges`` of a call's whole edge choice: exactly one of the three thresholds; or ``knn=`` with none of
+    them; or ``backbone=`` with at most one of them, or with ``knn=``."""
     choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
     tree = _check_backbone(n, backbone)
     if choice is None and not tree:
-        return None, keep, num_edges, min_weight
-    if choice is None and _at_most_one(keep, num_edges, min_weight):
-        _, min_weight = _threshold_choice(n, units, unit_name, keep, num_edges, min_weight)
-    return _Edges(choice, tree, keep, num_edges, min_weight), None, None, 0.0
+        return _Edges(None, False, None, *_threshold_choice(n, units, unit_name, keep, num_edges, min_weight))
+    united = None if choice is not None else _tree_thresholds(n, units, unit_name, keep, num_edges, min_weight)
+    return _Edges(choice, tree, united, 0, 0.0)
 
 
-def _sparsified(matrices: torch.Tensor, units: int, edges: _Edges, out=None) -> torch.Tensor:
-    """The resident matrices sparsified as ``edges`` says, into ``out`` (which may be ``matrices``) or a new tensor."""
-    if edges.knn is None:
-        thr = None
-        if any(a is not None for a in edges[2:]):
-            thr = _thresholds(matrices, units, *edges[2:])
-        return _mst(matrices, thr, out)
-    tree = _mst(matrices, None) if edges.tree else None               # (before `out` may overwrite the matrices)
-    out = _knn(matrices, edges.knn, out)
-    return out if tree is None else torch.maximum(out, tree, out=out)
-
-
-def _check_matrix_out(out, matrices: torch.Tensor) -> None:
-    if out is None:
-        return
-    if not isinstance(out, torch.Tensor):
-        raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
-    if out.dtype != torch.float32:
-        raise TypeError(f"out must be float32, got {out.dtype}")
-    if out.shape != matrices.shape:
-        raise ValueError(f"out must be {tuple(matrices.shape)} as the matrices are, got {tuple(out.shape)}")
-    if out.device != matrices.device:
-        raise ValueError(f"out is on {out.device}, the matrices on {matrices.device}")
-    if not out.is_contiguous():
-        raise ValueError("out must be contiguous")
-
-
-def _knn(matrices: torch.Tensor, choice: tuple, out=None) -> torch.Tensor:
-    """cgnn_ingest_knn of resident matrices for ``_check_knn``'s pair, into ``out`` (which may be ``matrices``) or a new
-    tensor."""
+def _into(matrices: torch.Tensor, out, name: str, *args) -> torch.Tensor:
+    """The launch ``name(matrices, S, n, *args, out, out_bytes)`` of resident matrices, into ``out`` (which may be
+    ``matrices``) or a new tensor; ``_WORK`` among ``args`` is the workspace ``name`` asks for, which lives for the call."""
     S, n = int(matrices.shape[0]), int(matrices.shape[1])
     if out is None:
         out = torch.empty_like(matrices)
     if S:
-        _call(matrices.device, "cgnn_ingest_knn", matrices, S, n, *choice, *_lib.buf(out))
+        _call(matrices.device, name, matrices, S, n, *args, *_lib.buf(out),
+              workspace=(name, S, n) if any(a is _WORK for a in args) else None)
     return out
+
+
+def _knn(matrices: torch.Tensor, choice: tuple, out=None) -> torch.Tensor:
+    """cgnn_ingest_knn for ``_check_knn``'s pair."""
+    return _into(matrices, out, "cgnn_ingest_knn", *choice)
+
+
+def _mst(matrices: torch.Tensor, thr, out=None) -> torch.Tensor:
+    """cgnn_ingest_mst at the ``[S]`` thresholds ``thr`` (None: the tree alone); a slab per workgroup is its workspace."""
+    return _into(matrices, out, "cgnn_ingest_mst", thr, _WORK)
 
 
 def knn_sparsify(matrices: torch.Tensor, k: int, *, mode="union", out=None) -> torch.Tensor:
@@ -1542,21 +1559,9 @@ def knn_sparsify(matrices: torch.Tensor, k: int, *, mode="union", out=None) -> t
     no read-back, no atomics on global memory: every run and every grid gives the same bits."""
     S, n = _check_matrices(matrices)
     choice = _check_knn(n, k, mode)
-    _check_matrix_out(out, matrices)
+    _check_out(out, matrices, "matrices")
     _require_resident(matrices, *_MATRICES)
     return _knn(matrices, choice, out)
-
-
-def _mst(matrices: torch.Tensor, thr, out=None) -> torch.Tensor:
-    """cgnn_ingest_mst of resident matrices at the ``[S]`` thresholds ``thr`` (None: the tree alone), into ``out`` (which
-    may be ``matrices``) or a new tensor.  The workspace, a slab per workgroup of the launch, lives for the call."""
-    S, n = int(matrices.shape[0]), int(matrices.shape[1])
-    if out is None:
-        out = torch.empty_like(matrices)
-    if S:
-        _call(matrices.device, "cgnn_ingest_mst", matrices, S, n, thr, _WORK, *_lib.buf(out),
-              workspace=("cgnn_ingest_mst", S, n))
-    return out
 
 
 def mst_backbone(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, out=None) -> torch.Tensor:
@@ -1574,25 +1579,25 @@ def mst_backbone(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weigh
     after the selection of the thresholds; the one temporary is the workspace, a matrix-sized slab per workgroup of the
     launch and not per subject; no read-back, no atomics: every run and every grid gives the same bits."""
     S, n = _check_matrices(matrices)
-    if _at_most_one(keep, num_edges, min_weight):
-        _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    united = _tree_thresholds(n, S, "S", keep, num_edges, min_weight)
     _check_mst_size(n)
-    _check_matrix_out(out, matrices)
+    _check_out(out, matrices, "matrices")
     _require_resident(matrices, *_MATRICES)
-    return _sparsified(matrices, S, _Edges(None, True, keep, num_edges, min_weight), out)
+    return _Edges(None, True, united, 0, 0.0).sparsified(matrices, out)
 
 
-def _measure_ids(measures) -> list:
-    """A valid request, a non-empty tuple of distinct names, as one ``(family, id)`` per column."""
+def _measure_ids(measures, families=_FAMILIES, what="measures") -> list:
+    """A valid request, a non-empty tuple of distinct names of ``families``, as one ``(family, id)`` per column."""
+    names = tuple(name for fam in families for name in fam.names)
     if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
-        raise TypeError(f"measures must be a tuple of names from {_ALL_MEASURES}, got {measures!r}")
+        raise TypeError(f"measures must be a tuple of names from {names}, got {measures!r}")
     if len(measures) == 0:
-        raise ValueError(f"measures is empty: name at least one of {_ALL_MEASURES}")
+        raise ValueError(f"measures is empty: name at least one of {names}")
     ids = []
     for name in measures:
-        entry = next(((fam, fam.names.index(name)) for fam in _FAMILIES if name in fam.names), None)
+        entry = next(((fam, fam.names.index(name)) for fam in families if name in fam.names), None)
         if entry is None:
-            raise ValueError(f"unknown measure {name!r}: the measures are {_ALL_MEASURES}")
+            raise ValueError(f"unknown measure {name!r}: the {what} are {names}")
         if entry in ids:
             raise ValueError(f"measure {name!r} is named twice")
         ids.append(entry)
@@ -1668,48 +1673,41 @@ def _check_modules_argument(ids, modules, n: int):
     return _check_modules(modules, n)
 
 
-def _run_family(fam: _Family, matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x, dist=None,
-                modules=None, profile=None, profile_flags=0):
+def _run_family(fam: _Family, matrices: torch.Tensor, thr: torch.Tensor, ids, cols, x, head=(), mid=(), tail=None):
     """One call of ``fam``: measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as
-    they are; a family without ``cols`` fills ``x`` ``[S, n, len(ids)]`` in the order of ``ids``), and the distances into
-    ``dist`` ``[S, n, n]`` if given.  The workspace is what the family's query asks for: nothing for the paths and the
-    module measures, one slab per workgroup for the weighted paths.  ``modules`` is ``_check_modules``'s pair on the
-    matrices' device and ``profile`` ``[S, n, M]`` the network profile, for the family that takes them.  Returns ``x``."""
+    they are; a family without ``cols`` fills ``x`` ``[S, n, len(ids)]`` in the order of ``ids``).  The workspace is what
+    the family's query asks for.  What else the C signature of the family takes, as the header lists it: ``head``
+    between ``thr`` and the request (``_check_modules``'s pair on the matrices' device), ``mid`` between ``cols, ldx``
+    and the workspace (the damping), ``tail`` behind ``x`` (``dist``; ``profile`` and its flags; ``iterations``; each
+    pointer with its byte count), by default ``fam.tail``: none of them.  Returns ``x``."""
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
     if S == 0:
         return x
     num = len(ids)
     arr = (ctypes.c_int32 * num)(*ids)
-    args = [matrices, S, n, thr]
-    if fam.modules:
-        args += list(modules)
-    args += [arr, num]
-    if fam.cols:
-        args += [(ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1]
-    args += [_WORK, *_lib.buf(x)]
-    if fam.dist:
-        args += _lib.buf(dist)
-    if fam.modules:
-        args += [*_lib.buf(profile), profile_flags]
-    _call(matrices.device, fam.call, *args, workspace=(fam.call, S, n, arr, num))
+    where = ((ctypes.c_int32 * num)(*cols), x.shape[2] if x is not None else 1) if fam.cols else ()
+    _call(matrices.device, fam.call, matrices, S, n, thr, *head, arr, num, *where, *mid, _WORK, *_lib.buf(x),
+          *(fam.tail if tail is None else tail), workspace=(fam.call, S, n, arr, num))
     return x
 
 
 def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, modules=None) -> torch.Tensor:
     """``[S, n, len(ids)]``, one call per family that is named.  A request of classic names only is one packed
     cgnn_ingest_measures call, as before; the other families write their columns in place (cols / ldx).  ``modules`` is
-    ``_check_modules_argument``'s."""
+    ``_check_modules_argument``'s, on the host."""
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
     for fam in _FAMILIES:
         cols = [c for c, (f, _) in enumerate(ids) if f is fam]
         fam_ids = [ids[c][1] for c in cols]
         if not cols:
             continue
+        head = (modules[0].to(matrices.device), modules[1]) if fam.modules else ()
         if fam.cols or len(cols) == len(ids):
-            _run_family(fam, matrices, S, n, thr, fam_ids, cols, x, modules=modules)
+            _run_family(fam, matrices, thr, fam_ids, cols, x, head)
         else:
             # cgnn_ingest_measures writes a packed block only, so in a mixed request its columns are copied in.  Removing
             # this temporary takes a cols / ldx entry point for the classic family: another change (DESIGN.md 7).
-            x[:, :, cols] = _run_family(fam, matrices, S, n, thr, fam_ids, cols,
+            x[:, :, cols] = _run_family(fam, matrices, thr, fam_ids, cols,
                                         torch.empty(S, n, len(cols), dtype=torch.float32, device=matrices.device))
     return x
 
@@ -1726,17 +1724,12 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``; one partition for the cohort, checked on the host.
     ``backbone`` is ``from_matrices``'s: the measures of the graph united with the spanning tree."""
     S, n = _check_matrices(matrices)
-    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
     partition = _check_modules_argument(ids, modules, n)
-    _require_resident(matrices, *_MATRICES)
-    if partition is not None:
-        partition = (partition[0].to(matrices.device), partition[1])
-    if edges is not None:
-        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
-    return _measures(matrices, S, n, _thresholds(matrices, S, keep, num_edges, min_weight), ids, partition)
+    matrices, thr = edges.apply(matrices)
+    return _measures(matrices, S, n, thr, ids, partition)
 
 
 def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None, min_weight=None, knn=None,
@@ -1751,35 +1744,14 @@ def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None
     cohort on the fused GCN path.  ``n <= MODULE_MAX_NODES``.  ``backbone`` is ``from_matrices``'s (the profile of the
     united graph; it and ``knn=`` cost the cohort-sized temporaries named there)."""
     S, n = _check_matrices(matrices)
-    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _check_size(_MODULES, n, "module_profile takes")
     labels, M = _check_modules(modules, n)
-    _require_resident(matrices, *_MATRICES)
-    if edges is not None:
-        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
-    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
+    matrices, thr = edges.apply(matrices)
     profile = torch.empty(S, n, M, dtype=torch.float32, device=matrices.device)
     flags = (_lib.MODULE_PROFILE_BINARY if binary else 0) | (_lib.MODULE_PROFILE_NORMALIZE if normalize else 0)
-    _run_family(_MODULES, matrices, S, n, thr, [], [], None, modules=(labels.to(matrices.device), M), profile=profile,
-                profile_flags=flags)
+    _run_family(_MODULES, matrices, thr, [], [], None, (labels.to(matrices.device), M), tail=_lib.buf(profile) + (flags,))
     return profile
-
-
-def _centrality_ids(measures) -> list:
-    """A valid request of ``centrality_measures``, a non-empty tuple of distinct names, as their ids."""
-    if isinstance(measures, str) or not isinstance(measures, (tuple, list)):
-        raise TypeError(f"measures must be a tuple of names from {CENTRALITY_MEASURES}, got {measures!r}")
-    if len(measures) == 0:
-        raise ValueError(f"measures is empty: name at least one of {CENTRALITY_MEASURES}")
-    ids = []
-    for name in measures:
-        if name not in CENTRALITY_MEASURES:
-            raise ValueError(f"unknown measure {name!r}: the centrality measures are {CENTRALITY_MEASURES}")
-        if CENTRALITY_MEASURES.index(name) in ids:
-            raise ValueError(f"measure {name!r} is named twice")
-        ids.append(CENTRALITY_MEASURES.index(name))
-    return ids
 
 
 def _check_damping(damping) -> float:
@@ -1797,19 +1769,6 @@ def pagerank_max_steps(damping) -> int:
     before it in exact arithmetic."""
     d = _check_damping(damping)
     return int(math.ceil(43.0 * math.log(2.0) / -math.log(d))) + 2 if d > 0.0 else 2
-
-
-def _pagerank(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids, cols, x: torch.Tensor, damping: float,
-              iterations=None) -> torch.Tensor:
-    """cgnn_ingest_pagerank: measure ``ids[m]`` into column ``cols[m]`` of ``x`` ``[S, n, F]`` (the other columns stay as
-    they are), and the step counts into ``iterations`` ``[S]`` int32 if given.  Returns ``x``."""
-    if S:
-        num = len(ids)
-        arr = (ctypes.c_int32 * num)(*ids)
-        _call(matrices.device, "cgnn_ingest_pagerank", matrices, S, n, thr, arr, num, (ctypes.c_int32 * num)(*cols),
-              x.shape[2], damping, _WORK, *_lib.buf(x), *_lib.buf(iterations),
-              workspace=("cgnn_ingest_pagerank", S, n, arr, num))
-    return x
 
 
 def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
@@ -1830,19 +1789,13 @@ def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, mi
     ``node_measures(measures=)``: that table of four families and seventeen names is pinned.  The C entry point writes
     its columns inside a wider ``x`` (cols / ldx) so that a later change can merge the names into ``measures=``."""
     S, n = _check_matrices(matrices)
-    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
-    ids = _centrality_ids(measures)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    ids = [i for _, i in _measure_ids(measures, (_CENTRALITY,), _CENTRALITY.what)]
     damping = _check_damping(damping)
-    if n > PAGERANK_MAX_NODES:
-        raise ValueError(f"centrality_measures takes n <= {PAGERANK_MAX_NODES} nodes (a kept entry's column is stored in "
-                         f"16 bits), got n = {n}")
-    _require_resident(matrices, *_MATRICES)
-    if edges is not None:
-        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
-    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
+    _check_size(_CENTRALITY, n, "centrality_measures takes")
+    matrices, thr = edges.apply(matrices)
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
-    return _pagerank(matrices, S, n, thr, ids, list(range(len(ids))), x, damping)
+    return _run_family(_CENTRALITY, matrices, thr, ids, list(range(len(ids))), x, mid=(damping,))
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
@@ -1855,27 +1808,21 @@ def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weigh
     the three: the distances on the k-NN graph, as in ``from_matrices``.  ``backbone`` is ``from_matrices``'s: on a
     subject whose positive entries form one component every distance is then finite."""
     S, n = _check_matrices(matrices)
-    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    _, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _check_size(_WEIGHTED, n, "path_lengths takes")
-    _require_resident(matrices, *_MATRICES)
-    if edges is not None:
-        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
-    thr = _thresholds(matrices, S, keep, num_edges, min_weight)
+    matrices, thr = edges.apply(matrices)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
-    _run_family(_WEIGHTED, matrices, S, n, thr, [], [], None, dist)
+    _run_family(_WEIGHTED, matrices, thr, [], [], None, tail=_lib.buf(dist))
     return dist
 
 
 def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> torch.Tensor:
     """Per subject, the off-diagonal entry of descending rank ``k`` (``[S]`` float32 on the matrices'
     device): the threshold that ``from_matrices`` applies for the same ``keep`` / ``num_edges``."""
-    S, n = _check_matrices(matrices)
+    _, n = _check_matrices(matrices)
     k = _rank(n, keep, num_edges)
     _require_resident(matrices, *_MATRICES)
-    thr = torch.empty(S, dtype=torch.float32, device=matrices.device)
-    _call(matrices.device, "cgnn_ingest_select", matrices, S, n, k, *_lib.buf(thr))
-    return thr
+    return _thresholds(matrices, k, None)
 
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
@@ -1906,24 +1853,18 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     measure are those of the united graph, which has at most ``2 (n - 1)`` more entries than the choice alone.  Any
     other value raises a ``ValueError`` naming ``BACKBONES``."""
     S, n = _check_matrices(matrices)
-    edges, keep, num_edges, min_weight = _edge_choice(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
-    k, min_weight = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
     _check_labels_and_features(labels, S, node_features, "S", S, n)
     if node_features is not None and node_features.device != matrices.device:
         raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
     partition = _check_modules_argument(ids, modules, n)
-    _require_resident(matrices, *_MATRICES)
+    matrices, thr = edges.apply(matrices, select=False)
     dev = matrices.device
-    if partition is not None:
-        partition = (partition[0].to(dev), partition[1])
-    if edges is not None:
-        matrices = _sparsified(matrices, S, edges)    # the cohort-sized temporary (two for knn= with a backbone)
-    if min_weight is None:
-        thr = torch.empty(S, dtype=torch.float32, device=dev)     # cgnn_ingest_count selects them: no launch of its own
-    else:
-        thr = _thresholds(matrices, S, None, None, min_weight)
+    select = thr is None                              # cgnn_ingest_count selects them: no launch of its own
+    if select:
+        thr = torch.empty(S, dtype=torch.float32, device=dev)
     row_count = torch.empty(S * n, dtype=torch.int32, device=dev)
     strength = None                                   # the default feature, unless x comes from elsewhere
     if node_features is None and ids is None:
@@ -1932,7 +1873,7 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     row_off = torch.zeros(S * n + 1, dtype=torch.long, device=dev)
     with _lib.device_guard(dev):
         sp = _lib.stream_ptr(dev)
-        _lib.call("cgnn_ingest_count", matrices, S, n, int(min_weight is None), k, *_lib.buf(thr), *_lib.buf(row_count),
+        _lib.call("cgnn_ingest_count", matrices, S, n, int(select), edges.k, *_lib.buf(thr), *_lib.buf(row_count),
                   *_lib.buf(strength), stream=sp)
         torch.cumsum(row_count, 0, dtype=torch.long, out=row_off[1:])
         edge_ptr_dev = row_off[::n].contiguous()          # [S + 1]: every subject's first row

@@ -28,7 +28,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from connectome_gnn_amd import ingest  # noqa: E402
+from connectome_gnn_amd import _lib, ingest  # noqa: E402
 from tools.ingest_time import cohort, spread, timed  # noqa: E402
 
 NAMES = ingest.CENTRALITY_MEASURES
@@ -57,7 +57,7 @@ def steps_taken(m, thr, d, ident):
     S, n, _ = m.shape
     it = torch.empty(S, dtype=torch.int32, device=m.device)
     x = torch.empty(S, n, 1, device=m.device)
-    ingest._pagerank(m, S, n, thr, [ident], [0], x, d, it)
+    ingest._run_family(ingest._CENTRALITY, m, thr, [ident], [0], x, mid=(d,), tail=_lib.buf(it))
     it = it.cpu()
     return {"median": int(it.median()), "max": int(it.max())}
 
