@@ -328,6 +328,17 @@ PAGERANK_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_group.h declares (cgnn.h includes it), in the same form, the ids of the statistics
+# and the number of consecutive units whose fp64 partial sum is formed first (CGNN_GROUP_SLICE).
+GROUP_MEAN, GROUP_FISHER_MEAN, GROUP_CONSISTENCY = 0, 1, 2
+GROUP_SLICE = 64
+GROUP_PROTOTYPES = {
+    "cgnn_ingest_group_workspace_bytes": (I64, [I64, I32]),
+    "cgnn_ingest_group": (c_int, [P, I64, I32, I32, P, P, P, I64, P, I64, P]),
+    "cgnn_ingest_group_mask": (c_int, [P, I64, I32, P, P, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -348,7 +359,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
                               **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
-                              **PAGERANK_PROTOTYPES}.items():
+                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

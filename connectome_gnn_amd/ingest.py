@@ -497,6 +497,41 @@ the first step whose L1 change is at most ``(1 - d) 2^-42``, which leaves ``2^-4
 entries is exactly ``1 / n``; a kept ``+inf`` makes that subject's ``weighted_pagerank`` NaN and nothing else.  One launch (csrc/pagerank.hip), a workgroup per subject with its kept entries
 compacted into LDS where they fit (``n <= PAGERANK_MAX_NODES = 1024``); no workspace, no atomics, no read-back, the same
 bits on every run, for every grid and for every subset and order of the two names.
+
+Group-consensus edges: every choice above is made inside one subject's matrix, so every subject gets a
+graph of its own and the differences are mostly noise.  ``group=`` of ``from_matrices``, ``node_measures``,
+``module_profile``, ``path_lengths``, ``centrality_measures`` and ``from_timeseries`` changes whose matrix the choice is
+made on: the whole edge choice (one of the three thresholds; or ``knn=`` / ``knn_mode=``; with or without
+``backbone="mst"``) is applied to a group matrix ``G`` ``[n, n]`` as a cohort of one unit, and every subject is masked to
+that edge set.  ``group_matrix(matrices, statistic, among=)`` gives ``G`` (csrc/group.hip), ``statistic`` one of
+``GROUP_STATISTICS``; ``N`` is the number of included units, those with ``among[s]`` true (all, without ``among``).
+
+* The sum, per entry ``(i, j)``, in fp64, in an order that depends on neither the grid nor the run: the units are cut
+  into slices of 64 consecutive units (``CGNN_GROUP_SLICE``); a slice's partial starts at ``0.0`` and adds its included
+  units in ascending order; the partials are folded in ascending slice order from ``0.0``.
+* ``"mean"``: ``sum_s A_sij / N``.  ``"fisher_mean"``: ``tanh(sum_s atanh(A_sij) / N)``, fp64 ``atanh`` and ``tanh``.
+  ``"consistency"`` (van den Heuvel & Sporns): ``count_s[i != j and A_sij > t_s and A_sij > 0] / N``, the edge test above
+  at every unit's own threshold ``t_s`` -- exactly one of ``keep=`` / ``num_edges=`` / ``min_weight=`` (``[S]`` as a
+  tensor), which the other two statistics refuse; the count is an exact integer.
+* One fp64 division and one rounding to fp32, and no special case: ``N == 0`` gives NaN everywhere; a NaN in an included
+  unit makes that entry NaN; ``+inf`` and ``-inf`` in the same entry give NaN; ``|r| == 1`` goes through ``atanh`` as
+  ``+-inf``; the diagonal is reduced like any entry, except that ``"consistency"`` leaves it at 0; a bit-symmetric cohort
+  gives a bit-symmetric ``G``.
+* A unit left out by ``among`` is never read: NaN, Inf or ``1e30`` there change no bit (the rule ``sample_mask=`` follows
+  for frames), and an all-True ``among`` gives the bits of the call without it.
+* The group edge set: ``(G', t) = `` the edge choice applied to ``G[None]``; ``E = {(i, j): i != j, G'_ij > t and
+  G'_ij > 0}``; a NaN group entry is never an edge.
+* The mask, ``group_sparsify(matrices, group, <the choice>, out=)``: ``out_sij`` is the bits of ``A_sij`` if ``(i, j)`` is
+  in ``E`` and ``A_sij > 0``, else ``+0.0`` (the diagonal, every NaN and ``-0.0`` too); ``out=matrices`` gives the same
+  bits.  ``group`` is ``"mean"``, ``"fisher_mean"`` or a float32 ``[n, n]`` tensor on the device; ``"consistency"`` as a
+  string is refused, it needs a threshold choice of its own.
+
+Each call with ``group=`` is, bit for bit, the same call on ``group_sparsify(matrices, group, <the choice>)`` with
+``min_weight=0.0``; the caller's matrices are left alone and the masked cohort is the one cohort-sized temporary
+(``from_timeseries`` masks its connectivity temporary in place; its units are the windows).  A subject whose entry at a
+group edge is not positive drops that edge, so subjects' edge sets are subsets of ``E``.  The statistic streams the cohort
+once into a workspace ``1 / 32`` its size and folds it (two launches), the mask copies it once (one launch); no atomics, no
+read-back, the same bits on every run and for every grid.  Without ``group=`` every call launches what it launched before.
 """
 from __future__ import annotations
 
@@ -543,6 +578,7 @@ _SERIES_SPECTRAL = SERIES_FEATURES[2:]                # the names that need t_r 
 CENTRALITY_MEASURES = ("pagerank", "weighted_pagerank")   # ids: include/cgnn_pagerank.h
 PAGERANK_MAX_NODES = 1024                             # CGNN_PAGERANK_MAX_NODES: a kept entry's column is stored in 16 bits
 PAGERANK_MAX_DAMPING = _lib.PAGERANK_MAX_DAMPING      # CGNN_PAGERANK_MAX_DAMPING: the step bound grows as 1 / (1 - d)
+GROUP_STATISTICS = ("mean", "fisher_mean", "consistency")   # ids: include/cgnn_group.h
 
 
 class _Family(NamedTuple):
@@ -1397,7 +1433,7 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
                     kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
-                    knn_mode="union", modules=None, backbone=None) -> RaggedPackedDataset:
+                    knn_mode="union", modules=None, backbone=None, group=None) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
@@ -1405,7 +1441,8 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     without edges).  The one read-back is ``from_matrices``'s.  ``knn=k`` (with ``knn_mode``) instead of the three
     thresholds: the k-NN graph of every unit's matrix, as in ``from_matrices``; the connectivity temporary is sparsified
     in place, which costs no extra memory.  ``modules`` is ``from_matrices``'s.  ``backbone`` is ``from_matrices``'s: the
-    connectivity temporary becomes the united graph in place (with ``knn=`` the tree is one more temporary)."""
+    connectivity temporary becomes the united graph in place (with ``knn=`` the tree is one more temporary).  ``group``
+    is ``from_matrices``'s, its units the windows: the connectivity temporary is masked to the group's edges in place."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
@@ -1413,7 +1450,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
     _check_modules_argument(ids, modules, n)
-    edges = _edge_plan(n, U, "U", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, U, "U", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
@@ -1478,23 +1515,91 @@ def _tree_thresholds(n: int, units: int, unit_name: str, keep, num_edges, min_we
     return _threshold_choice(n, units, unit_name, keep, num_edges, min_weight) if given else None
 
 
+def _check_statistic(statistic) -> int:
+    if not isinstance(statistic, str) or statistic not in GROUP_STATISTICS:
+        raise ValueError(f"unknown statistic {statistic!r}: the statistics are GROUP_STATISTICS = {GROUP_STATISTICS}")
+    return GROUP_STATISTICS.index(statistic)          # ids: include/cgnn_group.h
+
+
+def _check_group(n: int, group):
+    """A valid ``group=`` for matrices of ``n`` nodes: the id of ``"mean"`` / ``"fisher_mean"``, or the float32
+    contiguous ``[n, n]`` tensor it is (whether it lies on the matrices' device is ``_group_of``'s check)."""
+    if isinstance(group, torch.Tensor):
+        if group.dtype != torch.float32:
+            raise TypeError(f"a group tensor must be float32, got {group.dtype}")
+        if tuple(group.shape) != (n, n):
+            raise ValueError(f"a group tensor must be [n, n] = [{n}, {n}], got {tuple(group.shape)}")
+        if not group.is_contiguous():
+            raise ValueError("a group tensor must be contiguous")
+        return group
+    if not isinstance(group, str):
+        raise TypeError(f"group must be one of {GROUP_STATISTICS[:2]} or a float32 tensor [n, n], got "
+                        f"{type(group).__name__}")
+    if group == "consistency":
+        raise ValueError('group="consistency" needs a threshold choice of its own, every unit\'s: pass the tensor '
+                         'group_matrix(matrices, "consistency", keep=...) as group=')
+    return _check_statistic(group)
+
+
+def _check_among(among, S: int, device):
+    """A valid ``among=`` for ``S`` units on ``device``: None, or bool ``[S]``."""
+    if among is None:
+        return None
+    if not isinstance(among, torch.Tensor):
+        raise TypeError(f"among must be a torch.Tensor or None, got {type(among).__name__}")
+    if among.dtype != torch.bool:
+        raise TypeError(f"among must be bool (True: the unit enters the statistic), got {among.dtype}")
+    if tuple(among.shape) != (S,):
+        raise ValueError(f"among must be [S] = [{S}], one flag per unit, got {tuple(among.shape)}")
+    if among.device != device:
+        raise ValueError(f"among is on {among.device}, the matrices on {device}")
+    if not among.is_contiguous():
+        raise ValueError("among must be contiguous")
+    return among
+
+
+def _group(matrices: torch.Tensor, statistic: int, thr=None, among=None) -> torch.Tensor:
+    """cgnn_ingest_group of resident matrices: ``[n, n]``; ``thr`` is ``[S]`` exactly for the consistency."""
+    S, n = int(matrices.shape[0]), int(matrices.shape[1])
+    out = torch.empty(n, n, dtype=torch.float32, device=matrices.device)
+    _call(matrices.device, "cgnn_ingest_group", matrices, S, n, statistic, thr, among, _WORK, *_lib.buf(out),
+          workspace=("cgnn_ingest_group", S, n))
+    return out
+
+
+def _group_of(matrices: torch.Tensor, group) -> torch.Tensor:
+    """The group matrix ``[n, n]`` of ``_check_group``'s value for these resident matrices."""
+    if not isinstance(group, torch.Tensor):
+        return _group(matrices, group)
+    if group.device != matrices.device:
+        raise ValueError(f"the group tensor is on {group.device}, the matrices on {matrices.device}")
+    return group
+
+
 class _Edges(NamedTuple):
     """The valid edge choice of a call.  With ``knn`` (``_check_knn``'s pair) or ``tree`` the matrices are sparsified
     first: the k-NN graph, united with the tree if ``tree``; without ``knn`` the tree united with the thresholds of
     ``united`` (``_threshold_choice``'s pair; None: the tree alone).  The call then goes on at ``_threshold_choice``'s
-    pair ``(k, min_weight)``, which on sparsified matrices is ``min_weight=0.0``."""
+    pair ``(k, min_weight)``, which on sparsified matrices is ``min_weight=0.0``.  With ``group`` -- ``_check_group``'s
+    value and the ``_Edges`` of the whole choice for a cohort of one unit -- that choice is made on the group matrix and
+    the matrices are sparsified to its edge set; the other fields then say ``min_weight=0.0`` and nothing else."""
     knn: Optional[tuple]
     tree: bool
     united: Optional[tuple]
     k: int
     min_weight: object
+    group: Optional[tuple] = None
 
     @property
     def sparsify(self) -> bool:
-        return self.knn is not None or self.tree
+        return self.knn is not None or self.tree or self.group is not None
 
     def sparsified(self, matrices: torch.Tensor, out=None) -> torch.Tensor:
         """The resident matrices sparsified, into ``out`` (which may be ``matrices``) or a new tensor."""
+        if self.group is not None:
+            group, plan = self.group
+            chosen, thr = plan.apply(_group_of(matrices, group)[None])     # (before `out` may overwrite the matrices)
+            return _into(matrices, out, "cgnn_ingest_group_mask", chosen, thr)
         if self.knn is None:
             return _mst(matrices, None if self.united is None else _thresholds(matrices, *self.united), out)
         tree = _mst(matrices, None) if self.tree else None            # (before `out` may overwrite the matrices)
@@ -1514,9 +1619,14 @@ class _Edges(NamedTuple):
         return matrices, _thresholds(matrices, self.k, self.min_weight)
 
 
-def _edge_plan(n: int, units: int, unit_name: str, knn, knn_mode, backbone, keep, num_edges, min_weight) -> _Edges:
+def _edge_plan(n: int, units: int, unit_name: str, knn, knn_mode, backbone, keep, num_edges, min_weight,
+               group=None) -> _Edges:
     """The ``_Edges`` of a call's whole edge choice: exactly one of the three thresholds; or ``knn=`` with none of
-    them; or ``backbone=`` with at most one of them, or with ``knn=``."""
+    them; or ``backbone=`` with at most one of them, or with ``knn=``.  With ``group=`` the same choice, for the group
+    matrix as a cohort of one unit."""
+    if group is not None:
+        plan = _edge_plan(n, 1, "the group matrix", knn, knn_mode, backbone, keep, num_edges, min_weight)
+        return _Edges(None, False, None, 0, 0.0, (_check_group(n, group), plan))
     choice = _knn_choice(n, knn, knn_mode, keep, num_edges, min_weight)
     tree = _check_backbone(n, backbone)
     if choice is None and not tree:
@@ -1584,6 +1694,54 @@ def mst_backbone(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weigh
     _check_out(out, matrices, "matrices")
     _require_resident(matrices, *_MATRICES)
     return _Edges(None, True, united, 0, 0.0).sparsified(matrices, out)
+
+
+def group_matrix(matrices: torch.Tensor, statistic="mean", *, among=None, keep=None, num_edges=None,
+                 min_weight=None) -> torch.Tensor:
+    """The group-level matrix of a cohort: float32 ``[n, n]`` on ``matrices.device`` (module docstring), what ``group=``
+    takes as a tensor.  ``statistic`` is one of ``GROUP_STATISTICS``: ``"mean"``, the entrywise mean over the units;
+    ``"fisher_mean"``, ``tanh`` of the mean of ``atanh``; ``"consistency"``, the share of units in which an entry
+    survives the unit's own threshold -- exactly one of ``keep`` / ``num_edges`` / ``min_weight`` (a tensor is ``[S]``),
+    chosen per unit as ``from_matrices`` would; the other two statistics refuse the three.  ``among`` (``torch.bool``
+    ``[S]`` on the device, True: the unit enters the statistic) lets the training split alone define the topology: a
+    unit left out is never read, and an all-True ``among`` gives the bits of the call without it.  Sums are fp64 in a
+    fixed order, one division, one rounding; no units at all give NaN everywhere.  Two launches on resident data
+    (csrc/group.hip; the consistency selects its thresholds first, which reads the cohort once more); the one temporary
+    is a workspace ``1 / 32`` of the cohort; no read-back, no atomics: every run and every grid gives the same bits."""
+    S, n = _check_matrices(matrices)
+    stat = _check_statistic(statistic)
+    choice = None
+    if statistic == "consistency":
+        choice = _threshold_choice(n, S, "S", keep, num_edges, min_weight)
+    elif any(a is not None for a in (keep, num_edges, min_weight)):
+        raise ValueError(f'keep=, num_edges= and min_weight= are every unit\'s own threshold under "consistency": '
+                         f"statistic={statistic!r} takes none of them")
+    among = _check_among(among, S, matrices.device)
+    _require_resident(matrices, *_MATRICES)
+    return _group(matrices, stat, None if choice is None else _thresholds(matrices, *choice), among)
+
+
+def group_sparsify(matrices: torch.Tensor, group="mean", *, keep=None, num_edges=None, min_weight=None, knn=None,
+                   knn_mode="union", backbone=None, out=None) -> torch.Tensor:
+    """Every subject masked to one edge set, chosen on a group matrix: float32 ``[S, n, n]`` on ``matrices.device`` with
+    the bits of ``matrices`` where an entry is a group edge and positive in the subject, and ``+0.0`` elsewhere (module
+    docstring), so that every call of this module at ``min_weight=0.0`` sees the common topology with the subject's own
+    weights.  ``group`` is ``"mean"`` or ``"fisher_mean"`` (``group_matrix`` of these matrices), or a float32 contiguous
+    ``[n, n]`` tensor on the same device: the way in for ``"consistency"``, which needs a threshold choice of its own and
+    is refused as a string, for an ``among=`` split and for a group matrix from elsewhere.  The edge choice -- exactly
+    one of ``keep`` / ``num_edges`` / ``min_weight``, or ``knn=`` / ``knn_mode=``, with or without ``backbone="mst"``, as
+    in ``from_matrices`` -- is made on the group matrix as a cohort of one unit (a ``min_weight`` tensor is ``[1]``).
+    ``out`` is where the result goes: a float32 contiguous tensor of the same shape on the same device, which is
+    returned; it may be ``matrices`` itself (in place, the same bits as out of place; any other overlap is refused).  The
+    statistic's two launches, the choice's, and one that copies the cohort under the mask (csrc/group.hip); the
+    temporaries are group-sized; no read-back, no atomics: every run and every grid gives the same bits."""
+    S, n = _check_matrices(matrices)
+    if group is None:
+        raise TypeError(f"group must be one of {GROUP_STATISTICS[:2]} or a float32 tensor [n, n], got None")
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
+    _check_out(out, matrices, "matrices")
+    _require_resident(matrices, *_MATRICES)
+    return edges.sparsified(matrices, out)
 
 
 def _measure_ids(measures, families=_FAMILIES, what="measures") -> list:
@@ -1713,7 +1871,8 @@ def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: li
 
 
 def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
-                  measures=MEASURES, knn=None, knn_mode="union", modules=None, backbone=None) -> torch.Tensor:
+                  measures=MEASURES, knn=None, knn_mode="union", modules=None, backbone=None,
+                  group=None) -> torch.Tensor:
     """Graph measures of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
     ``matrices.device``, one column per name in ``measures``: names from ``MEASURES``, ``PATH_MEASURES``,
     ``WEIGHTED_PATH_MEASURES`` and ``MODULE_MEASURES`` in any order and mix (module docstring).  The thresholds are
@@ -1722,9 +1881,10 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     ``from_matrices``.  ``modules`` is the partition of the ROIs that the names of ``MODULE_MEASURES`` need, and is
     given exactly when one of them is named: a sequence, a numpy array or a CPU integer tensor of ``n`` labels
     ``0 .. M - 1``, each used at least once, ``M <= MODULE_MAX``; one partition for the cohort, checked on the host.
-    ``backbone`` is ``from_matrices``'s: the measures of the graph united with the spanning tree."""
+    ``backbone`` is ``from_matrices``'s: the measures of the graph united with the spanning tree.  ``group`` is
+    ``from_matrices``'s: the measures of every subject on the group's edge set."""
     S, n = _check_matrices(matrices)
-    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     ids = _measure_ids(measures)
     _check_path_size(ids, n)
     partition = _check_modules_argument(ids, modules, n)
@@ -1733,7 +1893,7 @@ def node_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
 
 
 def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None, min_weight=None, knn=None,
-                   knn_mode="union", binary=False, normalize=False, backbone=None) -> torch.Tensor:
+                   knn_mode="union", binary=False, normalize=False, backbone=None, group=None) -> torch.Tensor:
     """The network profile of every node, the node-to-network feature: float32 ``[S, n, M]`` on ``matrices.device`` with
     ``s_i(m)``, node ``i``'s kept strength into module ``m`` (module docstring), at the thresholds ``from_matrices``
     applies for the same ``keep`` / ``num_edges`` / ``min_weight`` (or on the k-NN graph of ``knn=`` / ``knn_mode=``).
@@ -1742,9 +1902,9 @@ def module_profile(matrices: torch.Tensor, modules, *, keep=None, num_edges=None
     launch (cgnn_ingest_modules without measures); no cohort-sized temporary, no read-back.  With a partition of
     ``M <= 8`` modules (the 7 Yeo networks) the result, passed as ``from_matrices(..., node_features=)``, keeps a
     cohort on the fused GCN path.  ``n <= MODULE_MAX_NODES``.  ``backbone`` is ``from_matrices``'s (the profile of the
-    united graph; it and ``knn=`` cost the cohort-sized temporaries named there)."""
+    united graph; it and ``knn=`` cost the cohort-sized temporaries named there).  ``group`` is ``from_matrices``'s."""
     S, n = _check_matrices(matrices)
-    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     _check_size(_MODULES, n, "module_profile takes")
     labels, M = _check_modules(modules, n)
     matrices, thr = edges.apply(matrices)
@@ -1772,7 +1932,8 @@ def pagerank_max_steps(damping) -> int:
 
 
 def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
-                        knn_mode="union", backbone=None, measures=CENTRALITY_MEASURES, damping=0.85) -> torch.Tensor:
+                        knn_mode="union", backbone=None, measures=CENTRALITY_MEASURES, damping=0.85,
+                        group=None) -> torch.Tensor:
     """PageRank centrality of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
     ``matrices.device``, one column per name in ``measures``, names from ``CENTRALITY_MEASURES`` in any order (module
     docstring): ``pagerank`` walks the kept entries with equal weights, ``weighted_pagerank`` with the entries' values.
@@ -1783,13 +1944,14 @@ def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, mi
     ``(i, j)`` is an edge ``j -> i`` and a node without out-strength spreads its mass uniformly.  One launch on resident
     data (csrc/pagerank.hip); no workspace, no read-back, no atomics: every run, every grid and every subset and order of
     the names gives the same bits.  ``n <= PAGERANK_MAX_NODES``.  The result is what ``node_features=`` of
-    ``from_matrices`` / ``from_timeseries`` takes; its two columns keep a cohort on the fused GCN path.
+    ``from_matrices`` / ``from_timeseries`` takes; its two columns keep a cohort on the fused GCN path.  ``group`` is
+    ``from_matrices``'s.
 
     This is a call of its own beside ``module_profile`` and ``series_features`` and the names are not among those of
     ``node_measures(measures=)``: that table of four families and seventeen names is pinned.  The C entry point writes
     its columns inside a wider ``x`` (cols / ldx) so that a later change can merge the names into ``measures=``."""
     S, n = _check_matrices(matrices)
-    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     ids = [i for _, i in _measure_ids(measures, (_CENTRALITY,), _CENTRALITY.what)]
     damping = _check_damping(damping)
     _check_size(_CENTRALITY, n, "centrality_measures takes")
@@ -1799,16 +1961,16 @@ def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, mi
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
-                 knn_mode="union", backbone=None) -> torch.Tensor:
+                 knn_mode="union", backbone=None, group=None) -> torch.Tensor:
     """The weighted distances ``dw`` of the module docstring: float32 ``[S, n, n]`` on ``matrices.device``, ``+inf``
     where ``j`` is not reached from ``i`` and a zero diagonal, at the thresholds ``from_matrices`` applies for the same
     ``keep`` / ``num_edges`` / ``min_weight``.  This is the one call of this module whose output is cohort-sized: as
     large as ``matrices`` itself.  The measures of ``WEIGHTED_PATH_MEASURES`` are formed from the same distances without
     it (``node_measures``).  ``n <= WEIGHTED_PATH_MAX_NODES``.  No read-back.  ``knn=k`` (with ``knn_mode``) instead of
     the three: the distances on the k-NN graph, as in ``from_matrices``.  ``backbone`` is ``from_matrices``'s: on a
-    subject whose positive entries form one component every distance is then finite."""
+    subject whose positive entries form one component every distance is then finite.  ``group`` is ``from_matrices``'s."""
     S, n = _check_matrices(matrices)
-    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     _check_size(_WEIGHTED, n, "path_lengths takes")
     matrices, thr = edges.apply(matrices)
     dist = torch.empty(S, n, n, dtype=torch.float32, device=matrices.device)
@@ -1827,7 +1989,7 @@ def select_thresholds(matrices: torch.Tensor, *, keep=None, num_edges=None) -> t
 
 def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                   node_features=None, measures=None, knn=None, knn_mode="union",
-                  modules=None, backbone=None) -> RaggedPackedDataset:
+                  modules=None, backbone=None, group=None) -> RaggedPackedDataset:
     """The thresholded cohort as a ``RaggedPackedDataset`` on ``matrices.device`` (module docstring).  With
     ``measures`` (a tuple of names from ``MEASURES``, ``PATH_MEASURES``, ``WEIGHTED_PATH_MEASURES`` and
     ``MODULE_MEASURES``, or ``True`` for all of ``MEASURES``) ``x`` is ``node_measures`` at the thresholds of this call,
@@ -1851,9 +2013,17 @@ def from_matrices(matrices: torch.Tensor, labels: torch.Tensor, *, keep=None, nu
     mst_backbone(matrices))`` with ``min_weight=0.0``, which needs two cohort-sized temporaries for the length of the
     call, the k-NN graph and the tree (the other choices need one, the united graph).  The strength feature and every
     measure are those of the united graph, which has at most ``2 (n - 1)`` more entries than the choice alone.  Any
-    other value raises a ``ValueError`` naming ``BACKBONES``."""
+    other value raises a ``ValueError`` naming ``BACKBONES``.
+
+    ``group=`` changes whose matrix that whole choice is made on: ``"mean"``, ``"fisher_mean"`` or a float32 ``[n, n]``
+    tensor on the matrices' device (``group_matrix``'s, which is the way in for ``"consistency"`` and for an ``among=``
+    split).  The choice above, thresholds, ``knn=`` and ``backbone=`` alike, is applied to the group matrix as a cohort
+    of one unit (a ``min_weight`` tensor is ``[1]``) and every subject carries that edge set with its own weights: the
+    call is, bit for bit, this call on ``group_sparsify(matrices, group, <the choice>)`` with ``min_weight=0.0``.  A
+    subject whose entry at a group edge is not positive drops that edge.  The masked cohort is the one cohort-sized
+    temporary."""
     S, n = _check_matrices(matrices)
-    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     _check_labels_and_features(labels, S, node_features, "S", S, n)
     if node_features is not None and node_features.device != matrices.device:
         raise ValueError(f"node_features are on {node_features.device}, the matrices on {matrices.device}")

@@ -1366,5 +1366,6 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 #include "cgnn_mst.h"
 #include "cgnn_activity.h"
 #include "cgnn_pagerank.h"
+#include "cgnn_group.h"
 
 #endif /* CGNN_H */
