@@ -339,6 +339,13 @@ GROUP_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_core.h declares (cgnn.h includes it), in the same form.
+CORE_PROTOTYPES = {
+    "cgnn_ingest_cores_workspace_bytes": (I64, [I64, I32, P, I32]),
+    "cgnn_ingest_cores": (c_int, [P, I64, I32, P, P, I32, P, I32, P, I64, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -359,7 +366,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
                               **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
-                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES}.items():
+                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES, **CORE_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -1,5 +1,5 @@
 // measure_request.h -- the host side that the cohort entry points share (measures.hip, paths.hip, wpaths.hip,
-// modules.hip, pagerank.hip, knn.hip, mst.hip): the columns a kernel writes, the check of a
+// modules.hip, pagerank.hip, core.hip, knn.hip, mst.hip): the columns a kernel writes, the check of a
 // request, of the cohort's size, of its buffers and of an output that may be the input, and the two rules of a
 // one-workgroup-per-subject launch on dynamic LDS.  Host code only; every check is CGNN_OK or CGNN_EINVAL
 // (cgnn_check_cohort_within: or CGNN_EUNSUPPORTED) and touches no device.

@@ -1,4 +1,4 @@
-// wave_ops.h -- what the ingest kernels share of wave-level plumbing (knn.hip, mst.hip, modules.hip, pagerank.hip;
+// wave_ops.h -- what the ingest kernels share of wave-level plumbing (knn.hip, mst.hip, modules.hip, pagerank.hip, core.hip;
 // DESIGN.md 4.3u): the fence between a wave's own LDS accesses, and sums over the 64 lanes by a DPP scan in registers.
 // Device code only.
 #pragma once

@@ -498,9 +498,34 @@ entries is exactly ``1 / n``; a kept ``+inf`` makes that subject's ``weighted_pa
 compacted into LDS where they fit (``n <= PAGERANK_MAX_NODES = 1024``); no workspace, no atomics, no read-back, the same
 bits on every run, for every grid and for every subset and order of the two names.
 
+Cores: ``core_measures(matrices, keep=.., measures=CORE_MEASURES)`` answers not "how many neighbours"
+but "how deep inside the densely connected core": a leaf on a hub and a member of a 20-clique can share a degree and
+differ widely here.  With ``e_ij``, ``a_ij`` and ``b_ij`` as above, ``k_i(H) = sum_{j in H} b_ij`` and
+``s_i(H) = sum_{j in H} a_ij`` for a node set ``H`` (rows are what is summed; nothing is symmetrised), the generalised
+core value of Batagelj & Zaversnik for ``p = k`` or ``p = s`` is ``c(i) = max_{H containing i} min_{u in H} p_u(H)``,
+unique on any graph.  It is computed by peeling in rounds: ``L = 0``, ``r = 0``, all nodes alive; while a node is alive,
+``r += 1``, ``L = max(L, min over alive u of p_u(alive))`` and every alive ``u`` with ``p_u(alive) <= L`` is removed
+together, with value ``L`` and layer ``r``.
+
+* ``coreness``: ``k_i / (n - 1)`` with ``k_i`` the value for ``p = k``, the k-core number (``networkx.core_number`` on a
+  symmetric kept set; BCT's ``kcoreness_centrality_bu``); 0 for ``n == 1``; at most ``degree``
+* ``onion_layer``: ``r_i / n`` with ``r_i`` the layer for ``p = k`` (``networkx.onion_layers``; an isolated node is in
+  layer 1 of core 0)
+* ``s_coreness``: ``sigma_i / (max_i s_i(all) + 1e-8)`` with ``sigma_i`` the value for ``p = s``, the s-core level of
+  BCT's ``score_wu``, over ``strength``'s normaliser; at most ``strength``
+
+``k_i`` and ``r_i`` are exact integers and the first two columns one correctly rounded fp32 quotient.  Everything of
+``s`` after the edge test is fp64, rounded to fp32 once, and every ``s_u(alive)`` is summed anew from 0.0 over the row's
+kept entries at alive columns in ascending column order -- a removed neighbour is left out, never subtracted from a
+running sum -- so the rounded ``s`` is still monotone and the peeling is exactly its generalised core.  A kept ``+inf``
+makes that subject's ``s_coreness`` NaN and nothing else.  ``core_levels`` gives ``k_i``, ``r_i`` and the weighted layer
+``rho_i`` as int32 ``[S, n, 3]``.  One launch (csrc/core.hip), a workgroup per subject with its adjacency bitset in LDS
+(``n <= CORE_MAX_NODES = 1024``) and, where they fit, its kept weights beside it; no workspace, no atomics, no read-back,
+the same bits on every run, for every grid and for every subset and order of the three names.
+
 Group-consensus edges: every choice above is made inside one subject's matrix, so every subject gets a
 graph of its own and the differences are mostly noise.  ``group=`` of ``from_matrices``, ``node_measures``,
-``module_profile``, ``path_lengths``, ``centrality_measures`` and ``from_timeseries`` changes whose matrix the choice is
+``module_profile``, ``path_lengths``, ``centrality_measures``, ``core_measures`` and ``from_timeseries`` changes whose matrix the choice is
 made on: the whole edge choice (one of the three thresholds; or ``knn=`` / ``knn_mode=``; with or without
 ``backbone="mst"``) is applied to a group matrix ``G`` ``[n, n]`` as a cohort of one unit, and every subject is masked to
 that edge set.  ``group_matrix(matrices, statistic, among=)`` gives ``G`` (csrc/group.hip), ``statistic`` one of
@@ -579,6 +604,8 @@ CENTRALITY_MEASURES = ("pagerank", "weighted_pagerank")   # ids: include/cgnn_pa
 PAGERANK_MAX_NODES = 1024                             # CGNN_PAGERANK_MAX_NODES: a kept entry's column is stored in 16 bits
 PAGERANK_MAX_DAMPING = _lib.PAGERANK_MAX_DAMPING      # CGNN_PAGERANK_MAX_DAMPING: the step bound grows as 1 / (1 - d)
 GROUP_STATISTICS = ("mean", "fisher_mean", "consistency")   # ids: include/cgnn_group.h
+CORE_MEASURES = ("coreness", "onion_layer", "s_coreness")   # ids: include/cgnn_core.h
+CORE_MAX_NODES = 1024                                 # CGNN_CORE_MAX_NODES: the adjacency bitset must fit LDS
 
 
 class _Family(NamedTuple):
@@ -609,6 +636,9 @@ _ALL_MEASURES = tuple(name for fam in _FAMILIES for name in fam.names)
 # of the workspace, iterations / iterations_bytes follow x)
 _CENTRALITY = _Family(CENTRALITY_MEASURES, "cgnn_ingest_pagerank", True, False, PAGERANK_MAX_NODES,
                       "centrality measures", "a kept entry's column is stored in 16 bits", tail=_lib.buf(None))
+# core_measures's and core_levels's: likewise a call of its own (levels / levels_bytes follow x)
+_CORE = _Family(CORE_MEASURES, "cgnn_ingest_cores", True, False, CORE_MAX_NODES, "core measures",
+                "the adjacency bitset of a subject must fit LDS", tail=_lib.buf(None))
 
 
 def _check_matrices(matrices) -> tuple:
@@ -1958,6 +1988,50 @@ def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, mi
     matrices, thr = edges.apply(matrices)
     x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
     return _run_family(_CENTRALITY, matrices, thr, ids, list(range(len(ids))), x, mid=(damping,))
+
+
+def core_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None, knn_mode="union",
+                  backbone=None, measures=CORE_MEASURES, group=None) -> torch.Tensor:
+    """The core decomposition of the thresholded matrices as node features: float32 ``[S, n, len(measures)]`` on
+    ``matrices.device``, one column per name in ``measures``, names from ``CORE_MEASURES`` in any order (module
+    docstring): ``coreness`` is the k-core number over ``n - 1`` (how deep inside the densely connected core a node
+    lies; at most its ``degree``), ``onion_layer`` the round of the peeling in which the node leaves, over ``n``, and
+    ``s_coreness`` the s-core level over the largest strength (at most its ``strength``).  The edges are those
+    ``node_measures`` sees for the same ``keep`` / ``num_edges`` / ``min_weight`` / ``knn`` / ``knn_mode`` /
+    ``backbone``, chosen the same way (``knn=`` and ``backbone=`` cost the cohort-sized temporaries named in
+    ``from_matrices``).  One launch on resident data (csrc/core.hip); no workspace, no read-back, no atomics: every
+    run, every grid and every subset and order of the names gives the same bits.  A kept ``+inf`` makes that subject's
+    ``s_coreness`` NaN and nothing else.  ``n <= CORE_MAX_NODES``.  The result is what ``node_features=`` of
+    ``from_matrices`` / ``from_timeseries`` takes; its three columns keep a cohort on the fused GCN path.  ``group`` is
+    ``from_matrices``'s.
+
+    Like ``centrality_measures`` this is a call of its own and the names are not among those of
+    ``node_measures(measures=)``, whose table is pinned."""
+    S, n = _check_matrices(matrices)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
+    ids = [i for _, i in _measure_ids(measures, (_CORE,), _CORE.what)]
+    _check_size(_CORE, n, "core_measures takes")
+    matrices, thr = edges.apply(matrices)
+    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
+    return _run_family(_CORE, matrices, thr, ids, list(range(len(ids))), x)
+
+
+def core_levels(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None, knn_mode="union",
+                backbone=None, group=None) -> torch.Tensor:
+    """The integers behind ``core_measures``: int32 ``[S, n, 3]`` on ``matrices.device`` with the k-core number ``k_i``,
+    the onion layer ``r_i`` and the layer ``rho_i`` of the weighted peeling (module docstring), for analyses that want
+    them as such -- the members of the 12-core are ``core_levels(m, keep=0.1)[:, :, 0] >= 12``.  A subject with a kept
+    ``+inf`` has ``rho_i = -1``.  The edge choice is ``core_measures``'s; one launch, the same kernel, whose three
+    float columns are the one temporary.  ``n <= CORE_MAX_NODES``."""
+    S, n = _check_matrices(matrices)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
+    _check_size(_CORE, n, "core_levels takes")
+    matrices, thr = edges.apply(matrices)
+    num = len(CORE_MEASURES)
+    x = torch.empty(S, n, num, dtype=torch.float32, device=matrices.device)
+    levels = torch.empty(S, n, 3, dtype=torch.int32, device=matrices.device)
+    _run_family(_CORE, matrices, thr, list(range(num)), list(range(num)), x, tail=_lib.buf(levels))
+    return levels
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
