@@ -346,6 +346,14 @@ CORE_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_rw.h declares (cgnn.h includes it), in the same form, and the one flag.
+RW_BINARY = 1
+RW_PROTOTYPES = {
+    "cgnn_ingest_rw_workspace_bytes": (I64, [I64, I32, P, I32]),
+    "cgnn_ingest_rw": (c_int, [P, I64, I32, P, P, I32, P, I32, I32, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -366,7 +374,8 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
                               **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
-                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES, **CORE_PROTOTYPES}.items():
+                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES, **CORE_PROTOTYPES,
+                              **RW_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

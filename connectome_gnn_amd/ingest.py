@@ -523,9 +523,28 @@ makes that subject's ``s_coreness`` NaN and nothing else.  ``core_levels`` gives
 (``n <= CORE_MAX_NODES = 1024``) and, where they fit, its kept weights beside it; no workspace, no atomics, no read-back,
 the same bits on every run, for every grid and for every subset and order of the three names.
 
+Random-walk encodings: ``random_walk_encodings(matrices, keep=.., steps=8)`` is the structural
+encoding a GNN user reaches for first (RWSE: Dwivedi et al. 2022, PyG's ``AddRandomWalkPE``): the probability that a
+``k``-step random walk from a node is back at it.  With ``e_ij`` as above, ``a_ij = A_ij`` on edges (``1`` on edges with
+``binary=True``) and ``0`` elsewhere, ``s_i = sum_j a_ij`` and ``P_ij = a_ij / s_i`` (an exact zero row where
+``s_i == 0``; rows are what is summed, nothing is symmetrised), the column of step ``k`` is ``r_k(i) = ((P)^k)_ii``.
+That is the definition for asymmetric input too; on a symmetric kept set it is ``AddRandomWalkPE``.  Every value lies in
+``[0, 1]`` and is unique on the disconnected graphs a threshold returns.  ``r_1``, an isolated node's row, a subject
+without edges and ``n == 1`` are exactly ``0.0``, and so is every odd step on a bipartite kept set; a kept ``+inf``
+(weights only: ``binary=True`` never reads a weight as a number) makes that subject's columns for ``k >= 2`` NaN and
+nothing else.  Arithmetic: ``s_i`` is an fp64 sum in ascending column order rounded to fp32 once, ``P_ij`` one fp32
+division, ``M2 = P P``, ``M3 = P M2`` and ``M4 = M2 M2`` are fp32 products on the matrix pipe with ``k`` ascending (only
+those the largest step needs), and ``r_k(i) = sum_j (M_a)_ij (M_b)_ji`` with ``a = k // 2``, ``b = k - a`` and
+``M1 = P`` is an fp64 sum of exact products in ascending ``j``, rounded to fp32 once:
+``|r_k - fp64| <= 1.01 ((k - 2) n + 2 k + 1) 2^-24 |r_k| + 2^-40``.  One launch (csrc/rw.hip), persistent workgroups
+with a grid stride over the subjects, the intermediates in a slab set per workgroup (``n <= RW_MAX_NODES = 1024``;
+``P`` is never stored); no cohort-sized temporary, no atomics, no read-back, the same bits on every run, for every grid
+and for every subset and order of the steps.
+
 Group-consensus edges: every choice above is made inside one subject's matrix, so every subject gets a
 graph of its own and the differences are mostly noise.  ``group=`` of ``from_matrices``, ``node_measures``,
-``module_profile``, ``path_lengths``, ``centrality_measures``, ``core_measures`` and ``from_timeseries`` changes whose matrix the choice is
+``module_profile``, ``path_lengths``, ``centrality_measures``, ``core_measures``, ``random_walk_encodings`` and
+``from_timeseries`` changes whose matrix the choice is
 made on: the whole edge choice (one of the three thresholds; or ``knn=`` / ``knn_mode=``; with or without
 ``backbone="mst"``) is applied to a group matrix ``G`` ``[n, n]`` as a cohort of one unit, and every subject is masked to
 that edge set.  ``group_matrix(matrices, statistic, among=)`` gives ``G`` (csrc/group.hip), ``statistic`` one of
@@ -606,6 +625,8 @@ PAGERANK_MAX_DAMPING = _lib.PAGERANK_MAX_DAMPING      # CGNN_PAGERANK_MAX_DAMPIN
 GROUP_STATISTICS = ("mean", "fisher_mean", "consistency")   # ids: include/cgnn_group.h
 CORE_MEASURES = ("coreness", "onion_layer", "s_coreness")   # ids: include/cgnn_core.h
 CORE_MAX_NODES = 1024                                 # CGNN_CORE_MAX_NODES: the adjacency bitset must fit LDS
+RW_MAX_STEPS = 8                                      # CGNN_RW_MAX_STEPS: M2, M3 and M4 reach step 8
+RW_MAX_NODES = 1024                                   # CGNN_RW_MAX_NODES: the fp32 row sums of a subject live in LDS
 
 
 class _Family(NamedTuple):
@@ -639,6 +660,10 @@ _CENTRALITY = _Family(CENTRALITY_MEASURES, "cgnn_ingest_pagerank", True, False, 
 # core_measures's and core_levels's: likewise a call of its own (levels / levels_bytes follow x)
 _CORE = _Family(CORE_MEASURES, "cgnn_ingest_cores", True, False, CORE_MAX_NODES, "core measures",
                 "the adjacency bitset of a subject must fit LDS", tail=_lib.buf(None))
+# random_walk_encodings's: likewise a call of its own; the "names" are the steps 1 .. RW_MAX_STEPS, step k has id k - 1
+# (the flags stand in front of the workspace)
+_RW = _Family(tuple(range(1, RW_MAX_STEPS + 1)), "cgnn_ingest_rw", True, False, RW_MAX_NODES, "random-walk encodings",
+              "the fp32 row sums of a subject live in LDS")
 
 
 def _check_matrices(matrices) -> tuple:
@@ -2032,6 +2057,58 @@ def core_levels(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight
     levels = torch.empty(S, n, 3, dtype=torch.int32, device=matrices.device)
     _run_family(_CORE, matrices, thr, list(range(num)), list(range(num)), x, tail=_lib.buf(levels))
     return levels
+
+
+def _check_steps(steps) -> list:
+    """The ids (``k - 1``) of a valid ``steps=``: an int ``K`` in ``1 .. RW_MAX_STEPS`` stands for ``1, .., K``; else a
+    non-empty tuple or list of distinct ints in that range, in any order."""
+    def step(k):
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise TypeError(f"steps must be an int or a tuple of ints in 1 .. {RW_MAX_STEPS}, got {k!r}")
+        if not 1 <= k <= RW_MAX_STEPS:
+            raise ValueError(f"a step must lie in 1 .. RW_MAX_STEPS = {RW_MAX_STEPS} (steps beyond it need more "
+                             f"intermediate products), got {k}")
+        return k
+    if isinstance(steps, (tuple, list)):
+        if len(steps) == 0:
+            raise ValueError(f"steps is empty: name at least one of 1 .. {RW_MAX_STEPS}")
+        ids = []
+        for k in steps:
+            if step(k) - 1 in ids:
+                raise ValueError(f"step {k} is named twice")
+            ids.append(k - 1)
+        return ids
+    return list(range(step(steps)))
+
+
+def random_walk_encodings(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
+                          knn_mode="union", backbone=None, group=None, steps=RW_MAX_STEPS,
+                          binary=False) -> torch.Tensor:
+    """The random-walk structural encoding of the thresholded matrices as node features (RWSE; PyG's
+    ``AddRandomWalkPE`` on a symmetric kept set): float32 ``[S, n, len(steps)]`` on ``matrices.device``, the column of
+    step ``k`` holding ``((P)^k)_ii``, the probability that a ``k``-step walk from node ``i`` is back at ``i``, with
+    ``P`` the row-normalised kept weights (module docstring; ``binary=True`` walks the kept entries with equal weights).
+    ``steps`` is an int ``K`` in ``1 .. RW_MAX_STEPS`` for the steps ``1, .., K``, or a tuple of distinct steps in any
+    order, one column each.  The edges are those ``node_measures`` sees for the same ``keep`` / ``num_edges`` /
+    ``min_weight`` / ``knn`` / ``knn_mode`` / ``backbone``, chosen the same way (``knn=`` and ``backbone=`` cost the
+    cohort-sized temporaries named in ``from_matrices``).  One launch on resident data (csrc/rw.hip); the intermediate
+    products live in a workspace of one slab set per workgroup, whatever ``S`` is; no read-back, no atomics: every run,
+    every grid and every subset and order of the steps gives the same bits.  Every value lies in ``[0, 1]``; step 1 is
+    exactly 0; a kept ``+inf`` makes that subject's columns for ``k >= 2`` NaN and nothing else.
+    ``n <= RW_MAX_NODES``.  The result is what ``node_features=`` of ``from_matrices`` / ``from_timeseries`` takes; the
+    default eight columns are exactly those that keep a cohort on the fused GCN path.  ``group`` is ``from_matrices``'s.
+
+    Like ``centrality_measures`` and ``core_measures`` this is a call of its own, not a name of
+    ``node_measures(measures=)``, whose table is pinned."""
+    S, n = _check_matrices(matrices)
+    edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
+    ids = _check_steps(steps)
+    if not isinstance(binary, bool):
+        raise TypeError(f"binary must be a bool, got {type(binary).__name__}")
+    _check_size(_RW, n, "random_walk_encodings takes")
+    matrices, thr = edges.apply(matrices)
+    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
+    return _run_family(_RW, matrices, thr, ids, list(range(len(ids))), x, mid=(_lib.RW_BINARY if binary else 0,))
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,
