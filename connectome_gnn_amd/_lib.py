@@ -354,6 +354,13 @@ RW_PROTOTYPES = {
 }
 
 
+# The entry points that include/cgnn_rank.h declares (cgnn.h includes it), in the same form.
+RANK_PROTOTYPES = {
+    "cgnn_ingest_rank": (c_int, [P, I64, I32, I32, I32, I32, P, I64, P]),
+    "cgnn_ingest_rank_masked": (c_int, [P, I64, I32, I32, I32, I32, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -375,7 +382,7 @@ def load() -> ctypes.CDLL:
     for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
                               **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
                               **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES, **CORE_PROTOTYPES,
-                              **RW_PROTOTYPES}.items():
+                              **RW_PROTOTYPES, **RANK_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -576,6 +576,26 @@ Each call with ``group=`` is, bit for bit, the same call on ``group_sparsify(mat
 group edge is not positive drops that edge, so subjects' edge sets are subsets of ``E``.  The statistic streams the cohort
 once into a workspace ``1 / 32`` its size and folds it (two launches), the mask copies it once (one launch); no atomics, no
 read-back, the same bits on every run and for every grid.  Without ``group=`` every call launches what it launched before.
+
+Rank correlation: Pearson and partial correlation are moment estimators, so a few spiky frames decide an
+edge; scrubbing helps only where the bad frames are known.  Spearman's rho needs no frame list, and it is the Pearson
+correlation of the mid-ranks, so the one new step is the ranking: ``rank_timeseries(timeseries, window=, stride=,
+sample_mask=)`` gives float32 ``[U, L, n]`` (``[S, T, n]`` without a window), per unit and column over the unit's kept
+frames ``rank(t) = 1 + #{t': v_t' < v_t} + (#{t': v_t' == v_t} - 1) / 2``, ``scipy.stats.rankdata(method="average")``.
+The comparisons are the IEEE ones of the fp32 values, on order-preserving integer keys: ``-0.0 == +0.0``, ``+-inf`` are
+ordinary values, subnormals are distinct and never flushed.  A NaN in a kept frame makes the kept frames of that column
+of that unit NaN and nothing else; a censored frame is exactly ``0.0`` and its value is never looked at; a column that is
+constant on its ``L_u`` kept frames is ``(L_u + 1) / 2`` there, which the correlation's constant-ROI rule turns into an
+exact zero row and column.  Every value is a multiple of ``1/2`` up to ``RANK_MAX_FRAMES = 4096``, exact in fp32: the
+output is the fp32 cast of the statement bit for bit, on every run, for every grid, and in place (``out=timeseries``,
+without a window).  ``rank=True`` of ``correlation_matrices``, ``from_timeseries`` and ``ledoit_wolf_shrinkage`` is, bit
+for bit, the same call without a window on ``rank_timeseries(timeseries, window=, stride=, sample_mask=)`` with the mask
+unfolded to ``[U, L]``; ranking is an argument beside ``kind``, not a kind, so ``rank=True, kind="partial"`` is the
+partial Spearman correlation.  The ranked series is one temporary ``[U, L, n]``: the size of the input without a window,
+``W L / T`` times it with one; it is freed before the call returns.  One launch (csrc/rank.hip): persistent workgroups
+over (unit, 4 adjacent columns), the columns staged in LDS as (key, frame) pairs, a wave sorting a column (bitonic), tie
+runs by neighbour comparison and two scans; no workspace, no atomics, no read-back.  Left out: Kendall's tau, rank-based
+inverse-normal scores, units of more than 4096 frames.
 """
 from __future__ import annotations
 
@@ -627,6 +647,7 @@ CORE_MEASURES = ("coreness", "onion_layer", "s_coreness")   # ids: include/cgnn_
 CORE_MAX_NODES = 1024                                 # CGNN_CORE_MAX_NODES: the adjacency bitset must fit LDS
 RW_MAX_STEPS = 8                                      # CGNN_RW_MAX_STEPS: M2, M3 and M4 reach step 8
 RW_MAX_NODES = 1024                                   # CGNN_RW_MAX_NODES: the fp32 row sums of a subject live in LDS
+RANK_MAX_FRAMES = 4096                                # CGNN_RANK_MAX_FRAMES: a unit's (key, frame) pairs of 4 columns must fit LDS
 
 
 class _Family(NamedTuple):
@@ -854,15 +875,17 @@ def filter_components(T: int, t_r, high_pass=None, low_pass=None) -> tuple:
     return k_lo, k_hi
 
 
-def _check_out(out, like: torch.Tensor, noun="time series") -> None:
+def _check_out(out, like: torch.Tensor, noun="time series", shape=None) -> None:
+    """A valid ``out=``: None, or a float32 contiguous tensor on ``like``'s device, of ``like``'s shape or of ``shape``."""
     if out is None:
         return
     if not isinstance(out, torch.Tensor):
         raise TypeError(f"out must be a torch.Tensor or None, got {type(out).__name__}")
     if out.dtype != torch.float32:
         raise TypeError(f"out must be float32, got {out.dtype}")
-    if out.shape != like.shape:
-        raise ValueError(f"out must be {tuple(like.shape)} as the {noun} are, got {tuple(out.shape)}")
+    if tuple(out.shape) != tuple(like.shape if shape is None else shape):
+        raise ValueError(f"out must be {tuple(like.shape if shape is None else shape)} as the {noun} are, got "
+                         f"{tuple(out.shape)}")
     if out.device != like.device:
         raise ValueError(f"out is on {out.device}, the {noun} on {like.device}")
     if not out.is_contiguous():
@@ -1442,6 +1465,63 @@ def _connectivity(timeseries: torch.Tensor, series: _Series, windowed: bool, abs
     return _partial(matrices, series.S * series.W, series.n, shrinkage, absolute, matrices)
 
 
+def _check_rank(rank, L: int) -> bool:
+    """A valid rank= for units of L frames."""
+    if not isinstance(rank, bool):
+        raise TypeError(f"rank must be a bool, got {type(rank).__name__}")
+    if rank:
+        _check_rank_frames(L)
+    return rank
+
+
+def _check_rank_frames(L: int) -> None:
+    if L > RANK_MAX_FRAMES:
+        raise ValueError(f"ranking takes units of at most RANK_MAX_FRAMES = {RANK_MAX_FRAMES} frames (a unit's values "
+                         f"and their frame indices must fit LDS), got {L}: rank shorter windows")
+
+
+def _rank_series(timeseries: torch.Tensor, series: _Series, windowed: bool, keep, out: torch.Tensor) -> torch.Tensor:
+    """cgnn_ingest_rank of a valid request on resident data into ``out`` [U, L, n], which without a window may be
+    ``timeseries``."""
+    S, T, n = series[:3]
+    if S:
+        name, mask = _masked("cgnn_ingest_rank", keep)
+        _call(timeseries.device, name, timeseries, S, T, n, *series.window(windowed), *mask, *_lib.buf(out))
+    return out
+
+
+def _ranked(timeseries: torch.Tensor, series: _Series, windowed: bool, keep) -> tuple:
+    """What ``rank=True`` puts in place of a valid request on resident data: (the ranked series ``[U, L, n]``, a new
+    tensor; its ``_Series``, whole runs of L frames; its mask ``[U, L]``, the windows of ``keep``)."""
+    S, T, n, L, st, W = series
+    ranked = torch.empty(S * W, L, n, dtype=torch.float32, device=timeseries.device)
+    _rank_series(timeseries, series, windowed, keep, ranked)
+    if keep is not None and windowed:
+        keep = keep.unfold(1, L, st).reshape(S * W, L).contiguous()
+    return ranked, _Series(S * W, L, n, L, L, 1), keep
+
+
+def rank_timeseries(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None, out=None) -> torch.Tensor:
+    """The mid-ranks of every column of every unit over the unit's kept frames (module docstring): float32 ``[U, L, n]``
+    on the time series' device, ``[S, T, n]`` without a window; the units are ``correlation_matrices``'s.  The Pearson
+    correlation of the result is Spearman's rho.  ``sample_mask`` (bool ``[S, T]``, True: kept): the ranks run over the
+    unit's kept frames, a censored frame is exactly ``0.0`` and its value is never looked at.  ``out``: without a window
+    it may be ``timeseries`` itself, with the same bits; with one it is None or a ``[U, L, n]`` tensor.  A unit has at
+    most ``RANK_MAX_FRAMES`` frames.  One launch on resident data, no temporaries, no read-back."""
+    series = _check_timeseries(timeseries, window, stride)
+    S, T, n, L, _, W = series
+    _check_rank_frames(L)
+    keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
+    if window is None:
+        _check_out(out, timeseries)
+    else:
+        _check_out(out, timeseries, "ranked units", (S * W, L, n))
+    _require_resident(timeseries, *_SERIES)
+    if out is None:
+        out = torch.empty(S * W, L, n, dtype=torch.float32, device=timeseries.device)
+    return _rank_series(timeseries, series, window is not None, keep, out)
+
+
 def _check_labels_and_features(labels, S: int, node_features, letter: str, units: int, n: int) -> None:
     """``labels`` int64 ``[S]``; ``node_features`` None or float32 ``[units, n, F]``, ``letter`` naming the units."""
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
@@ -1452,23 +1532,30 @@ def _check_labels_and_features(labels, S: int, node_features, letter: str, units
             raise ValueError(f"node_features must be a float32 tensor [{letter}, n, F] = [{units}, {n}, F]")
 
 
-def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None) -> torch.Tensor:
+def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None,
+                          rank=False) -> torch.Tensor:
     """The Ledoit-Wolf shrinkage of every unit's correlation matrix, estimated from the unit's own frames: float64
     ``[U]`` on the time series' device (module docstring); what ``partial_correlation(..., shrinkage=)`` takes.  Three
     launches on resident data (the two of ``correlation_matrices``, then the estimate); the matrices and the statistics
     are temporaries.  ``n <= PARTIAL_MAX_NODES``.  No read-back.  ``sample_mask`` (bool ``[S, T]``, True: kept): a
-    unit's frames are its window's kept ones, ``L_u`` of them, and ``L_u`` stands wherever ``L`` does."""
+    unit's frames are its window's kept ones, ``L_u`` of them, and ``L_u`` stands wherever ``L`` does.  ``rank=True``:
+    the estimate for the Spearman matrices, from ``rank_timeseries(timeseries, window=, stride=, sample_mask=)`` (one
+    more launch; the ranked series ``[U, L, n]`` is one more temporary, ``W L / T`` times the input with a window)."""
     series = _check_timeseries(timeseries, window, stride)
     _check_partial_size(series.n)
+    rank = _check_rank(rank, series.L)
     keep = _check_sample_mask(sample_mask, series.S, series.T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
     windowed = window is not None
+    if rank:
+        timeseries, series, keep = _ranked(timeseries, series, windowed, keep)
+        windowed = False
     matrices, stats = _correlate(timeseries, series, windowed, False, keep)
     return _estimate(timeseries, series, windowed, stats, matrices, keep)
 
 
 def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
-                         shrinkage=0.0, sample_mask=None) -> torch.Tensor:
+                         shrinkage=0.0, sample_mask=None, rank=False) -> torch.Tensor:
     """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
     (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics.
     ``kind="partial"`` gives ``partial_correlation`` of the signed correlations at ``shrinkage``, written in place
@@ -1476,19 +1563,28 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
     tensor or ``"ledoit_wolf"``: each unit's own estimate (``ledoit_wolf_shrinkage``), a launch between the two.
     ``sample_mask`` (bool ``[S, T]``, True: kept): a unit's frames are its window's kept ones; a unit with fewer than
     two is an all-zero matrix.  The ``n + 2`` frames that ``shrinkage == 0`` asks for are still counted on the window:
-    kept counts stay on the device, and a unit that its kept frames leave singular is all NaN."""
+    kept counts stay on the device, and a unit that its kept frames leave singular is all NaN.
+    ``rank=True`` gives Spearman's rank correlation (with ``kind="partial"`` the partial one): bit for bit this call
+    without a window on ``rank_timeseries(timeseries, window=, stride=, sample_mask=)`` and the mask's windows
+    ``[U, L]``.  One more launch; the ranked series ``[U, L, n]`` is one more temporary -- the size of the input without
+    a window, ``W L / T`` times it with one -- freed before the call returns.  ``L <= RANK_MAX_FRAMES``."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
+    rank = _check_rank(rank, L)
     shrinkage = _check_kind(kind, shrinkage, n, L, S * W, timeseries)
     keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
-    return _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, keep)
+    windowed = window is not None
+    if rank:
+        timeseries, series, keep = _ranked(timeseries, series, windowed, keep)
+        windowed = False
+    return _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, keep)
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
                     kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
-                    knn_mode="union", modules=None, backbone=None, group=None) -> RaggedPackedDataset:
+                    knn_mode="union", modules=None, backbone=None, group=None, rank=False) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
@@ -1497,10 +1593,13 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     thresholds: the k-NN graph of every unit's matrix, as in ``from_matrices``; the connectivity temporary is sparsified
     in place, which costs no extra memory.  ``modules`` is ``from_matrices``'s.  ``backbone`` is ``from_matrices``'s: the
     connectivity temporary becomes the united graph in place (with ``knn=`` the tree is one more temporary).  ``group``
-    is ``from_matrices``'s, its units the windows: the connectivity temporary is masked to the group's edges in place."""
+    is ``from_matrices``'s, its units the windows: the connectivity temporary is masked to the group's edges in place.
+    ``rank`` is ``correlation_matrices``'s: Spearman connectivity; the ranked series ``[U, L, n]`` is a temporary beside
+    the connectivity one (``W L / T`` times the input with a window) and is freed before the dataset is built."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
+    rank = _check_rank(rank, L)
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
@@ -1509,7 +1608,12 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     _check_labels_and_features(labels, S, node_features, "U", U, n)
     sample_mask = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
-    matrices = _connectivity(timeseries, series, window is not None, absolute, kind, shrinkage, sample_mask)
+    windowed = window is not None
+    if rank:
+        timeseries, series, sample_mask = _ranked(timeseries, series, windowed, sample_mask)
+        windowed = False
+    matrices = _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, sample_mask)
+    del timeseries                                    # (the ranked temporary, under rank=True)
     choice = dict(keep=keep, num_edges=num_edges, min_weight=min_weight)       # the caller's, as they came
     if edges.sparsify:
         edges.sparsified(matrices, matrices)
