@@ -365,6 +365,37 @@ class CgnnError(RuntimeError):
     pass
 
 
+# THE binding: header under include/ -> its table, cgnn.h first, then the headers it includes in its order.  An entry
+# here is all that binds a family: load() walks this mapping, tests/abi_header.py compares a table with its header, and
+# tests/test_host_logic.py compares the keys with cgnn.h's include lines.
+HEADERS = {
+    "cgnn.h": PROTOTYPES,
+    "cgnn_butterworth.h": BUTTERWORTH_PROTOTYPES,
+    "cgnn_optim.h": OPTIM_PROTOTYPES,
+    "cgnn_knn.h": KNN_PROTOTYPES,
+    "cgnn_modules.h": MODULE_PROTOTYPES,
+    "cgnn_mst.h": MST_PROTOTYPES,
+    "cgnn_activity.h": ACTIVITY_PROTOTYPES,
+    "cgnn_pagerank.h": PAGERANK_PROTOTYPES,
+    "cgnn_group.h": GROUP_PROTOTYPES,
+    "cgnn_core.h": CORE_PROTOTYPES,
+    "cgnn_rw.h": RW_PROTOTYPES,
+    "cgnn_rank.h": RANK_PROTOTYPES,
+}
+
+
+def check_disjoint(headers) -> None:
+    """A name in the tables of two headers raises, naming both: bound one after the other, the later row would win."""
+    owner = {}
+    for header, table in headers.items():
+        for name in table:
+            if name in owner:
+                raise CgnnError(f"{name} is in the tables of both {owner[name]} and {header}")
+            owner[name] = header
+
+
+check_disjoint(HEADERS)
+
 _lib = None
 
 
@@ -379,15 +410,13 @@ def load() -> ctypes.CDLL:
             "g.build()'` or `make -C connectome_gnn_amd/csrc`.  connectome_gnn_amd has no "
             "CPU/eager fallback for the message-passing path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **BUTTERWORTH_PROTOTYPES, **OPTIM_PROTOTYPES, **KNN_PROTOTYPES,
-                              **MODULE_PROTOTYPES, **MST_PROTOTYPES, **ACTIVITY_PROTOTYPES,
-                              **PAGERANK_PROTOTYPES, **GROUP_PROTOTYPES, **CORE_PROTOTYPES,
-                              **RW_PROTOTYPES, **RANK_PROTOTYPES}.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:  # pragma: no cover
-            raise CgnnError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype, fn.argtypes = res, args
+    for header, table in HEADERS.items():
+        for name, (res, args) in table.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:  # pragma: no cover
+                raise CgnnError(f"{LIB_PATH} does not export {name} ({header})") from e
+            fn.restype, fn.argtypes = res, args
     v = lib.cgnn_abi_version()
     if v != ABI_VERSION:
         raise CgnnError(f"libcgnn_hip.so ABI {v} != binding ABI {ABI_VERSION}")

@@ -2008,6 +2008,13 @@ def _run_family(fam: _Family, matrices: torch.Tensor, thr: torch.Tensor, ids, co
     return x
 
 
+def _run_packed(fam: _Family, matrices: torch.Tensor, thr: torch.Tensor, ids, mid=(), tail=None) -> torch.Tensor:
+    """One call of ``fam`` on its own: a new float32 ``[S, n, len(ids)]`` on the matrices' device, column ``m`` holding
+    ``ids[m]``.  ``mid`` and ``tail`` are ``_run_family``'s."""
+    x = torch.empty(matrices.shape[0], matrices.shape[1], len(ids), dtype=torch.float32, device=matrices.device)
+    return _run_family(fam, matrices, thr, ids, list(range(len(ids))), x, mid=mid, tail=tail)
+
+
 def _measures(matrices: torch.Tensor, S: int, n: int, thr: torch.Tensor, ids: list, modules=None) -> torch.Tensor:
     """``[S, n, len(ids)]``, one call per family that is named.  A request of classic names only is one packed
     cgnn_ingest_measures call, as before; the other families write their columns in place (cols / ldx).  ``modules`` is
@@ -2115,8 +2122,7 @@ def centrality_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, mi
     damping = _check_damping(damping)
     _check_size(_CENTRALITY, n, "centrality_measures takes")
     matrices, thr = edges.apply(matrices)
-    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
-    return _run_family(_CENTRALITY, matrices, thr, ids, list(range(len(ids))), x, mid=(damping,))
+    return _run_packed(_CENTRALITY, matrices, thr, ids, mid=(damping,))
 
 
 def core_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None, knn_mode="union",
@@ -2141,8 +2147,7 @@ def core_measures(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weig
     ids = [i for _, i in _measure_ids(measures, (_CORE,), _CORE.what)]
     _check_size(_CORE, n, "core_measures takes")
     matrices, thr = edges.apply(matrices)
-    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
-    return _run_family(_CORE, matrices, thr, ids, list(range(len(ids))), x)
+    return _run_packed(_CORE, matrices, thr, ids)
 
 
 def core_levels(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None, knn_mode="union",
@@ -2156,10 +2161,8 @@ def core_levels(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight
     edges = _edge_plan(n, S, "S", knn, knn_mode, backbone, keep, num_edges, min_weight, group)
     _check_size(_CORE, n, "core_levels takes")
     matrices, thr = edges.apply(matrices)
-    num = len(CORE_MEASURES)
-    x = torch.empty(S, n, num, dtype=torch.float32, device=matrices.device)
     levels = torch.empty(S, n, 3, dtype=torch.int32, device=matrices.device)
-    _run_family(_CORE, matrices, thr, list(range(num)), list(range(num)), x, tail=_lib.buf(levels))
+    _run_packed(_CORE, matrices, thr, list(range(len(CORE_MEASURES))), tail=_lib.buf(levels))
     return levels
 
 
@@ -2211,8 +2214,7 @@ def random_walk_encodings(matrices: torch.Tensor, *, keep=None, num_edges=None, 
         raise TypeError(f"binary must be a bool, got {type(binary).__name__}")
     _check_size(_RW, n, "random_walk_encodings takes")
     matrices, thr = edges.apply(matrices)
-    x = torch.empty(S, n, len(ids), dtype=torch.float32, device=matrices.device)
-    return _run_family(_RW, matrices, thr, ids, list(range(len(ids))), x, mid=(_lib.RW_BINARY if binary else 0,))
+    return _run_packed(_RW, matrices, thr, ids, mid=(_lib.RW_BINARY if binary else 0,))
 
 
 def path_lengths(matrices: torch.Tensor, *, keep=None, num_edges=None, min_weight=None, knn=None,

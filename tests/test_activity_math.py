@@ -14,6 +14,7 @@ import torch
 
 from connectome_gnn_amd import _lib, ingest
 from tests import activity_data as A
+from tests.abi_header import check_header
 
 # what is under test: the statement of tests/activity_data.py is checked below as the reference of these two, with the
 # band taken from series_band and the names and their order from ingest.SERIES_FEATURES
@@ -29,8 +30,9 @@ def test_the_names_and_limits_are_the_headers():
     assert ingest.SERIES_MAX_FRAMES == 4096
     T = ingest.SERIES_MAX_FRAMES
     assert T * 2 * (T // 2) * 4 <= 64 * 2 ** 20, "falff's table stays at or below 64 MB"
-    assert set(_lib.ACTIVITY_PROTOTYPES) == {"cgnn_ingest_activity_workspace_bytes", "cgnn_ingest_activity"}
-    assert not set(_lib.ACTIVITY_PROTOTYPES) & set(_lib.PROTOTYPES)
+    check_header("cgnn_activity.h", _lib.ACTIVITY_PROTOTYPES,
+                 ["cgnn_ingest_activity_workspace_bytes", "cgnn_ingest_activity"],
+                 [("int32_t n, int32_t bins", "int64_t n, int32_t bins"), ("int32_t k_lo, ", "")])
 
 
 @pytest.mark.parametrize("T,n,t_r,lo,hi", A.CASES)

@@ -9,8 +9,6 @@ within 2^-43.4 max_t |x| (order 6; 2^-45.8 at order 5) of ``sosfiltfilt`` over t
 """
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -21,6 +19,7 @@ import scipy.signal  # noqa: E402
 
 from connectome_gnn_amd import _lib, ingest  # noqa: E402
 from tests import butter_data as B  # noqa: E402
+from tests.abi_header import check_header  # noqa: E402
 from tests import confound_data as D  # noqa: E402
 from tests import filter_data as F  # noqa: E402
 
@@ -217,24 +216,9 @@ def test_the_prototypes_match_their_header_type_by_type():
     """The two entry points are declared in include/cgnn_butterworth.h, which cgnn.h includes, and bound by
     ``_lib.BUTTERWORTH_PROTOTYPES``: the return type and every argument type of both, the library's exports, and the
     comparison itself against a doctored header."""
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_butterworth.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.BUTTERWORTH_PROTOTYPES.items()}
-    assert len(_lib.BUTTERWORTH_PROTOTYPES) == 2 and not set(_lib.BUTTERWORTH_PROTOTYPES) & set(_lib.PROTOTYPES)
-    assert declared(hdr.replace("const double* sos, int32_t L", "const double* sos, int64_t L")) != declared(hdr)
-    assert '#include "cgnn_butterworth.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
-    lib = _lib.load()
-    for name, (res, args) in _lib.BUTTERWORTH_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
+    hdr = check_header("cgnn_butterworth.h", _lib.BUTTERWORTH_PROTOTYPES,
+                       ["cgnn_ingest_butterworth_workspace_bytes", "cgnn_ingest_butterworth"],
+                       [("const double* sos, int32_t L", "const double* sos, int64_t L")])
     assert "#define CGNN_BUTTER_MAX_SECTIONS 8" in hdr and ingest.BUTTERWORTH_MAX_ORDER == 8
 
 

@@ -3,8 +3,6 @@
 the strength; the argument checks of ``ingest.core_measures`` / ``core_levels``; the header and the binding of
 cgnn_ingest_cores and the refusals of the C entry point, none of which reaches a launch.  No device is touched."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import torch
 from connectome_gnn_amd import _lib, ingest
 from tests import core_data as CD
 from tests import measures_data as MD
+from tests.abi_header import check_header
 
 NAMES = CD.CORE_MEASURES
 HOST_SIZES = (1, 2, 3, 5, 63, 84, 129, 360)
@@ -175,30 +174,10 @@ def test_core_measures_checks_its_arguments():
 
 # ---- the C ABI ----
 def test_the_prototypes_match_their_header_type_by_type():
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_core.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.CORE_PROTOTYPES.items()}
-    assert list(_lib.CORE_PROTOTYPES) == ["cgnn_ingest_cores_workspace_bytes", "cgnn_ingest_cores"]
-    others = (_lib.PROTOTYPES, _lib.BUTTERWORTH_PROTOTYPES, _lib.OPTIM_PROTOTYPES, _lib.KNN_PROTOTYPES,
-              _lib.MODULE_PROTOTYPES, _lib.MST_PROTOTYPES, _lib.ACTIVITY_PROTOTYPES, _lib.PAGERANK_PROTOTYPES,
-              _lib.GROUP_PROTOTYPES)
-    assert not any(set(_lib.CORE_PROTOTYPES) & set(o) for o in others)
+    hdr = check_header("cgnn_core.h", _lib.CORE_PROTOTYPES, ["cgnn_ingest_cores_workspace_bytes", "cgnn_ingest_cores"],
+                       [("int32_t* levels", "int32_t levels"), ("int64_t levels_bytes, ", "")])
     assert len(_lib.PROTOTYPES) == 127
-    assert declared(hdr.replace("int32_t* levels", "int32_t levels")) != declared(hdr)
-    assert declared(hdr.replace("int64_t levels_bytes, ", "")) != declared(hdr)
-    assert '#include "cgnn_core.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
     lib = _lib.load()
-    for name, (res, args) in _lib.CORE_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
     for name, value in (("CGNN_CORE_CORENESS", 0), ("CGNN_CORE_ONION_LAYER", 1), ("CGNN_CORE_S_CORENESS", 2),
                         ("CGNN_NUM_CORE_MEASURES", 3), ("CGNN_CORE_MAX_NODES", 1024)):
         assert f"#define {name} {value}\n" in hdr

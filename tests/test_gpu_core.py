@@ -39,44 +39,27 @@ import numpy as np
 import pytest
 import torch
 
-import connectome_gnn_amd as C
-from connectome_gnn_amd import _lib, encoder_choice, ingest
-from connectome_gnn_amd.resident import ResidentDataLoader
+from connectome_gnn_amd import _lib, ingest
+from tests import cohort_kit as K
 from tests import core_data as CD
 from tests import ingest_data as I
 from tests import modules_data as D
 from tests import pagerank_data as PD
+from tests.cohort_kit import DEV, NAN_BITS, bits as _bits, thresholds as _thresholds
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 NAMES = CD.CORE_MEASURES
 IDS, COLS, LDX = [0, 1, 2], [3, 1, 0], 5          # the raw calls write into a wider x; columns 2 and 4 stay
-NAN_BITS = 0x7FC00000
 # every subset and order of the three names
 REQUESTS = [list(p) for r in (1, 2, 3) for p in itertools.permutations(range(3), r)]
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _raw(dev, thr, ids=IDS, cols=COLS, ldx=LDX, want_levels=True):
     """One cgnn_ingest_cores call into a NaN-filled x: (x [S, n, ldx], levels [S, n, 3])."""
     S, n = int(dev.shape[0]), int(dev.shape[1])
-    x = torch.full((S, n, ldx), float("nan"), device=DEV)
     lv = torch.full((S, n, 3), -7, dtype=torch.int32, device=DEV) if want_levels else None
-    num = len(ids)
-    _lib.call("cgnn_ingest_cores", dev, S, n, thr, (ctypes.c_int32 * num)(*ids), num, (ctypes.c_int32 * num)(*cols),
-              ldx, None, 0, *_lib.buf(x), *_lib.buf(lv))
+    x, _ = K.raw("cgnn_ingest_cores", dev, thr, ids, cols, ldx, tail=_lib.buf(lv))
     return x, lv
-
-
-def _thresholds(dev, mats, kw):
-    """(device thresholds, the host's): the same numbers."""
-    host = CD.host_thresholds(mats, kw)
-    thr = ingest.select_thresholds(dev, **kw) if "keep" in kw else torch.zeros(len(mats), device=DEV)
-    assert thr.cpu().tolist() == host
-    return thr, host
 
 
 def _staging(n, E):
@@ -220,20 +203,12 @@ def test_a_grid_of_three_gives_the_bits_of_the_default_grid_and_of_a_second_run(
     mats = torch.cat([PD.cohort(n, seed) for seed in range(3)]).contiguous()
     assert mats.shape[0] == 24
     dev = mats.to(DEV)
-    lib = _lib.load()
 
     def run():
         thr = ingest.select_thresholds(dev, keep=0.1)
         x, lv = _raw(dev, thr)
         return x, lv, ingest.core_measures(dev, keep=0.1)
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
-        few = run()
-    finally:
-        lib.cgnn_set_fused_grid(0)
-    full, again = run(), run()
-    for a, b, c in zip(few, full, again):
-        assert torch.equal(_bits(a), _bits(b)) and torch.equal(_bits(b), _bits(c))
+    few, full = K.check_grid_of_three(run)
     alone = ingest.core_measures(PD.cohort(n).to(DEV), keep=0.1)
     assert torch.equal(_bits(full[2][:8]), _bits(alone)), "a subject's result does not depend on its cohort"
     tail = mats[-8:]
@@ -246,50 +221,27 @@ def test_knn_the_backbone_and_the_group_are_the_call_on_the_sparsified_matrices(
     n = 84
     dev = CD.cohort(n).to(DEV)
     for call in (ingest.core_measures, ingest.core_levels):
-        for mode in ("union", "mutual"):
-            sparse = ingest.knn_sparsify(dev, 8, mode=mode)
-            assert torch.equal(_bits(call(dev, knn=8, knn_mode=mode)), _bits(call(sparse, min_weight=0.0))), mode
-        assert torch.equal(_bits(call(dev, backbone="mst")), _bits(call(ingest.mst_backbone(dev), min_weight=0.0)))
-        united = ingest.mst_backbone(dev, keep=0.1)
-        assert torch.equal(_bits(call(dev, backbone="mst", keep=0.1)), _bits(call(united, min_weight=0.0)))
-        masked = ingest.group_sparsify(dev, "mean", keep=0.1)
-        assert torch.equal(_bits(call(dev, group="mean", keep=0.1)), _bits(call(masked, min_weight=0.0)))
+        K.check_knn(call, dev)
+        K.check_backbone(call, dev)
+        K.check_group(call, dev)
     tree = ingest.core_levels(dev, backbone="mst").cpu()
     assert int(tree[CD.STAR, :, 0].max()) == 1, "a tree has no 2-core"
     assert bool(torch.isfinite(ingest.core_measures(dev, backbone="mst", keep=0.1)).all())
 
 
 def test_the_three_columns_train_on_the_fused_path():
-    S, n = 12, 84
-    r = torch.rand(S, n, n, generator=torch.Generator().manual_seed(4))
-    mats = torch.maximum(r, r.transpose(1, 2)).contiguous().to(DEV)
-    feats = ingest.core_measures(mats, keep=0.1)
-    assert feats.shape == (S, n, 3) and bool(torch.isfinite(feats).all())
+    mats, feats = K.check_trains_on_the_fused_path(lambda m: ingest.core_measures(m, keep=0.1), 3)
     assert bool((feats >= 0).all()) and bool((feats <= 1).all())
     ref = ingest.node_measures(mats, keep=0.1, measures=("degree",))
     assert bool((feats[:, :, 0] <= ref[:, :, 0]).all()), "coreness <= degree: the same correctly rounded quotient"
-    ds = ingest.from_matrices(mats, I.labels(S).to(DEV), keep=0.1, node_features=feats)
-    assert ds.x.shape == (S, n, 3)
-    torch.manual_seed(3)
-    m = C.GCNConnectome(3, 64, dropout=0.0)
-    tr = C.Trainer(m, torch.optim.Adam(m.parameters(), lr=1e-3), device=DEV)
-    ld = ResidentDataLoader(ds, 6, shuffle=True, structure_cache=True)
-    loss = tr.train_epoch(ld)
-    assert loss == loss and abs(loss) != float("inf"), loss
-    assert tr.model.impl_used == "fused" and tr.model._fused_kind == "tile"
-    batch = next(iter(ld))
-    choice = encoder_choice.choose(tr.model, batch, batch.structure())
-    assert choice.kind == "tile" and choice.reason is None, choice
 
 
 # ---- 6: an empty cohort ----
 def test_no_subjects_give_an_empty_tensor_without_a_launch():
     n = 20
     dev = CD.cohort(n).to(DEV)[:0]
-    x = ingest.core_measures(dev, keep=0.1)
-    assert tuple(x.shape) == (0, n, 3) and x.dtype == torch.float32 and x.device.type == "cuda"
-    lv = ingest.core_levels(dev, keep=0.1)
-    assert tuple(lv.shape) == (0, n, 3) and lv.dtype == torch.int32 and lv.device.type == "cuda"
+    K.check_no_subjects(lambda m: ingest.core_measures(m, keep=0.1), dev, 3)
+    K.check_no_subjects(lambda m: ingest.core_levels(m, keep=0.1), dev, 3, torch.int32)
     lib = _lib.load()
     assert lib.cgnn_ingest_cores(None, 0, n, None, (ctypes.c_int32 * 1)(2), 1, (ctypes.c_int32 * 1)(0), 1, None, 0,
                                  None, 0, None, 0, _lib.stream_ptr()) == _lib.CGNN_OK

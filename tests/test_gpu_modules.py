@@ -23,27 +23,21 @@ import numpy as np
 import pytest
 import torch
 
-import connectome_gnn_amd as C
-from connectome_gnn_amd import _lib, encoder_choice, ingest
-from connectome_gnn_amd.resident import ResidentDataLoader
+from connectome_gnn_amd import _lib, ingest
+from tests import cohort_kit as K
 from tests import ingest_data as I
 from tests import measures_data as MD
 from tests import modules_data as D
 from tests import paths_data as P
 from tests import timeseries_data as TS
 from tests import wpaths_data as W
+from tests.cohort_kit import DEV, NAN_BITS, bits as _bits, thresholds as _thresholds
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 NAMES = D.MODULE_MEASURES
 ALL17 = MD.MEASURES + P.PATH_MEASURES + W.WEIGHTED_PATH_MEASURES + NAMES
 IDS, COLS, LDX = [0, 1, 2, 3, 4], [5, 0, 3, 6, 1], 7       # the raw calls write into a wider x; columns 2 and 4 stay
-NAN_BITS = 0x7FC00000
 FORMS = list(itertools.product((False, True), (False, True)))           # (binary, normalize)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _labels(c):
@@ -53,11 +47,9 @@ def _labels(c):
 def _raw(dev, thr, c_dev, M, ids=(), cols=(), ldx=1, profile_flags=None):
     """One cgnn_ingest_modules call into NaN-filled outputs: (x [S, n, ldx] or None, profile [S, n, M] or None)."""
     S, n = int(dev.shape[0]), int(dev.shape[1])
-    x = torch.full((S, n, ldx), float("nan"), device=DEV) if ids else None
     prof = torch.full((S, n, M), float("nan"), device=DEV) if profile_flags is not None else None
-    num = len(ids)
-    _lib.call("cgnn_ingest_modules", dev, S, n, thr, c_dev, M, (ctypes.c_int32 * num)(*ids), num,
-              (ctypes.c_int32 * num)(*cols), ldx, None, 0, *_lib.buf(x), *_lib.buf(prof), profile_flags or 0)
+    x, _ = K.raw("cgnn_ingest_modules", dev, thr, ids, cols, ldx, head=(c_dev, M),
+                 tail=_lib.buf(prof) + (profile_flags or 0,))
     return x, prof
 
 
@@ -68,14 +60,6 @@ def _ratio(got, want):
     if got.numel() == 0:
         return 0.0
     return float(((got.double() - want).abs() / (2.0 ** -24 * want.abs() + 2.0 ** -30)).max())
-
-
-def _thresholds(dev, mats, kw):
-    """(device thresholds, the host's): the same numbers."""
-    host = D.host_thresholds(mats, kw)
-    thr = ingest.select_thresholds(dev, **kw) if "keep" in kw else torch.zeros(len(mats), device=DEV)
-    assert thr.cpu().tolist() == host
-    return thr, host
 
 
 def _check_cohort(mats, dev, c, M, kw, what):
@@ -151,19 +135,11 @@ def test_a_grid_of_three_gives_the_bits_of_the_default_grid_and_of_a_second_run(
     mats = torch.cat([D.cohort(n, seed) for seed in range(50)]).contiguous()
     assert mats.shape[0] == 300
     dev, c = mats.to(DEV), D.case_partition(n, M)
-    lib = _lib.load()
 
     def run():
         return (ingest.node_measures(dev, keep=0.1, measures=NAMES, modules=c),
                 ingest.module_profile(dev, c, keep=0.1, normalize=True))
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
-        few = run()
-    finally:
-        lib.cgnn_set_fused_grid(0)
-    full, again = run(), run()
-    for a, b, d in zip(few, full, again):
-        assert torch.equal(_bits(a), _bits(b)) and torch.equal(_bits(b), _bits(d))
+    few, full = K.check_grid_of_three(run)
     alone = ingest.node_measures(D.cohort(n).to(DEV), keep=0.1, measures=NAMES, modules=c)
     assert torch.equal(_bits(full[0][:6]), _bits(alone)), "a subject's result does not depend on its cohort"
     tail = mats[-6:]
@@ -233,26 +209,11 @@ def test_knn_is_the_call_on_the_sparsified_matrices(mode):
 
 # ---- 5: the profile as node features on the fused path ----
 def test_the_normalised_profile_of_seven_networks_trains_on_the_fused_path():
-    S, n, M = 12, 84, 7
-    r = torch.rand(S, n, n, generator=torch.Generator().manual_seed(4))
-    mats = torch.maximum(r, r.transpose(1, 2)).contiguous().to(DEV)
+    n, M = 84, 7
     c = D.case_partition(n, M)
-    prof = ingest.module_profile(mats, c, keep=0.1, normalize=True)
-    assert prof.shape == (S, n, M) and bool(torch.isfinite(prof).all())
+    _, prof = K.check_trains_on_the_fused_path(lambda m: ingest.module_profile(m, c, keep=0.1, normalize=True), M)
     rows = prof.sum(2)
     assert bool(((rows - 1).abs() < 1e-6).logical_or(rows == 0).all())
-    ds = ingest.from_matrices(mats, I.labels(S).to(DEV), keep=0.1, node_features=prof)
-    assert ds.x.shape == (S, n, M)
-    torch.manual_seed(3)
-    m = C.GCNConnectome(M, 64, dropout=0.0)
-    tr = C.Trainer(m, torch.optim.Adam(m.parameters(), lr=1e-3), device=DEV)
-    ld = ResidentDataLoader(ds, 6, shuffle=True, structure_cache=True)
-    loss = tr.train_epoch(ld)
-    assert loss == loss and abs(loss) != float("inf"), loss
-    assert tr.model.impl_used == "fused" and tr.model._fused_kind == "tile"
-    batch = next(iter(ld))
-    choice = encoder_choice.choose(tr.model, batch, batch.structure())
-    assert choice.kind == "tile" and choice.reason is None, choice
 
 
 # ---- 6: a kept +inf ----
@@ -292,10 +253,8 @@ def test_a_kept_infinity_follows_the_formulas():
 def test_no_subjects_give_empty_tensors_without_a_launch():
     n, M = 20, 3
     dev, c = D.cohort(n).to(DEV)[:0], D.partition(n, M)
-    x = ingest.node_measures(dev, keep=0.1, measures=MIXED, modules=c)
-    assert tuple(x.shape) == (0, n, len(MIXED)) and x.dtype == torch.float32 and x.device.type == "cuda"
-    p = ingest.module_profile(dev, c, keep=0.1, binary=True)
-    assert tuple(p.shape) == (0, n, M) and p.dtype == torch.float32 and p.device.type == "cuda"
+    K.check_no_subjects(lambda m: ingest.node_measures(m, keep=0.1, measures=MIXED, modules=c), dev, len(MIXED))
+    K.check_no_subjects(lambda m: ingest.module_profile(m, c, keep=0.1, binary=True), dev, M)
     lib = _lib.load()
     assert lib.cgnn_ingest_modules(None, 0, n, None, None, M, (ctypes.c_int32 * 1)(4), 1, (ctypes.c_int32 * 1)(0), 1,
                                    None, 0, None, 0, None, 0, 0, _lib.stream_ptr()) == _lib.CGNN_OK

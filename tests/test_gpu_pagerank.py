@@ -39,33 +39,23 @@ import numpy as np
 import pytest
 import torch
 
-import connectome_gnn_amd as C
-from connectome_gnn_amd import _lib, encoder_choice, ingest
-from connectome_gnn_amd.resident import ResidentDataLoader
+from connectome_gnn_amd import _lib, ingest
+from tests import cohort_kit as K
 from tests import ingest_data as I
 from tests import modules_data as D
 from tests import pagerank_data as PD
+from tests.cohort_kit import DEV, NAN_BITS, bits as _bits, thresholds as _thresholds
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 NAMES = PD.CENTRALITY_MEASURES
 IDS, COLS, LDX = [0, 1], [3, 1], 5                # the raw calls write into a wider x; columns 0, 2 and 4 stay
-NAN_BITS = 0x7FC00000
 REQUESTS = [([0], [3]), ([1], [1]), ([1, 0], [1, 3]), ([0], [0]), ([1, 0], [4, 2])]
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _raw(dev, thr, d, ids=IDS, cols=COLS, ldx=LDX):
     """One cgnn_ingest_pagerank call into a NaN-filled x: (x [S, n, ldx], iterations [S])."""
-    S, n = int(dev.shape[0]), int(dev.shape[1])
-    x = torch.full((S, n, ldx), float("nan"), device=DEV)
-    it = torch.full((S,), -7, dtype=torch.int32, device=DEV)
-    num = len(ids)
-    _lib.call("cgnn_ingest_pagerank", dev, S, n, thr, (ctypes.c_int32 * num)(*ids), num, (ctypes.c_int32 * num)(*cols),
-              ldx, float(d), None, 0, *_lib.buf(x), *_lib.buf(it))
+    it = torch.full((int(dev.shape[0]),), -7, dtype=torch.int32, device=DEV)
+    x, _ = K.raw("cgnn_ingest_pagerank", dev, thr, ids, cols, ldx, mid=(float(d),), tail=_lib.buf(it))
     return x, it
 
 
@@ -74,14 +64,6 @@ def _ratio(got, want):
     assert got.dtype == torch.float32 and got.shape == want.shape
     assert bool(torch.isfinite(got).all()) and bool(torch.isfinite(want).all())
     return float(((got.double() - want).abs() / (2.0 ** -24 * want.abs() + 2.0 ** -36)).max())
-
-
-def _thresholds(dev, mats, kw):
-    """(device thresholds, the host's): the same numbers."""
-    host = PD.host_thresholds(mats, kw)
-    thr = ingest.select_thresholds(dev, **kw) if "keep" in kw else torch.zeros(len(mats), device=DEV)
-    assert thr.cpu().tolist() == host
-    return thr, host
 
 
 def _staging(n, E):
@@ -208,20 +190,12 @@ def test_a_grid_of_three_gives_the_bits_of_the_default_grid_and_of_a_second_run(
     mats = torch.cat([PD.cohort(n, seed) for seed in range(3)]).contiguous()
     assert mats.shape[0] == 24
     dev = mats.to(DEV)
-    lib = _lib.load()
 
     def run():
         thr = ingest.select_thresholds(dev, keep=0.1)
         x, it = _raw(dev, thr, 0.85)
         return x, it, ingest.centrality_measures(dev, keep=0.1)
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
-        few = run()
-    finally:
-        lib.cgnn_set_fused_grid(0)
-    full, again = run(), run()
-    for a, b, c in zip(few, full, again):
-        assert torch.equal(_bits(a), _bits(b)) and torch.equal(_bits(b), _bits(c))
+    few, full = K.check_grid_of_three(run)
     alone = ingest.centrality_measures(PD.cohort(n).to(DEV), keep=0.1)
     assert torch.equal(_bits(full[2][:8]), _bits(alone)), "a subject's result does not depend on its cohort"
     tail = mats[-8:]
@@ -252,45 +226,20 @@ def test_a_kept_infinity_makes_the_weighted_column_nan_and_nothing_else():
 def test_knn_and_the_backbone_are_the_call_on_the_sparsified_matrices():
     n = 84
     dev = PD.cohort(n).to(DEV)
-    for mode in ("union", "mutual"):
-        sparse = ingest.knn_sparsify(dev, 8, mode=mode)
-        got = ingest.centrality_measures(dev, knn=8, knn_mode=mode)
-        assert torch.equal(_bits(got), _bits(ingest.centrality_measures(sparse, min_weight=0.0))), mode
-    got = ingest.centrality_measures(dev, backbone="mst")
-    assert torch.equal(_bits(got), _bits(ingest.centrality_measures(ingest.mst_backbone(dev), min_weight=0.0)))
-    got = ingest.centrality_measures(dev, backbone="mst", keep=0.1, damping=0.5)
-    united = ingest.mst_backbone(dev, keep=0.1)
-    assert torch.equal(_bits(got), _bits(ingest.centrality_measures(united, min_weight=0.0, damping=0.5)))
+    K.check_knn(ingest.centrality_measures, dev)
+    got = K.check_backbone(ingest.centrality_measures, dev, damping=0.5)
     assert bool(torch.isfinite(got).all())
 
 
 def test_the_two_columns_train_on_the_fused_path():
-    S, n = 12, 84
-    r = torch.rand(S, n, n, generator=torch.Generator().manual_seed(4))
-    mats = torch.maximum(r, r.transpose(1, 2)).contiguous().to(DEV)
-    feats = ingest.centrality_measures(mats, keep=0.1)
-    assert feats.shape == (S, n, 2) and bool(torch.isfinite(feats).all())
-    assert bool(((feats.sum(1) - 1).abs() <= n * 2.0 ** -24).all())
-    ds = ingest.from_matrices(mats, I.labels(S).to(DEV), keep=0.1, node_features=feats)
-    assert ds.x.shape == (S, n, 2)
-    torch.manual_seed(3)
-    m = C.GCNConnectome(2, 64, dropout=0.0)
-    tr = C.Trainer(m, torch.optim.Adam(m.parameters(), lr=1e-3), device=DEV)
-    ld = ResidentDataLoader(ds, 6, shuffle=True, structure_cache=True)
-    loss = tr.train_epoch(ld)
-    assert loss == loss and abs(loss) != float("inf"), loss
-    assert tr.model.impl_used == "fused" and tr.model._fused_kind == "tile"
-    batch = next(iter(ld))
-    choice = encoder_choice.choose(tr.model, batch, batch.structure())
-    assert choice.kind == "tile" and choice.reason is None, choice
+    mats, feats = K.check_trains_on_the_fused_path(lambda m: ingest.centrality_measures(m, keep=0.1), 2)
+    assert bool(((feats.sum(1) - 1).abs() <= mats.shape[1] * 2.0 ** -24).all())
 
 
 # ---- 6: an empty cohort ----
 def test_no_subjects_give_an_empty_tensor_without_a_launch():
     n = 20
-    dev = PD.cohort(n).to(DEV)[:0]
-    x = ingest.centrality_measures(dev, keep=0.1)
-    assert tuple(x.shape) == (0, n, 2) and x.dtype == torch.float32 and x.device.type == "cuda"
+    K.check_no_subjects(lambda m: ingest.centrality_measures(m, keep=0.1), PD.cohort(n).to(DEV)[:0], 2)
     lib = _lib.load()
     assert lib.cgnn_ingest_pagerank(None, 0, n, None, (ctypes.c_int32 * 1)(1), 1, (ctypes.c_int32 * 1)(0), 1, 0.85,
                                     None, 0, None, 0, None, 0, _lib.stream_ptr()) == _lib.CGNN_OK

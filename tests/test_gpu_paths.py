@@ -24,9 +24,9 @@ from tests import ingest_data as I
 from tests import measures_data as M
 from tests import paths_data as P
 from tests import timeseries_data as TS
+from tests.cohort_kit import DEV, bits as _bits, grid_of_three
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 BOUND = 2.0 ** -22
 SIZES = [1, 2, 3, 5, 20, 31, 32, 33, 63, 64, 65, 84, 96, 97, 130, 360]
 # keep 1.0 at 84 and 97: neighbourhoods of 65 .. 128 nodes (two words a row once renumbered); at 130: beyond 128 as well
@@ -34,10 +34,6 @@ CASES = [(n, 0.1) for n in SIZES] + [(n, keep) for keep in (0.5, 1.0) for n in (
 MIN_WEIGHT = (0.3, 0.5, 0.0, 0.7, -1.0, 0.6)          # the per-subject min_weight= case of test_gpu_measures.py
 COL = {name: c for c, name in enumerate(P.PATH_MEASURES)}
 NINE = M.MEASURES + P.PATH_MEASURES
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _check(mats, thr, got, what, local_nodes=None):
@@ -181,12 +177,8 @@ def test_two_calls_give_the_same_bits(n):
 def test_many_subjects_walk_the_grid_stride(S, n):
     mats = torch.cat([P.recipe(n, seed=seed) for seed in range(-(-S // 6))])[:S].contiguous()
     dev = mats.to(DEV)
-    lib = _lib.load()
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
+    with grid_of_three():
         few = _paths(dev, keep=0.1)
-    finally:
-        lib.cgnn_set_fused_grid(0)
     full = _paths(dev, keep=0.1)
     assert torch.equal(_bits(few), _bits(full))
     assert torch.equal(_bits(full[:6].cpu()), _bits(_got(n, 0.1))), "a subject's result does not depend on its cohort"

@@ -18,46 +18,31 @@ import numpy as np
 import pytest
 import torch
 
-import connectome_gnn_amd as C
-from connectome_gnn_amd import _lib, encoder_choice, ingest
-from connectome_gnn_amd.resident import ResidentDataLoader
+from connectome_gnn_amd import _lib, ingest
+from tests import cohort_kit as K
 from tests import ingest_data as I
 from tests import rw_data as RD
+from tests.cohort_kit import DEV, NAN_BITS, bits as _bits
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-NAN_BITS = 0x7FC00000
 ALL = list(range(8))
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _raw(dev, thr, ids=ALL, cols=ALL, ldx=8, flags=0, short_by=0, expect=_lib.CGNN_OK):
     """One cgnn_ingest_rw call into a NaN-filled x ``[S, n, ldx]`` with the workspace its query asks for, less
     ``short_by`` bytes."""
-    S, n = int(dev.shape[0]), int(dev.shape[1])
-    x = torch.full((S, n, ldx), float("nan"), device=DEV)
-    num = len(ids)
-    arr = (ctypes.c_int32 * num)(*ids)
-    lib = _lib.load()
-    need = lib.cgnn_ingest_rw_workspace_bytes(S, n, arr, num)
+    S, n, num = int(dev.shape[0]), int(dev.shape[1]), len(ids)
+    need = _lib.load().cgnn_ingest_rw_workspace_bytes(S, n, (ctypes.c_int32 * num)(*ids), num)
     assert need >= 0
     work = torch.empty(max(need - short_by, 0), dtype=torch.uint8, device=DEV) if need else None
-    rc = _lib.call("cgnn_ingest_rw", dev, S, n, thr, arr, num, (ctypes.c_int32 * num)(*cols), ldx, flags,
-                   *_lib.buf(work), *_lib.buf(x), accept=(expect,))
+    x, rc = K.raw("cgnn_ingest_rw", dev, thr, ids, cols, ldx, mid=(flags,), work=work, accept=(expect,))
     assert rc == expect
     torch.cuda.synchronize()
     return x, need
 
 
 def _thresholds(dev, mats, keep):
-    """(device thresholds, the host's): the same numbers."""
-    host = RD.host_thresholds(mats, {"keep": keep})
-    thr = ingest.select_thresholds(dev, keep=keep)
-    assert thr.cpu().tolist() == host
-    return thr, host
+    return K.thresholds(dev, mats, {"keep": keep})
 
 
 def _assert_within_bound(got, want, n, what, steps=RD.STEPS):
@@ -197,21 +182,13 @@ def test_a_grid_of_three_gives_the_bits_of_the_default_grid_and_of_a_second_run(
     mats = torch.cat([RD.cohort(n, seed) for seed in range(2)]).contiguous()
     assert mats.shape[0] == 12
     dev = mats.to(DEV)
-    lib = _lib.load()
 
     def run():
         return (ingest.random_walk_encodings(dev, keep=0.1), ingest.random_walk_encodings(dev, keep=0.3, steps=(6, 2)),
                 ingest.random_walk_encodings(dev, keep=0.1, binary=True))
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
-        arr = (ctypes.c_int32 * 1)(7)
-        assert lib.cgnn_ingest_rw_workspace_bytes(12, n, arr, 1) == 6 * 3 * 96 * 96 * 4
-        few = run()
-    finally:
-        lib.cgnn_set_fused_grid(0)
-    full, again = run(), run()
-    for a, b, c in zip(few, full, again):
-        assert torch.equal(_bits(a), _bits(b)) and torch.equal(_bits(b), _bits(c))
+    with K.grid_of_three():
+        assert _lib.load().cgnn_ingest_rw_workspace_bytes(12, n, (ctypes.c_int32 * 1)(7), 1) == 6 * 3 * 96 * 96 * 4
+    few, full = K.check_grid_of_three(run)
     alone = ingest.random_walk_encodings(RD.cohort(n).to(DEV), keep=0.1)
     assert torch.equal(_bits(full[0][:6]), _bits(alone)), "a subject's result does not depend on its cohort"
     tail = mats[6:]
@@ -224,14 +201,9 @@ def test_knn_the_backbone_and_the_group_are_the_call_on_the_sparsified_matrices(
     n = 84
     dev = RD.cohort(n).to(DEV)
     call = ingest.random_walk_encodings
-    for mode in ("union", "mutual"):
-        sparse = ingest.knn_sparsify(dev, 8, mode=mode)
-        assert torch.equal(_bits(call(dev, knn=8, knn_mode=mode)), _bits(call(sparse, min_weight=0.0))), mode
-    assert torch.equal(_bits(call(dev, backbone="mst")), _bits(call(ingest.mst_backbone(dev), min_weight=0.0)))
-    united = ingest.mst_backbone(dev, keep=0.1)
-    assert torch.equal(_bits(call(dev, backbone="mst", keep=0.1)), _bits(call(united, min_weight=0.0)))
-    masked = ingest.group_sparsify(dev, "mean", keep=0.1)
-    assert torch.equal(_bits(call(dev, group="mean", keep=0.1, steps=4)), _bits(call(masked, min_weight=0.0, steps=4)))
+    K.check_knn(call, dev)
+    K.check_backbone(call, dev)
+    K.check_group(call, dev, steps=4)
     tree = call(dev, backbone="mst")
     assert not _bits(tree[:, :, 0::2]).any(), "a tree is bipartite: every odd step is +0.0"
 
@@ -252,32 +224,14 @@ def test_a_short_workspace_is_refused():
 
 # ---- 7: training ----
 def test_the_eight_columns_train_on_the_fused_path():
-    S, n = 12, 84
-    r = torch.rand(S, n, n, generator=torch.Generator().manual_seed(4))
-    mats = torch.maximum(r, r.transpose(1, 2)).contiguous().to(DEV)
-    feats = ingest.random_walk_encodings(mats, keep=0.1)
-    assert feats.shape == (S, n, 8) and bool(torch.isfinite(feats).all())
+    _, feats = K.check_trains_on_the_fused_path(lambda m: ingest.random_walk_encodings(m, keep=0.1), 8)
     assert bool((feats >= 0).all()) and bool((feats <= 1).all())
-    ds = ingest.from_matrices(mats, I.labels(S).to(DEV), keep=0.1, node_features=feats)
-    assert ds.x.shape == (S, n, 8)
-    torch.manual_seed(3)
-    m = C.GCNConnectome(8, 64, dropout=0.0)
-    tr = C.Trainer(m, torch.optim.Adam(m.parameters(), lr=1e-3), device=DEV)
-    ld = ResidentDataLoader(ds, 6, shuffle=True, structure_cache=True)
-    loss = tr.train_epoch(ld)
-    assert loss == loss and abs(loss) != float("inf"), loss
-    assert tr.model.impl_used == "fused" and tr.model._fused_kind == "tile"
-    batch = next(iter(ld))
-    choice = encoder_choice.choose(tr.model, batch, batch.structure())
-    assert choice.kind == "tile" and choice.reason is None, choice
 
 
 # ---- 8: an empty cohort ----
 def test_no_subjects_give_an_empty_tensor_without_a_launch():
     n = 20
-    dev = RD.cohort(n).to(DEV)[:0]
-    x = ingest.random_walk_encodings(dev, keep=0.1, steps=(3, 1))
-    assert tuple(x.shape) == (0, n, 2) and x.dtype == torch.float32 and x.device.type == "cuda"
+    K.check_no_subjects(lambda m: ingest.random_walk_encodings(m, keep=0.1, steps=(3, 1)), RD.cohort(n).to(DEV)[:0], 2)
     lib = _lib.load()
     assert lib.cgnn_ingest_rw(None, 0, n, None, (ctypes.c_int32 * 1)(7), 1, (ctypes.c_int32 * 1)(0), 1, 0, None, 0,
                               None, 0, _lib.stream_ptr()) == _lib.CGNN_OK

@@ -25,18 +25,14 @@ from tests import measures_data as M
 from tests import paths_data as P
 from tests import timeseries_data as TS
 from tests import wpaths_data as W
+from tests.cohort_kit import DEV, bits as _bits, grid_of_three
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-U = 2.0 ** -24
+U =2.0 ** -24
 NAMES = W.WEIGHTED_PATH_MEASURES
 TWELVE = M.MEASURES + P.PATH_MEASURES + NAMES
 CASES = [(5, 0.5), (37, 0.1), (64, 0.3), (65, 0.1), (130, 0.1), (360, 0.1)]
 MIN_WEIGHT = (0.3, 0.5, 0.0)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _check_subject(dist, cols, want, what):
@@ -246,12 +242,8 @@ def test_two_calls_give_the_same_bits(n):
 def test_a_grid_of_three_gives_the_bits_of_the_default_grid(S, n):
     mats = torch.cat([W.recipe(n, seed=seed)[list(W.SUBJECTS)] for seed in range(-(-S // 3))])[:S].contiguous()
     dev = mats.to(DEV)
-    lib = _lib.load()
-    try:
-        assert lib.cgnn_set_fused_grid(3) == _lib.CGNN_OK
+    with grid_of_three():
         few, few_dist = _cols(dev, keep=0.1), ingest.path_lengths(dev, keep=0.1)
-    finally:
-        lib.cgnn_set_fused_grid(0)
     full, full_dist = _cols(dev, keep=0.1), ingest.path_lengths(dev, keep=0.1)
     assert torch.equal(_bits(few), _bits(full)) and torch.equal(_bits(few_dist), _bits(full_dist))
     assert torch.equal(_bits(full[:3].cpu()), _bits(_got(n, 0.1)[1])), "a subject's result does not depend on its cohort"

@@ -3,10 +3,7 @@ for the mean, integer counts for the consistency, numpy for the Fisher mean; the
 ``ingest.group_matrix``, ``ingest.group_sparsify`` and ``group=`` on CPU tensors; the header and the binding of
 cgnn_ingest_group / cgnn_ingest_group_mask; and the seeded cohort that shows what a common topology is for.  No device is
 touched."""
-import ctypes
 import itertools
-import os
-import re
 from fractions import Fraction
 
 import numpy as np
@@ -18,6 +15,7 @@ from connectome_gnn_amd import _lib, ingest
 from tests import group_data as G
 from tests import ingest_data as D
 from tests import knn_data as K
+from tests.abi_header import check_header
 
 NAN, INF = float("nan"), float("inf")
 
@@ -258,47 +256,15 @@ def test_group_sparsify_checks_its_own_arguments():
         ingest.node_measures(m, min_weight=torch.zeros(3))
 
 
-# What tests/test_host_logic.py's comparison of cgnn.h needs, restated for a header without structs.
-_SCALARS = {"int": _lib.I32, "int32_t": _lib.I32, "int64_t": _lib.I64, "uint64_t": _lib.U64, "float": _lib.F32,
-            "double": _lib.F64}
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _ctype(decl, is_return=False):
-    words = decl.replace("*", " * ").split()
-    base = [w for w in words if w != "const"][0]
-    if "*" in words:
-        return _lib.DevPtr
-    return ctypes.c_int if (is_return and base == "int") else _SCALARS[base]
-
-
-def _declared(text):
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-    rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    return {name: (_ctype(ret, True), [_ctype(p.strip()) for p in params.split(",")]) for ret, name, params in rows}
-
-
 def test_the_prototypes_match_their_header_type_by_type():
     """The three entry points are declared in include/cgnn_group.h, which cgnn.h includes, and bound by
     ``_lib.GROUP_PROTOTYPES``: every type, the library's exports, the constants, and the comparison itself against a
     doctored header."""
-    hdr = open(os.path.join(ROOT, "include", "cgnn_group.h")).read()
-    assert _declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.GROUP_PROTOTYPES.items()}
-    assert list(_lib.GROUP_PROTOTYPES) == ["cgnn_ingest_group_workspace_bytes", "cgnn_ingest_group",
-                                           "cgnn_ingest_group_mask"]
-    others = (_lib.PROTOTYPES, _lib.BUTTERWORTH_PROTOTYPES, _lib.OPTIM_PROTOTYPES, _lib.KNN_PROTOTYPES,
-              _lib.MODULE_PROTOTYPES, _lib.MST_PROTOTYPES, _lib.ACTIVITY_PROTOTYPES, _lib.PAGERANK_PROTOTYPES)
-    assert not any(set(_lib.GROUP_PROTOTYPES) & set(o) for o in others)
+    hdr = check_header("cgnn_group.h", _lib.GROUP_PROTOTYPES,
+                       ["cgnn_ingest_group_workspace_bytes", "cgnn_ingest_group", "cgnn_ingest_group_mask"],
+                       [("int64_t S, int32_t n)", "int32_t S, int32_t n)"), ("int32_t statistic, ", ""),
+                        ("const float* group /* [n, n] */,", "")])
     assert len(_lib.PROTOTYPES) == 127, "the main table is as it was"
-    assert _declared(hdr.replace("int64_t S, int32_t n)", "int32_t S, int32_t n)")) != _declared(hdr)
-    assert _declared(hdr.replace("int32_t statistic, ", "")) != _declared(hdr)
-    assert _declared(hdr.replace("const float* group /* [n, n] */,", "")) != _declared(hdr)
-    assert '#include "cgnn_group.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
-    lib = _lib.load()
-    for name, (res, args) in _lib.GROUP_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
     for line in ("#define CGNN_GROUP_MEAN 0\n", "#define CGNN_GROUP_FISHER_MEAN 1\n", "#define CGNN_GROUP_CONSISTENCY 2\n",
                  f"#define CGNN_GROUP_SLICE {_lib.GROUP_SLICE}\n"):
         assert line in hdr, line

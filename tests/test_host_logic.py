@@ -13,6 +13,7 @@ import connectome_gnn_amd as C
 from connectome_gnn_amd import _lib
 from connectome_gnn_amd.graph import shard_slice
 from connectome_gnn_amd.synthetic import NUM_REGIONS, generate_packed, small_world_stats
+from tests import abi_header
 from tests import golden_util as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,35 +52,10 @@ def test_library_exports_every_declared_symbol():
     assert loaded.cgnn_csr_workspace_bytes(-1, 0) < 0          # CGNN_EINVAL, no crash
 
 
-_HEADER_STRUCTS = {"cgnn_tiles": _lib.CgnnTiles, "cgnn_l0src": _lib.CgnnL0Src, "cgnn_bn_tail": _lib.CgnnBnTail,
-                   "cgnn_dw_jobs": _lib.CgnnDwJobs, "cgnn_adam_jobs": _lib.CgnnAdamJobs,
-                   "cgnn_gather_jobs": _lib.CgnnGatherJobs, "cgnn_reduce_jobs": _lib.CgnnReduceJobs}
-_HEADER_SCALARS = {"int": _lib.I32, "int32_t": _lib.I32, "int64_t": _lib.I64, "uint64_t": _lib.U64,
-                   "float": _lib.F32, "double": _lib.F64}
-
-
-def _header_ctype(decl: str, is_return: bool = False):
-    """The ctypes type of one C parameter (or return type) as include/cgnn.h writes it."""
-    words = decl.replace("*", " * ").split()
-    if "*" not in words:
-        base = [w for w in words if w != "const"][0]
-        return ctypes.c_int if (is_return and base == "int") else _HEADER_SCALARS[base]
-    base = [w for w in words[:words.index("*")] if w != "const"][0]
-    if base == "char":
-        return ctypes.c_char_p
-    return ctypes.POINTER(_HEADER_STRUCTS[base]) if base in _HEADER_STRUCTS else _lib.DevPtr
-
-
 def _abi_mismatches(header: str) -> set:
     """Names whose declaration in ``header`` and whose row of _lib.PROTOTYPES differ in the return type or in any
     argument type (or that only one of the two has)."""
-    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-    declared = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
-        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
-        declared[name] = (_header_ctype(ret, True), [_header_ctype(p) for p in params])
+    declared = abi_header.declared(header)
     bad = set(declared) ^ set(_lib.PROTOTYPES)
     for name in set(declared) & set(_lib.PROTOTYPES):
         res, args = _lib.PROTOTYPES[name]
@@ -100,6 +76,19 @@ def test_prototypes_match_the_header_type_by_type():
     assert one in hdr and two in hdr
     doctored = hdr.replace(one, one.replace("int32_t n", "int64_t n")).replace(two, two.replace("int32_t width, ", ""))
     assert _abi_mismatches(doctored) == {"cgnn_rng_advance", "cgnn_bn_reduce"}
+
+
+def test_the_registry_is_cgnn_h_and_the_headers_it_includes():
+    """_lib.HEADERS, which load() binds from: cgnn.h first, then every include/cgnn_*.h that cgnn.h includes, in its
+    order, and nothing else -- a family whose header is included but has no entry would load without argtypes.  Every
+    such header is a file, and no header under include/ is left out of cgnn.h."""
+    included = re.findall(r'^#include "(cgnn_\w+\.h)"', abi_header.read("cgnn.h"), flags=re.M)
+    assert len(included) >= 11 and len(set(included)) == len(included)
+    assert list(_lib.HEADERS) == ["cgnn.h"] + included
+    assert _lib.HEADERS["cgnn.h"] is _lib.PROTOTYPES
+    assert sorted(os.listdir(abi_header.INCLUDE)) == sorted(_lib.HEADERS)
+    with pytest.raises(_lib.CgnnError, match="cgnn_ingest_knn is in the tables of both cgnn_knn.h and cgnn_twice.h"):
+        _lib.check_disjoint({**_lib.HEADERS, "cgnn_twice.h": {"cgnn_ingest_knn": (ctypes.c_int, [])}})
 
 
 def test_devptr_through_a_foreign_call():

@@ -1,15 +1,13 @@
 """The host statement of the k-NN sparsification (tests/knn_data.py) against a brute-force count, a hand-written
 example and the consequences the module docstring lists; the public argument checks of ``ingest.knn_sparsify`` and of
 ``knn=`` on CPU tensors; the header and the binding of cgnn_ingest_knn.  No device is touched."""
-import os
-import re
-
 import pytest
 import torch
 
 from connectome_gnn_amd import _lib, ingest
 from tests import ingest_data as D
 from tests import knn_data as K
+from tests.abi_header import check_header
 
 NAN, INF = float("nan"), float("inf")
 SIZES = (1, 2, 3, 5, 20)
@@ -175,25 +173,8 @@ def test_the_prototype_matches_its_header_type_by_type():
     """cgnn_ingest_knn is declared in include/cgnn_knn.h, which cgnn.h includes, and bound by ``_lib.KNN_PROTOTYPES``:
     the return type and every argument type, the library's export, the constants, and the comparison itself against a
     doctored header."""
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_knn.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.KNN_PROTOTYPES.items()}
-    assert list(_lib.KNN_PROTOTYPES) == ["cgnn_ingest_knn"]
-    assert not set(_lib.KNN_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.BUTTERWORTH_PROTOTYPES) |
-                                           set(_lib.OPTIM_PROTOTYPES))
-    assert declared(hdr.replace("int64_t k, int32_t mode", "int32_t k, int32_t mode")) != declared(hdr)
-    assert '#include "cgnn_knn.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
-    fn = _lib.load().cgnn_ingest_knn
-    res, args = _lib.KNN_PROTOTYPES["cgnn_ingest_knn"]
-    assert fn.restype is res and list(fn.argtypes) == list(args)
+    hdr = check_header("cgnn_knn.h", _lib.KNN_PROTOTYPES, ["cgnn_ingest_knn"],
+                       [("int64_t k, int32_t mode", "int32_t k, int32_t mode")])
     for name, value in (("CGNN_KNN_DIRECTED", 0), ("CGNN_KNN_UNION", 1), ("CGNN_KNN_MUTUAL", 2),
                         ("CGNN_KNN_MAX_NODES", 1024)):
         assert f"#define {name} {value}\n" in hdr

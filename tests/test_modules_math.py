@@ -5,8 +5,6 @@ reaches a launch.
 """
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ from connectome_gnn_amd import _lib, ingest
 from tests import ingest_data as I
 from tests import modules_data as D
 from tests import timeseries_data as TS
+from tests.abi_header import check_header
 
 NAMES = D.MODULE_MEASURES
 
@@ -284,26 +283,10 @@ def test_the_prototypes_match_their_header_type_by_type():
     """The two entry points are declared in include/cgnn_modules.h, which cgnn.h includes, and bound by
     ``_lib.MODULE_PROTOTYPES``: every type, the library's exports, the constants, and the comparison itself against a
     doctored header."""
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_modules.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.MODULE_PROTOTYPES.items()}
-    assert list(_lib.MODULE_PROTOTYPES) == ["cgnn_ingest_modules_workspace_bytes", "cgnn_ingest_modules"]
-    assert not set(_lib.MODULE_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.BUTTERWORTH_PROTOTYPES) |
-                                              set(_lib.OPTIM_PROTOTYPES) | set(_lib.KNN_PROTOTYPES))
-    assert declared(hdr.replace("int32_t M, const", "int64_t M, const")) != declared(hdr)
-    assert '#include "cgnn_modules.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    hdr = check_header("cgnn_modules.h", _lib.MODULE_PROTOTYPES,
+                       ["cgnn_ingest_modules_workspace_bytes", "cgnn_ingest_modules"],
+                       [("int32_t M, const", "int64_t M, const")])
     lib = _lib.load()
-    for name, (res, args) in _lib.MODULE_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
     for name, value in (("CGNN_NUM_MODULE_MEASURES", 5), ("CGNN_MODULE_MAX", 64), ("CGNN_MODULE_MAX_NODES", 1024),
                         ("CGNN_MODULE_PROFILE_BINARY", 1), ("CGNN_MODULE_PROFILE_NORMALIZE", 2)):
         assert f"#define {name} {value}\n" in hdr

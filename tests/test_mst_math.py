@@ -2,9 +2,6 @@
 and weight against scipy, the star of a constant matrix, the connectedness the feature exists for; the public argument
 checks of ``ingest.mst_backbone`` and of ``backbone=`` on CPU tensors; the header and the binding of cgnn_ingest_mst.  No
 device is touched."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -15,6 +12,7 @@ from connectome_gnn_amd import _lib, ingest
 from tests import ingest_data as D
 from tests import knn_data as K
 from tests import mst_data as M
+from tests.abi_header import check_header
 
 NAN, INF = float("nan"), float("inf")
 SIZES = (1, 2, 3, 5, 20, 84)
@@ -202,45 +200,12 @@ def test_backbone_refuses_more_than_1024_nodes_in_every_matrix_entry_point():
             call()
 
 
-# What tests/test_host_logic.py's comparison of cgnn.h needs, restated for a header without structs.
-_SCALARS = {"int": _lib.I32, "int32_t": _lib.I32, "int64_t": _lib.I64, "uint64_t": _lib.U64, "float": _lib.F32,
-            "double": _lib.F64}
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _ctype(decl, is_return=False):
-    words = decl.replace("*", " * ").split()
-    base = [w for w in words if w != "const"][0]
-    if "*" in words:
-        return _lib.DevPtr
-    import ctypes
-    return ctypes.c_int if (is_return and base == "int") else _SCALARS[base]
-
-
-def _declared(text):
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-    rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    return {name: (_ctype(ret, True), [_ctype(p.strip()) for p in params.split(",")]) for ret, name, params in rows}
-
-
 def test_the_prototypes_match_their_header_type_by_type():
     """cgnn_ingest_mst and its workspace query are declared in include/cgnn_mst.h, which cgnn.h includes, and bound by
     ``_lib.MST_PROTOTYPES``: every type, the library's exports, the constant, and the comparison itself against a
     doctored header."""
-    hdr = open(os.path.join(ROOT, "include", "cgnn_mst.h")).read()
-    assert _declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.MST_PROTOTYPES.items()}
-    assert list(_lib.MST_PROTOTYPES) == ["cgnn_ingest_mst_workspace_bytes", "cgnn_ingest_mst"]
-    others = (_lib.PROTOTYPES, _lib.BUTTERWORTH_PROTOTYPES, _lib.OPTIM_PROTOTYPES, _lib.KNN_PROTOTYPES,
-              _lib.MODULE_PROTOTYPES)
-    assert not any(set(_lib.MST_PROTOTYPES) & set(o) for o in others)
-    assert _declared(hdr.replace("int64_t S, int32_t n)", "int32_t S, int32_t n)")) != _declared(hdr)
-    assert _declared(hdr.replace("void* workspace, ", "")) != _declared(hdr)
-    assert '#include "cgnn_mst.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
-    lib = _lib.load()
-    for name, (res, args) in _lib.MST_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    hdr = check_header("cgnn_mst.h", _lib.MST_PROTOTYPES, ["cgnn_ingest_mst_workspace_bytes", "cgnn_ingest_mst"],
+                       [("int64_t S, int32_t n)", "int32_t S, int32_t n)"), ("void* workspace, ", "")])
     assert "#define CGNN_MST_MAX_NODES 1024\n" in hdr
     assert _lib.ABI_VERSION == 2, "the change is additive"
 

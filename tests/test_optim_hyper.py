@@ -4,14 +4,12 @@ captured step keeps of a foreign optimizer's param groups (graphed.hyper_snapsho
 the entry that reads the table (include/cgnn_optim.h, _lib.OPTIM_PROTOTYPES).  No device is touched."""
 import ctypes
 import math
-import os
-import re
 
 import pytest
 import torch
 
 from connectome_gnn_amd import _lib, graphed, optim
-from tests.test_host_logic import ROOT, _header_ctype
+from tests.abi_header import check_header
 
 
 def _params(n=2):
@@ -128,24 +126,10 @@ def test_the_prototype_matches_its_header_type_by_type():
     """cgnn_adam_step_dev is declared in include/cgnn_optim.h, which cgnn.h includes (the butterworth entries' layout:
     tests/test_host_logic.py pins the row count of _lib.PROTOTYPES), bound by _lib.OPTIM_PROTOTYPES and exported; the
     by-value entry keeps its row; the ABI version is unchanged."""
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_optim.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.OPTIM_PROTOTYPES.items()}
-    assert list(_lib.OPTIM_PROTOTYPES) == ["cgnn_adam_step_dev"]
-    assert not set(_lib.OPTIM_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.BUTTERWORTH_PROTOTYPES))
-    assert declared(hdr.replace("int32_t decoupled", "int64_t decoupled")) != declared(hdr)
-    assert '#include "cgnn_optim.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    hdr = check_header("cgnn_optim.h", _lib.OPTIM_PROTOTYPES, ["cgnn_adam_step_dev"],
+                       [("int32_t decoupled", "int64_t decoupled")])
     assert "#define CGNN_ADAM_HYPER_STRIDE 8" in hdr
     lib = _lib.load()
-    fn = lib.cgnn_adam_step_dev
-    res, args = _lib.OPTIM_PROTOTYPES["cgnn_adam_step_dev"]
-    assert fn.restype is res and list(fn.argtypes) == list(args)
     assert _lib.PROTOTYPES["cgnn_adam_step"] == (ctypes.c_int, [ctypes.POINTER(_lib.CgnnAdamJobs), _lib.P, _lib.P, _lib.I32]
                                                  + [_lib.F64] * 5 + [_lib.P])
     assert _lib.ABI_VERSION == 2 and lib.cgnn_abi_version() == 2, "the change is additive"

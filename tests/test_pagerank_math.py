@@ -12,8 +12,6 @@ below measures that).  With two products a step the change of step ``K`` is at m
 stops before it on every case (at most 93 steps at ``d = 0.85``, 23 at ``d = 0.5``).
 """
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -21,6 +19,7 @@ import torch
 
 from connectome_gnn_amd import _lib, ingest
 from tests import pagerank_data as PD
+from tests.abi_header import check_header
 
 NAMES = PD.CENTRALITY_MEASURES
 
@@ -207,26 +206,10 @@ def test_centrality_measures_checks_its_arguments():
 
 # ---- the C ABI ----
 def test_the_prototypes_match_their_header_type_by_type():
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_pagerank.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.PAGERANK_PROTOTYPES.items()}
-    assert list(_lib.PAGERANK_PROTOTYPES) == ["cgnn_ingest_pagerank_workspace_bytes", "cgnn_ingest_pagerank"]
-    assert not set(_lib.PAGERANK_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.MODULE_PROTOTYPES) |
-                                                set(_lib.MST_PROTOTYPES) | set(_lib.ACTIVITY_PROTOTYPES))
-    assert declared(hdr.replace("double damping", "float damping")) != declared(hdr)
-    assert '#include "cgnn_pagerank.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    hdr = check_header("cgnn_pagerank.h", _lib.PAGERANK_PROTOTYPES,
+                       ["cgnn_ingest_pagerank_workspace_bytes", "cgnn_ingest_pagerank"],
+                       [("double damping", "float damping")])
     lib = _lib.load()
-    for name, (res, args) in _lib.PAGERANK_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
     for name, value in (("CGNN_PAGERANK", 0), ("CGNN_PAGERANK_WEIGHTED", 1), ("CGNN_NUM_PAGERANK_MEASURES", 2),
                         ("CGNN_PAGERANK_MAX_NODES", 1024), ("CGNN_PAGERANK_MAX_DAMPING", 0.99)):
         assert f"#define {name} {value}\n" in hdr

@@ -2,9 +2,6 @@
 exactness in fp32; the constants and the tables that must not move; the argument checks of ``ingest.rank_timeseries`` and
 ``rank=``; the header and the binding of cgnn_ingest_rank and the refusals of the C entry points, none of which reaches
 a launch.  No device is touched."""
-import os
-import re
-
 import numpy as np
 import pytest
 import scipy.stats
@@ -13,6 +10,7 @@ import torch
 from connectome_gnn_amd import _lib, ingest
 from tests import censor_data as CD
 from tests import rank_data as RD
+from tests.abi_header import check_header
 
 S = 3
 SHAPES = [(2, 1), (3, 7), (65, 5), (129, 33), (300, 9)]
@@ -163,28 +161,9 @@ def test_rank_timeseries_and_rank_check_their_arguments():
 
 # ---- the C ABI ----
 def test_the_prototypes_match_their_header_type_by_type():
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_rank.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.RANK_PROTOTYPES.items()}
-    others = (_lib.PROTOTYPES, _lib.BUTTERWORTH_PROTOTYPES, _lib.OPTIM_PROTOTYPES, _lib.KNN_PROTOTYPES,
-              _lib.MODULE_PROTOTYPES, _lib.MST_PROTOTYPES, _lib.ACTIVITY_PROTOTYPES, _lib.PAGERANK_PROTOTYPES,
-              _lib.GROUP_PROTOTYPES, _lib.CORE_PROTOTYPES, _lib.RW_PROTOTYPES)
-    assert not any(set(_lib.RANK_PROTOTYPES) & set(o) for o in others)
-    assert declared(hdr.replace("int32_t stride, ", "")) != declared(hdr)
-    assert declared(hdr.replace("const uint8_t* keep", "int32_t keep")) != declared(hdr)
-    assert '#include "cgnn_rank.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    hdr = check_header("cgnn_rank.h", _lib.RANK_PROTOTYPES, ["cgnn_ingest_rank", "cgnn_ingest_rank_masked"],
+                       [("int32_t stride, ", ""), ("const uint8_t* keep", "int32_t keep")])
     lib = _lib.load()
-    for name, (res, args) in _lib.RANK_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
     assert f"#define CGNN_RANK_MAX_FRAMES {ingest.RANK_MAX_FRAMES}\n" in hdr
     assert _lib.ABI_VERSION == 2 and lib.cgnn_abi_version() == 2, "the change is additive"
 

@@ -3,8 +3,6 @@ forms, the split table of the header against ``diag(P^k)``, the fp32 model of th
 bound; the argument checks of ``ingest.random_walk_encodings``; the header and the binding of cgnn_ingest_rw and the
 refusals of the C entry point, none of which reaches a launch.  No device is touched."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import torch
 from connectome_gnn_amd import _lib, ingest
 from tests import measures_data as MD
 from tests import rw_data as RD
+from tests.abi_header import check_header
 
 
 def test_the_constants():
@@ -187,30 +186,10 @@ def test_random_walk_encodings_checks_its_arguments():
 
 # ---- the C ABI ----
 def test_the_prototypes_match_their_header_type_by_type():
-    from tests.test_host_logic import ROOT, _header_ctype
-
-    def declared(text):
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
-        rows = re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(cgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-        return {name: (_header_ctype(ret, True), [_header_ctype(p.strip()) for p in params.split(",")])
-                for ret, name, params in rows}
-
-    hdr = open(os.path.join(ROOT, "include", "cgnn_rw.h")).read()
-    assert declared(hdr) == {k: (r, list(a)) for k, (r, a) in _lib.RW_PROTOTYPES.items()}
-    assert list(_lib.RW_PROTOTYPES) == ["cgnn_ingest_rw_workspace_bytes", "cgnn_ingest_rw"]
-    others = (_lib.PROTOTYPES, _lib.BUTTERWORTH_PROTOTYPES, _lib.OPTIM_PROTOTYPES, _lib.KNN_PROTOTYPES,
-              _lib.MODULE_PROTOTYPES, _lib.MST_PROTOTYPES, _lib.ACTIVITY_PROTOTYPES, _lib.PAGERANK_PROTOTYPES,
-              _lib.GROUP_PROTOTYPES, _lib.CORE_PROTOTYPES)
-    assert not any(set(_lib.RW_PROTOTYPES) & set(o) for o in others)
+    hdr = check_header("cgnn_rw.h", _lib.RW_PROTOTYPES, ["cgnn_ingest_rw_workspace_bytes", "cgnn_ingest_rw"],
+                       [("int32_t flags, ", ""), ("const int32_t* steps", "int32_t steps")])
     assert len(_lib.PROTOTYPES) == 127
-    assert declared(hdr.replace("int32_t flags, ", "")) != declared(hdr)
-    assert declared(hdr.replace("const int32_t* steps", "int32_t steps")) != declared(hdr)
-    assert '#include "cgnn_rw.h"' in open(os.path.join(ROOT, "include", "cgnn.h")).read()
     lib = _lib.load()
-    for name, (res, args) in _lib.RW_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
     for name, value in (("CGNN_RW_MAX_STEPS", ingest.RW_MAX_STEPS), ("CGNN_RW_MAX_NODES", ingest.RW_MAX_NODES),
                         ("CGNN_RW_BINARY", _lib.RW_BINARY)):
         assert f"#define {name} {value}\n" in hdr
