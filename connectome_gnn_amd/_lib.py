@@ -361,6 +361,12 @@ RANK_PROTOTYPES = {
 }
 
 
+# The entry point that include/cgnn_kendall.h declares (cgnn.h includes it), in the same form.
+KENDALL_PROTOTYPES = {
+    "cgnn_ingest_kendall": (c_int, [P, I64, I32, I32, I32, P, I64, P, I64, P]),
+}
+
+
 class CgnnError(RuntimeError):
     pass
 
@@ -381,6 +387,7 @@ HEADERS = {
     "cgnn_core.h": CORE_PROTOTYPES,
     "cgnn_rw.h": RW_PROTOTYPES,
     "cgnn_rank.h": RANK_PROTOTYPES,
+    "cgnn_kendall.h": KENDALL_PROTOTYPES,
 }
 
 

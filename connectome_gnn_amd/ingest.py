@@ -594,8 +594,31 @@ unfolded to ``[U, L]``; ranking is an argument beside ``kind``, not a kind, so `
 partial Spearman correlation.  The ranked series is one temporary ``[U, L, n]``: the size of the input without a window,
 ``W L / T`` times it with one; it is freed before the call returns.  One launch (csrc/rank.hip): persistent workgroups
 over (unit, 4 adjacent columns), the columns staged in LDS as (key, frame) pairs, a wave sorting a column (bitonic), tie
-runs by neighbour comparison and two scans; no workspace, no atomics, no read-back.  Left out: Kendall's tau, rank-based
-inverse-normal scores, units of more than 4096 frames.
+runs by neighbour comparison and two scans; no workspace, no atomics, no read-back.  Left out: rank-based inverse-normal
+scores, units of more than 4096 frames.
+
+Kendall's tau: the other rank estimator, concordant minus discordant pairs of frames, with a proper
+treatment of ties.  Over the pairs ``k = (s < t)`` of a unit's kept frames and ``a_ik = sign(x_si - x_ti)``, ``G = A^T A``
+is an integer Gram matrix: ``G_ij`` is concordant minus discordant, ``G_ii = L_u (L_u - 1) / 2 - n1_i`` the pairs not tied
+in column ``i``, and ``tau_b(i, j) = G_ij / sqrt(G_ii G_jj)``: the tie correction is the diagonal of the same product.
+``kendall_counts(timeseries, window=, stride=, sample_mask=)`` gives ``G``, int32 ``[U, n, n]``, exact and bit-symmetric;
+``kendall_matrices(..., absolute=)`` gives tau-b, float32, ``fp32(G_ij / sqrt(G_ii G_jj))`` formed in fp64 and rounded
+once: ``scipy.stats.kendalltau``.  The diagonal is exactly 1; a column that is constant over its kept frames
+(``G_ii == 0``) is an exact zero row and column, diagonal included -- the correlation's constant-ROI rule, where scipy
+gives NaN; a column with a NaN in a kept frame has ``G_ii = -1`` and zeros elsewhere in its row and column, NaN in the
+matrices, and touches nothing else; a unit with fewer than two kept frames is all zeros; a censored frame takes part in
+no pair and is never looked at; ``|tau| <= 1``.  The comparisons are the ranking's: the calls rank first (the path
+``rank=True`` takes, the ranked series ``[U, L, n]`` being the one temporary) and the kernel compares 16-bit keys, twice
+the mid-ranks, so ``L <= KENDALL_MAX_FRAMES = 4096``.  ``kendall=True`` of ``correlation_matrices`` and
+``from_timeseries`` is an argument beside ``rank`` and ``kind``, not a kind: bit for bit ``kendall_matrices``, with
+``kind="partial"`` and a float or ``[U]`` shrinkage ``partial_correlation`` of the signed tau matrices written over them
+(a normalised Gram matrix is positive semidefinite), handed to every edge choice and to ``measures=`` unchanged.  It is
+refused with ``rank=True`` (tau is a function of the ranks alone) and with ``shrinkage="ledoit_wolf"`` (a statement about
+the frames of a Pearson matrix).  Launches (csrc/kendall.hip): the ranking; the counts, persistent workgroups over (unit,
+pair of 96-column tiles) that form the sign bytes of 64-frame block pairs once in LDS and multiply them on the int8 matrix
+pipe (``v_mfma_i32_16x16x64_i8``, int32 sums: the same bits on every run and for every grid, no atomics); and the
+normalisation, which without a request for the counts runs in place over them.  Left out: tau-a and tau-c, p-values,
+units of more than 4096 frames.
 """
 from __future__ import annotations
 
@@ -648,6 +671,7 @@ CORE_MAX_NODES = 1024                                 # CGNN_CORE_MAX_NODES: the
 RW_MAX_STEPS = 8                                      # CGNN_RW_MAX_STEPS: M2, M3 and M4 reach step 8
 RW_MAX_NODES = 1024                                   # CGNN_RW_MAX_NODES: the fp32 row sums of a subject live in LDS
 RANK_MAX_FRAMES = 4096                                # CGNN_RANK_MAX_FRAMES: a unit's (key, frame) pairs of 4 columns must fit LDS
+KENDALL_MAX_FRAMES = 4096                             # CGNN_KENDALL_MAX_FRAMES: keys 2 x mid-rank <= 8192 in 16 bits, counts < 2^23
 
 
 class _Family(NamedTuple):
@@ -1452,10 +1476,15 @@ def partial_correlation(matrices: torch.Tensor, *, shrinkage=0.0, absolute=False
 
 
 def _connectivity(timeseries: torch.Tensor, series: _Series, windowed: bool, absolute: bool, kind: str, shrinkage,
-                  keep=None) -> torch.Tensor:
+                  keep=None, kendall=False) -> torch.Tensor:
     """The matrices of a valid request: the correlations, or the partial correlations of the signed correlations
     written over them (no second cohort-sized tensor).  A shrinkage named in SHRINKAGES is estimated in between, from
-    the frames, the statistics and the signed correlations."""
+    the frames, the statistics and the signed correlations.  ``kendall``: Kendall's tau-b stands where Pearson's
+    correlation does."""
+    if kendall:
+        signed = kind != "correlation"
+        matrices = _kendall(timeseries, series, windowed, keep, absolute and not signed, False, True)[1]
+        return _partial(matrices, series.S * series.W, series.n, shrinkage, absolute, matrices) if signed else matrices
     if kind == "correlation":
         return _correlate(timeseries, series, windowed, absolute, keep)[0]
     matrices, stats = _correlate(timeseries, series, windowed, False, keep)
@@ -1522,6 +1551,74 @@ def rank_timeseries(timeseries: torch.Tensor, *, window=None, stride=None, sampl
     return _rank_series(timeseries, series, window is not None, keep, out)
 
 
+def _check_kendall(kendall, rank: bool, shrinkage, L: int) -> bool:
+    """A valid kendall= beside a valid rank= and a shrinkage that ``_check_kind`` has passed, for units of L frames."""
+    if not isinstance(kendall, bool):
+        raise TypeError(f"kendall must be a bool, got {type(kendall).__name__}")
+    if kendall:
+        if rank:
+            raise ValueError("kendall=True with rank=True: Kendall's tau is a function of the ranks alone, so the ranked "
+                             "call would give the same matrix; leave rank=False")
+        if isinstance(shrinkage, str):
+            raise ValueError(f"kendall=True with shrinkage={shrinkage!r}: that estimate is a statement about the frames "
+                             "of a Pearson correlation matrix; give a float or a [U] tensor")
+        _check_kendall_frames(L)
+    return kendall
+
+
+def _check_kendall_frames(L: int) -> None:
+    if L > KENDALL_MAX_FRAMES:
+        raise ValueError(f"Kendall's tau takes units of at most KENDALL_MAX_FRAMES = {KENDALL_MAX_FRAMES} frames (the "
+                         f"keys are twice the mid-ranks in 16 bits and the ranking's own bound is the same), got {L}: "
+                         "rank shorter windows")
+
+
+def _kendall(timeseries: torch.Tensor, series: _Series, windowed: bool, keep, absolute: bool, counts: bool,
+             matrices: bool) -> tuple:
+    """cgnn_ingest_kendall of a valid request on resident data: (the counts int32 ``[U, n, n]`` or None, tau float32
+    ``[U, n, n]`` or None).  The ranked series is the one temporary; without ``counts`` they are formed in the bytes
+    of the matrices."""
+    ranked, units, _ = _ranked(timeseries, series, windowed, keep)
+    U, L, n = units[:3]
+    dev = timeseries.device
+    g = torch.empty(U, n, n, dtype=torch.int32, device=dev) if counts else None
+    tau = torch.empty(U, n, n, dtype=torch.float32, device=dev) if matrices else None
+    if U:
+        _call(dev, "cgnn_ingest_kendall", ranked, U, L, n, int(bool(absolute)), *_lib.buf(g), *_lib.buf(tau))
+    del ranked
+    return g, tau
+
+
+def _kendall_request(timeseries, window, stride, sample_mask) -> tuple:
+    """(series, windowed, keep) of a valid request of the two Kendall calls, on resident data."""
+    series = _check_timeseries(timeseries, window, stride)
+    _check_kendall_frames(series.L)
+    keep = _check_sample_mask(sample_mask, series.S, series.T, timeseries.device)
+    _require_resident(timeseries, *_SERIES)
+    return series, window is not None, keep
+
+
+def kendall_counts(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None) -> torch.Tensor:
+    """``G = A^T A`` of every unit (module docstring): int32 ``[U, n, n]`` on the time series' device, the units
+    ``correlation_matrices``'s.  ``G_ij`` is concordant minus discordant pairs of kept frames, ``G_ii`` the pairs not
+    tied in column ``i``; exact and bit-symmetric.  A unit with fewer than two kept frames is all zeros; a column with a
+    NaN in a kept frame has ``G_ii = -1`` and zeros elsewhere in its row and column.  Two launches on resident data (the
+    ranking, the counts); the ranked series ``[U, L, n]`` is the one temporary.  ``L <= KENDALL_MAX_FRAMES``."""
+    series, windowed, keep = _kendall_request(timeseries, window, stride, sample_mask)
+    return _kendall(timeseries, series, windowed, keep, False, True, False)[0]
+
+
+def kendall_matrices(timeseries: torch.Tensor, *, window=None, stride=None, sample_mask=None,
+                     absolute=False) -> torch.Tensor:
+    """Kendall's tau-b of the ROI columns of every unit (module docstring): float32 ``[U, n, n]``,
+    ``fp32(G_ij / sqrt(G_ii G_jj))`` in fp64 rounded once, ``scipy.stats.kendalltau``.  The diagonal is exactly 1; a
+    column that is constant over its kept frames is an exact zero row and column, diagonal included (scipy: NaN); a NaN
+    column is NaN in its row and column.  Three launches on resident data (the ranking, the counts written into the
+    result's own bytes, the normalisation in place); the ranked series is the one temporary."""
+    series, windowed, keep = _kendall_request(timeseries, window, stride, sample_mask)
+    return _kendall(timeseries, series, windowed, keep, absolute, False, True)[1]
+
+
 def _check_labels_and_features(labels, S: int, node_features, letter: str, units: int, n: int) -> None:
     """``labels`` int64 ``[S]``; ``node_features`` None or float32 ``[units, n, F]``, ``letter`` naming the units."""
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.long or labels.shape != (S,):
@@ -1555,7 +1652,7 @@ def ledoit_wolf_shrinkage(timeseries: torch.Tensor, *, window=None, stride=None,
 
 
 def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, absolute=False, kind="correlation",
-                         shrinkage=0.0, sample_mask=None, rank=False) -> torch.Tensor:
+                         shrinkage=0.0, sample_mask=None, rank=False, kendall=False) -> torch.Tensor:
     """Pearson correlation of the ROI columns of every unit: ``[U, n, n]`` float32 on the time series' device
     (module docstring).  Two launches on resident data; the only temporary is ``[U, n, 2]`` statistics.
     ``kind="partial"`` gives ``partial_correlation`` of the signed correlations at ``shrinkage``, written in place
@@ -1567,24 +1664,30 @@ def correlation_matrices(timeseries: torch.Tensor, *, window=None, stride=None, 
     ``rank=True`` gives Spearman's rank correlation (with ``kind="partial"`` the partial one): bit for bit this call
     without a window on ``rank_timeseries(timeseries, window=, stride=, sample_mask=)`` and the mask's windows
     ``[U, L]``.  One more launch; the ranked series ``[U, L, n]`` is one more temporary -- the size of the input without
-    a window, ``W L / T`` times it with one -- freed before the call returns.  ``L <= RANK_MAX_FRAMES``."""
+    a window, ``W L / T`` times it with one -- freed before the call returns.  ``L <= RANK_MAX_FRAMES``.
+    ``kendall=True`` gives Kendall's tau-b, bit for bit ``kendall_matrices(timeseries, ...)``, and with
+    ``kind="partial"`` and a float or ``[U]`` shrinkage ``partial_correlation`` of the signed tau matrices (positive
+    semidefinite: normalised Gram matrices), written over them.  Not with ``rank=True`` (tau is a function of the ranks
+    alone) and not with ``shrinkage="ledoit_wolf"`` (an estimate for Pearson matrices).  ``L <= KENDALL_MAX_FRAMES``."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     rank = _check_rank(rank, L)
     shrinkage = _check_kind(kind, shrinkage, n, L, S * W, timeseries)
+    kendall = _check_kendall(kendall, rank, shrinkage, L)
     keep = _check_sample_mask(sample_mask, S, T, timeseries.device)
     _require_resident(timeseries, *_SERIES)
     windowed = window is not None
     if rank:
         timeseries, series, keep = _ranked(timeseries, series, windowed, keep)
         windowed = False
-    return _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, keep)
+    return _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, keep, kendall)
 
 
 def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None, num_edges=None, min_weight=None,
                     window=None, stride=None, absolute=False, node_features=None, measures=None,
                     kind="correlation", shrinkage=0.0, sample_mask=None, knn=None,
-                    knn_mode="union", modules=None, backbone=None, group=None, rank=False) -> RaggedPackedDataset:
+                    knn_mode="union", modules=None, backbone=None, group=None, rank=False,
+                    kendall=False) -> RaggedPackedDataset:
     """``from_matrices(correlation_matrices(timeseries, ...), labels.repeat_interleave(W), ...)``: one graph per
     unit, every window of a subject carrying the subject's label.  ``labels`` is int64 ``[S]``; ``node_features``,
     if given, is ``[U, n, F]``; a ``min_weight`` tensor is ``[U]``; ``measures`` is ``from_matrices``'s; ``kind`` and
@@ -1595,12 +1698,15 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     connectivity temporary becomes the united graph in place (with ``knn=`` the tree is one more temporary).  ``group``
     is ``from_matrices``'s, its units the windows: the connectivity temporary is masked to the group's edges in place.
     ``rank`` is ``correlation_matrices``'s: Spearman connectivity; the ranked series ``[U, L, n]`` is a temporary beside
-    the connectivity one (``W L / T`` times the input with a window) and is freed before the dataset is built."""
+    the connectivity one (``W L / T`` times the input with a window) and is freed before the dataset is built.
+    ``kendall`` is ``correlation_matrices``'s: Kendall's tau-b connectivity, handed to every edge choice and to
+    ``measures=`` unchanged; its ranked temporary is freed before the edges are chosen."""
     series = _check_timeseries(timeseries, window, stride)
     S, T, n, L, _, W = series
     U = S * W
     rank = _check_rank(rank, L)
     shrinkage = _check_kind(kind, shrinkage, n, L, U, timeseries)
+    kendall = _check_kendall(kendall, rank, shrinkage, L)
     ids = _check_measures_argument(measures, node_features)
     _check_path_size(ids, n)
     _check_modules_argument(ids, modules, n)
@@ -1612,7 +1718,7 @@ def from_timeseries(timeseries: torch.Tensor, labels: torch.Tensor, *, keep=None
     if rank:
         timeseries, series, sample_mask = _ranked(timeseries, series, windowed, sample_mask)
         windowed = False
-    matrices = _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, sample_mask)
+    matrices = _connectivity(timeseries, series, windowed, absolute, kind, shrinkage, sample_mask, kendall)
     del timeseries                                    # (the ranked temporary, under rank=True)
     choice = dict(keep=keep, num_edges=num_edges, min_weight=min_weight)       # the caller's, as they came
     if edges.sparsify:

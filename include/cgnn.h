@@ -1370,5 +1370,6 @@ int cgnn_head_loss_f32(const float* P, int32_t B, int32_t H, int32_t H2, int32_t
 #include "cgnn_core.h"
 #include "cgnn_rw.h"
 #include "cgnn_rank.h"
+#include "cgnn_kendall.h"
 
 #endif /* CGNN_H */
